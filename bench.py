@@ -3,10 +3,12 @@
 (training/train_maskgit_imagenet.py:405-452: VQGAN encode -> cosine-schedule mask -> MaskGitTransformer fwd/bwd ->
 AdamW), 256x256 synthetic images, bs=64 per GPU, random-init weights, 1..8 GPUs data-parallel over RCCL.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  Default workload = BASELINE.json configs[1]: configs/imagenet.yaml transformer
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config); --full adds everything else this script measures (below), --dump-outputs DIR writes
+what the last timed step computed (dump_outputs).  Default workload = BASELINE.json configs[1]: configs/imagenet.yaml transformer
 (hidden 768, 24 layers, 16 heads, vocab 2048 — SURVEY.md D1 "B"), bf16 compute for the transformer (the reference's
 autocast regime) and the frozen VQGAN tokenizer in its f32-class "bf16x3" mode: f32 activations, every product computed
 as 3 bf16 MFMAs with f32 accumulation (error <= 2^-16 per product).  The reference keeps the VQGAN in f32 tensors, and
@@ -15,7 +17,7 @@ enable_tf32); gfx950 has no xf32 MFMA, bf16x3 is the tighter CDNA4 counterpart (
 to f32 near-ties: tests/test_gpu_models.py::test_vq_indices_over_bench_batch_vs_oracle; the count over this run's CPU-baseline
 images is in cpu_baseline.vq_index_mismatches).
 
-The line carries
+With --full the line also carries (--no-extra then drops the secondary legs, --no-cpu-baseline the cpu_baseline block)
   roofline      the dominant kernel (live HIP-event timing of every launch of one instrumented step) against its roof; `traffic`
                 = HBM bytes per launch of that kernel from the committed PMC passes (profiles/r06_traffic.json, FETCH_SIZE x 2
                 + WRITE_SIZE as /opt/skills/guides/MI355X_MICROARCH.md prescribes), null when no such profile is in the tree
@@ -84,6 +86,25 @@ def synthetic_batch(bs, device, seed):
     px = torch.rand(bs, 3, 256, 256, generator=g)
     cls = torch.randint(0, 1000, (bs,), generator=g)
     return px.to(device), cls.to(device)
+
+
+def dump_outputs(out_dir, loss, mask_prob, model, opt, n_sample=1 << 20):
+    """--dump-outputs: what the last timed step returned to its caller (loss [1], mask_prob [B]) and the state it left in the
+    caller's objects: the updated transformer parameters and AdamW's first moment (this step's gradient enters it with weight 0.1),
+    each as the same fixed, seeded sample of n_sample elements of the parameters concatenated in optimizer order.  float32, 8 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for g in opt.param_groups for p in g["params"]]
+    state = opt.state_dict()["state"]
+    n = sum(p.numel() for p in params)
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, size=min(n, n_sample), replace=False))).to(params[0].device)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().float().reshape(-1) for p in params])
+        flat_m = torch.cat([state[i]["exp_avg"].float().reshape(-1) for i in range(len(params))])
+        arrays = {"loss": loss.detach().float().reshape(1), "mask_prob": mask_prob.detach().float().reshape(-1),
+                  "transformer_params_sample": flat_p[idx], "adamw_exp_avg_sample": flat_m[idx]}
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), a.cpu().numpy().astype(np.float32))
+    del flat_p, flat_m
 
 
 def vqgan_roundtrip(device, bs):
@@ -501,6 +522,77 @@ def traffic_of(kernel_family):
     return None, None
 
 
+def instrumented_step_figures(args, prof, prof_bytes, tr_ms, parity, extra):
+    """--full: the roofline block of the line (returned) and the transformer / tokenizer / ceiling figures (added to `extra`) from the
+    profile leg of run(): the instrumented step, the transformer fwd + bwd alone, the measured parity of the benched mode"""
+    # per-kernel roofline from live HIP-event timings of one instrumented step
+    agg = {}
+    for name, work, t, kind in prof:
+        a = agg.setdefault((name, kind), [0.0, 0.0, 0])
+        a[0] += work; a[1] += t; a[2] += 1
+    mfma = {k[0]: v for k, v in agg.items() if k[1] == "flop"}
+    hbm = {k[0]: v for k, v in agg.items() if k[1] == "byte"}
+    kinds = {k: {"launches": v[2], "ms_total": round(v[1], 3), "avg_us": round(v[1] / v[2] * 1e3, 1),
+                 "tflops": round(v[0] / (v[1] * 1e-3) / 1e12, 1)} for k, v in sorted(mfma.items(), key=lambda kv: -kv[1][1])}
+    hbm_kinds = {k: {"launches": v[2], "ms_total": round(v[1], 3), "GBps": round(v[0] / (v[1] * 1e-3) / 1e9, 1),
+                     "frac_of_8TBps": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK, 3)} for k, v in sorted(hbm.items(), key=lambda kv: -kv[1][1])}
+    dname, (dfl, dms, dn) = max(mfma.items(), key=lambda kv: kv[1][1])
+    x3 = dname.startswith("conv_bf16x3")
+    peak = round(PEAK["bf16"] / 3.0, 1) if x3 else PEAK["bf16" if "bf16" in dname else "f32"]
+    ach = dfl / (dms * 1e-3) / 1e12
+    traffic, tnote = traffic_of(dname)
+    roofline = {"bound": "mfma", "kernel": dname, "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(ach / peak, 4), "traffic": traffic, "launches_per_step": dn, "avg_launch_us": round(dms / dn * 1e3, 1),
+                "peak_basis": ("issued bf16 MFMA / 3: 2500 dense bf16 TFLOP/s divided by the three bf16 MFMAs the bf16x3 algorithm issues "
+                               "per f32 product; `achieved` counts ALGORITHMIC flops (2*B*H*W*Cout*9*Cin), executed_mfma_tflops the issued "
+                               "ones; against the plain 2500 peak frac would be frac/3") if x3 else "dense MFMA peak of the operand dtype",
+                "executed_mfma_tflops": round(ach * (3 if x3 else 1), 1),
+                "two_kernel_route": ({"conv_achieved": round(prof_bytes["__unfused__"]["conv_tflops"], 1),
+                                      "conv_frac": round(prof_bytes["__unfused__"]["conv_tflops"] / peak, 4),
+                                      "conv_ms_per_step": round(prof_bytes["__unfused__"]["conv_ms"], 3),
+                                      "groupnorm_apply_ms_per_step": round(prof_bytes["__unfused__"]["groupnorm_ms"], 3),
+                                      "what": "the same tokenizer pass with MUSE_GN_FUSE=0: bare patch-slab convolution + separate GroupNorm apply"}
+                                     if (dname == "conv_bf16x3_dma" and "__unfused__" in prof_bytes) else None),
+                "note": ("since round 3 this kernel also normalises its input (GroupNorm + SiLU + bf16x3 split inside the convolution, "
+                         "muse_conv2d_nhwc_gn_split2): `achieved` still counts the convolution's flops only, over a launch that now contains "
+                         "the former 5.3 ms / step GroupNorm apply pass - the fraction fell 0.56 -> ~0.50 while the step got 2.6 ms shorter "
+                         "(DESIGN.md section 5)") if dname == "conv_bf16x3_dma" else None,
+                "algorithmic_bytes_per_launch": round(prof_bytes[dname] / dn) if dname in prof_bytes else None,
+                "traffic_source": tnote,
+                "per_kernel": kinds, "hbm_bound_kernels": hbm_kinds}
+    tr_tf = 3 * GF_FWD[args.config] * args.batch / tr_ms   # GFLOP / ms = TFLOP/s
+    vq_hbm = [v for k, v in hbm.items() if k in ("groupnorm_silu", "avgpool2x2")]
+    vq_bytes, vq_ms = sum(v[0] for v in vq_hbm), sum(v[1] for v in vq_hbm)
+    extra.update({"transformer_fwd_bwd_ms": round(tr_ms, 2), "transformer_tflops": round(tr_tf, 1),
+                  "transformer_mfma_frac": round(tr_tf / PEAK["bf16"], 4),
+                  "vqgan_hbm_GBps": round(vq_bytes / (vq_ms * 1e-3) / 1e9, 1) if vq_ms else None,
+                  "vqgan_hbm_frac": round(vq_bytes / (vq_ms * 1e-3) / 1e9 / HBM_PEAK, 4) if vq_ms else None,
+                  "vqgan_hbm_note": "GroupNorm+SiLU and 2x2 pooling kernels of the encoder: algorithmic bytes (each operand once) / their time / 8 TB/s",
+                  "mfma_ms_in_instrumented_step": round(sum(v[1] for v in mfma.values()), 2),
+                  "hbm_kernel_ms_in_instrumented_step": round(sum(v[1] for v in hbm.values()), 2),
+                  "measured_parity_bf16_vs_f32_mode": {k: (round(v, 8) if isinstance(v, float) else v) for k, v in parity.items()}})
+    if args.config == "B" and args.batch == 64:
+        # VERDICT r5 item 3: per family the time its BINDING resource implies (derivation and sources: profiles/r06_ceiling.md) next to this
+        # run's serial time; a ratio above 1.15 has its measured decomposition there
+        def _ms(*names):
+            return round(sum(kinds[n]["ms_total"] for n in names if n in kinds) + sum(hbm_kinds[n]["ms_total"] for n in names if n in hbm_kinds), 3)
+        ceil_rows = {
+            "conv_bf16x3_dma": ("MFMA issue at the clock the kernel holds (1.72 GHz, power-limited): 3 x 8.155 TFLOP / (2.5 PF x 1.72 / 2.4)", 13.7,
+                                _ms("conv_bf16x3_dma")),
+            "gemm_fwd_dx": ("K loop bound by the operand stream from L2 into LDS (2500 cycles per K-tile against 2048 of MFMA: 26-28 B/clk/CU delivered, 32 needed) + "
+                            "whole 256^2 tiles on 256 CUs + 82 us tile change per layer "
+                            "(46 us register epilogue + 36 us stores, ablation)", 13.1, _ms("gemm_bf16_NN", "gemm_bf16_NT")),
+            "gemm_dw": ("the same K loop at K = 16448, five slices alone on the chip", 5.9, _ms("gemm_bf16_TT")),
+            "attention": ("HBM floor of q, k, v, o (+ dO, dq, dk, dv) at 6.3 TB/s", 1.15, _ms("attn_fwd_bf16", "attn_bwd_bf16")),
+            "row_kernels": ("HBM streaming at the 6.0 TB/s a three-operand stream reaches on this chip", 8.9,
+                            round(sum(v["ms_total"] for v in hbm_kinds.values()), 3)),
+        }
+        extra["ceiling"] = {"doc": "profiles/r06_ceiling.md",
+                            "families": {k: {"binding": b, "implied_ms": i, "measured_ms": m, "ratio": round(m / i, 2) if m else None}
+                                         for k, (b, i, m) in ceil_rows.items()}}
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -511,13 +603,18 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--grad-dtype", default="f32", choices=["f32", "bf16"], help="gradient all-reduce payload (N > 1)")
     ap.add_argument("--no-prefetch", action="store_true", help="encode each batch inline instead of one step ahead on a second stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (config A / 4 / 5, tokenizer variants)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: instrumented-step roofline, measured parity of the mode, "
+                                                         "ceiling table, secondary legs, CPU baseline, data-parallel diagnostics")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="(with --full) skip the secondary legs (config A / 4 / 5, tokenizer variants)")
     ap.add_argument("--uvit-leg", default=None, help="internal: run one config-4 leg 'batch,seq,steps' and print its JSON")
     ap.add_argument("--device", type=int, default=None, help="internal: GPU index of a secondary leg (default: LOCAL_RANK or 0)")
     ap.add_argument("--leg", default=None, help="internal: run one secondary leg ('run,<cfg>,<vq>,<mode>,<steps>,<batch>' | 'vqgan,<batch>' | "
                                                 "'taming,<batch>') and print its JSON")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.uvit_leg:
         parts = args.uvit_leg.split(",")
         b, sq, st = (int(x) for x in parts[:3])
@@ -569,7 +666,7 @@ def main():
     comm_info, parity = {}, {}
 
     def run(cfg_name, vq_dtype, steps, warmup, profile=False, tokens_given=False, inline_tokenizer=False, use_reducer=True,
-            transformer_dtype=torch.bfloat16):
+            transformer_dtype=torch.bfloat16, dump_dir=None):
         vq, model, opt, tcfg = build_models(cfg_name, vq_dtype, device, seed=1234, transformer_dtype=transformer_dtype)
         reducer = (muse.GradReducer(model, grad_dtype=torch.bfloat16 if args.grad_dtype == "bf16" else torch.float32)
                    if distributed and use_reducer else None)
@@ -598,6 +695,8 @@ def main():
         if distributed:
             dist.barrier()
         el = time.perf_counter() - t0
+        if dump_dir is not None and rank == 0:     # before anything below steps the model again
+            dump_outputs(dump_dir, loss, mask_prob, model, opt)
         if distributed:
             t = torch.tensor([el], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -607,37 +706,38 @@ def main():
                 comm_info.update(buckets_per_step=reducer.stats["buckets"] / steps, bytes_per_step=reducer.stats["bytes"] / steps,
                                  bucket_bytes=int(reducer.bucket_elems * (2 if args.grad_dtype == "bf16" else 4)),
                                  note="per_bucket comes from ONE extra traced step after the timed region (it also steps the optimizer)")
-                try:    # one more step with per-bucket events: which share of each bucket's all-reduce backward hid
-                    reducer.trace = []
-                    one()
-                    torch.cuda.synchronize()
-                    comm_info["per_bucket"] = reducer.bucket_overlap()
-                except Exception as e:   # noqa: BLE001
-                    comm_info["per_bucket_error"] = f"{type(e).__name__}: {str(e)[:160]}"
-                finally:
-                    reducer.trace = None
-                try:    # the gradient all-reduce ALONE (no compute beside it), in the reducer's own buckets: what the links deliver
-                    g = model.flat_grads()
-                    be = reducer.bucket_elems
-                    cuts = list(range(g.numel(), 0, -be))
-                    def allreduce_all():
-                        for hi in cuts:
-                            reducer._reduce(g[max(0, hi - be):hi], True)
-                    allreduce_all()
-                    torch.cuda.synchronize()
-                    dist.barrier()
-                    ta = time.perf_counter()
-                    for _ in range(3):
+                if args.full:   # two diagnostics that take GPU time of their own
+                    try:    # one more step with per-bucket events: which share of each bucket's all-reduce backward hid
+                        reducer.trace = []
+                        one()
+                        torch.cuda.synchronize()
+                        comm_info["per_bucket"] = reducer.bucket_overlap()
+                    except Exception as e:   # noqa: BLE001
+                        comm_info["per_bucket_error"] = f"{type(e).__name__}: {str(e)[:160]}"
+                    finally:
+                        reducer.trace = None
+                    try:    # the gradient all-reduce ALONE (no compute beside it), in the reducer's own buckets: what the links deliver
+                        g = model.flat_grads()
+                        be = reducer.bucket_elems
+                        cuts = list(range(g.numel(), 0, -be))
+                        def allreduce_all():
+                            for hi in cuts:
+                                reducer._reduce(g[max(0, hi - be):hi], True)
                         allreduce_all()
-                    torch.cuda.synchronize()
-                    tb = torch.tensor([(time.perf_counter() - ta) / 3], device=device, dtype=torch.float64)
-                    dist.all_reduce(tb, op=dist.ReduceOp.MAX)
-                    nbytes = g.numel() * (2 if args.grad_dtype == "bf16" else 4)
-                    comm_info.update(allreduce_alone_ms=round(float(tb) * 1e3, 3),
-                                     allreduce_alone_algbw_GBps=round(nbytes / float(tb) / 1e9, 1),
-                                     allreduce_alone_busbw_GBps=round(nbytes / float(tb) / 1e9 * 2 * (world - 1) / max(world, 1), 1))
-                except Exception as e:   # noqa: BLE001   (diagnostics must never take the bench line down)
-                    comm_info["allreduce_alone_error"] = f"{type(e).__name__}: {str(e)[:160]}"
+                        torch.cuda.synchronize()
+                        dist.barrier()
+                        ta = time.perf_counter()
+                        for _ in range(3):
+                            allreduce_all()
+                        torch.cuda.synchronize()
+                        tb = torch.tensor([(time.perf_counter() - ta) / 3], device=device, dtype=torch.float64)
+                        dist.all_reduce(tb, op=dist.ReduceOp.MAX)
+                        nbytes = g.numel() * (2 if args.grad_dtype == "bf16" else 4)
+                        comm_info.update(allreduce_alone_ms=round(float(tb) * 1e3, 3),
+                                         allreduce_alone_algbw_GBps=round(nbytes / float(tb) / 1e9, 1),
+                                         allreduce_alone_busbw_GBps=round(nbytes / float(tb) / 1e9 * 2 * (world - 1) / max(world, 1), 1))
+                    except Exception as e:   # noqa: BLE001   (diagnostics must never take the bench line down)
+                        comm_info["allreduce_alone_error"] = f"{type(e).__name__}: {str(e)[:160]}"
         prof = tr_ms = None
         if profile:
             # per-kernel timing needs the kernels one at a time: no token prefetch, weight gradients on the main stream
@@ -724,7 +824,7 @@ def main():
         return
 
     plain_ms = None
-    if distributed and os.environ.get("MUSE_BENCH_COMM_PLAIN", "1") != "0":
+    if distributed and args.full and os.environ.get("MUSE_BENCH_COMM_PLAIN", "1") != "0":
         # the same step WITHOUT the reducer on the same GPUs first (every rank its own replica, max over ranks): the data-parallel
         # step minus this is the communication the step could not hide.  In a process of its own per rank: a second leg inside this
         # process measures 10-15 % slower than a fresh one (same effect as leg_isolated's note), and the timed run must be the fresh one.
@@ -747,79 +847,15 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)      # keep the ranks' collectives paired
             except Exception:   # noqa: BLE001
                 pass
-    el, lossv, prof, tr_ms = run(args.config, args.vq_dtype, args.steps, args.warmup, profile=True)
+    el, lossv, prof, tr_ms = run(args.config, args.vq_dtype, args.steps, args.warmup, profile=args.full, dump_dir=args.dump_outputs)
     ms = el / args.steps * 1e3
     value = args.batch * world * args.steps / el
 
-    # per-kernel roofline from live HIP-event timings of one instrumented step
-    agg = {}
-    for name, work, t, kind in prof:
-        a = agg.setdefault((name, kind), [0.0, 0.0, 0])
-        a[0] += work; a[1] += t; a[2] += 1
-    mfma = {k[0]: v for k, v in agg.items() if k[1] == "flop"}
-    hbm = {k[0]: v for k, v in agg.items() if k[1] == "byte"}
-    kinds = {k: {"launches": v[2], "ms_total": round(v[1], 3), "avg_us": round(v[1] / v[2] * 1e3, 1),
-                 "tflops": round(v[0] / (v[1] * 1e-3) / 1e12, 1)} for k, v in sorted(mfma.items(), key=lambda kv: -kv[1][1])}
-    hbm_kinds = {k: {"launches": v[2], "ms_total": round(v[1], 3), "GBps": round(v[0] / (v[1] * 1e-3) / 1e9, 1),
-                     "frac_of_8TBps": round(v[0] / (v[1] * 1e-3) / 1e9 / HBM_PEAK, 3)} for k, v in sorted(hbm.items(), key=lambda kv: -kv[1][1])}
-    dname, (dfl, dms, dn) = max(mfma.items(), key=lambda kv: kv[1][1])
-    x3 = dname.startswith("conv_bf16x3")
-    peak = round(PEAK["bf16"] / 3.0, 1) if x3 else PEAK["bf16" if "bf16" in dname else "f32"]
-    ach = dfl / (dms * 1e-3) / 1e12
-    traffic, tnote = traffic_of(dname)
-    roofline = {"bound": "mfma", "kernel": dname, "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(ach / peak, 4), "traffic": traffic, "launches_per_step": dn, "avg_launch_us": round(dms / dn * 1e3, 1),
-                "peak_basis": ("issued bf16 MFMA / 3: 2500 dense bf16 TFLOP/s divided by the three bf16 MFMAs the bf16x3 algorithm issues "
-                               "per f32 product; `achieved` counts ALGORITHMIC flops (2*B*H*W*Cout*9*Cin), executed_mfma_tflops the issued "
-                               "ones; against the plain 2500 peak frac would be frac/3") if x3 else "dense MFMA peak of the operand dtype",
-                "executed_mfma_tflops": round(ach * (3 if x3 else 1), 1),
-                "two_kernel_route": ({"conv_achieved": round(prof_bytes["__unfused__"]["conv_tflops"], 1),
-                                      "conv_frac": round(prof_bytes["__unfused__"]["conv_tflops"] / peak, 4),
-                                      "conv_ms_per_step": round(prof_bytes["__unfused__"]["conv_ms"], 3),
-                                      "groupnorm_apply_ms_per_step": round(prof_bytes["__unfused__"]["groupnorm_ms"], 3),
-                                      "what": "the same tokenizer pass with MUSE_GN_FUSE=0: bare patch-slab convolution + separate GroupNorm apply"}
-                                     if (dname == "conv_bf16x3_dma" and "__unfused__" in prof_bytes) else None),
-                "note": ("since round 3 this kernel also normalises its input (GroupNorm + SiLU + bf16x3 split inside the convolution, "
-                         "muse_conv2d_nhwc_gn_split2): `achieved` still counts the convolution's flops only, over a launch that now contains "
-                         "the former 5.3 ms / step GroupNorm apply pass - the fraction fell 0.56 -> ~0.50 while the step got 2.6 ms shorter "
-                         "(DESIGN.md section 5)") if dname == "conv_bf16x3_dma" else None,
-                "algorithmic_bytes_per_launch": round(prof_bytes[dname] / dn) if dname in prof_bytes else None,
-                "traffic_source": tnote,
-                "per_kernel": kinds, "hbm_bound_kernels": hbm_kinds}
     gf_img = GF_ENCODE + 3 * GF_FWD[args.config]
-    tr_tf = 3 * GF_FWD[args.config] * args.batch / tr_ms   # GFLOP / ms = TFLOP/s
-    vq_hbm = [v for k, v in hbm.items() if k in ("groupnorm_silu", "avgpool2x2")]
-    vq_bytes, vq_ms = sum(v[0] for v in vq_hbm), sum(v[1] for v in vq_hbm)
     extra = {"loss": round(lossv, 4), "algorithmic_gflop_per_image": round(gf_img, 2),
-             "step_tflops_per_gpu": round(gf_img * args.batch / ms, 1),
-             "transformer_fwd_bwd_ms": round(tr_ms, 2), "transformer_tflops": round(tr_tf, 1),
-             "transformer_mfma_frac": round(tr_tf / PEAK["bf16"], 4),
-             "vqgan_hbm_GBps": round(vq_bytes / (vq_ms * 1e-3) / 1e9, 1) if vq_ms else None,
-             "vqgan_hbm_frac": round(vq_bytes / (vq_ms * 1e-3) / 1e9 / HBM_PEAK, 4) if vq_ms else None,
-             "vqgan_hbm_note": "GroupNorm+SiLU and 2x2 pooling kernels of the encoder: algorithmic bytes (each operand once) / their time / 8 TB/s",
-             "mfma_ms_in_instrumented_step": round(sum(v[1] for v in mfma.values()), 2),
-             "hbm_kernel_ms_in_instrumented_step": round(sum(v[1] for v in hbm.values()), 2),
-             "measured_parity_bf16_vs_f32_mode": {k: (round(v, 8) if isinstance(v, float) else v) for k, v in parity.items()}}
-    if args.config == "B" and args.batch == 64:
-        # per family the time its BINDING resource implies (derivation and sources: profiles/r06_ceiling.md) next to this
-        # run's serial time; a ratio above 1.15 has its measured decomposition there
-        def _ms(*names):
-            return round(sum(kinds[n]["ms_total"] for n in names if n in kinds) + sum(hbm_kinds[n]["ms_total"] for n in names if n in hbm_kinds), 3)
-        ceil_rows = {
-            "conv_bf16x3_dma": ("MFMA issue at the clock the kernel holds (1.72 GHz, power-limited): 3 x 8.155 TFLOP / (2.5 PF x 1.72 / 2.4)", 13.7,
-                                _ms("conv_bf16x3_dma")),
-            "gemm_fwd_dx": ("K loop bound by the operand stream from L2 into LDS (2500 cycles per K-tile against 2048 of MFMA: 26-28 B/clk/CU delivered, 32 needed) + "
-                            "whole 256^2 tiles on 256 CUs + 82 us tile change per layer "
-                            "(46 us register epilogue + 36 us stores, ablation)", 13.1, _ms("gemm_bf16_NN", "gemm_bf16_NT")),
-            "gemm_dw": ("the same K loop at K = 16448, five slices alone on the chip", 5.9, _ms("gemm_bf16_TT")),
-            "attention": ("HBM floor of q, k, v, o (+ dO, dq, dk, dv) at 6.3 TB/s", 1.15, _ms("attn_fwd_bf16", "attn_bwd_bf16")),
-            "row_kernels": ("HBM streaming at the 6.0 TB/s a three-operand stream reaches on this chip", 8.9,
-                            round(sum(v["ms_total"] for v in hbm_kinds.values()), 3)),
-        }
-        extra["ceiling"] = {"doc": "profiles/r06_ceiling.md",
-                            "families": {k: {"binding": b, "implied_ms": i, "measured_ms": m, "ratio": round(m / i, 2) if m else None}
-                                         for k, (b, i, m) in ceil_rows.items()}}
-    if world == 1 and not args.no_extra:
+             "step_tflops_per_gpu": round(gf_img * args.batch / ms, 1)}
+    roofline = instrumented_step_figures(args, prof, prof_bytes, tr_ms, parity, extra) if args.full else None
+    if world == 1 and args.full and not args.no_extra:
         n2 = max(3, args.steps // 2)
 
         def leg(cfgn, vqd, mode):
@@ -868,7 +904,7 @@ def main():
                      f"weights: loss {parity['loss_rel_diff']:.1e} rel, logits {parity['logits_max_abs_diff_over_max_logit']:.1e} of max|logit| "
                      "(the reference's own autocast-bf16 gap at this geometry is 1.2e-2, tests/golden/transformer_b_full_bf16.npz; the f32 "
                      "mode meets north_star's 1e-3 against the reference: logits 2e-6)") if "loss_rel_diff" in parity else
-                    "; parity of this mode was not measured in this run (" + parity.get("error", "profile leg skipped") + ")"),
+                    "; parity of this mode was not measured in this run (" + parity.get("error", "a --full run measures it") + ")"),
         "data": "synthetic",
         "config": {"workload": f"MaskGit train step: MaskGitVQGAN f16-256 encode ({args.vq_dtype}) + cosine mask + "
                                f"MaskGitTransformer config {args.config} "
@@ -883,7 +919,7 @@ def main():
     }
     if distributed:
         out["comm"] = comm_block(comm_info, world, ms, plain_ms, args.grad_dtype, rccl_log)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.config, device, bench_batch=args.batch)
     if rank == 0:
         print(json.dumps(out))

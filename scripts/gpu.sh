@@ -25,10 +25,10 @@ attn_stag)  # start stagger of the second workgroup per CU: sweep
 attn_ts)
   MUSE_HIP_LIB=$PWD/open-muse_amd/csrc/variants/libmuse_hip_ts.so timeout 300 python scripts/exp/attn2_ts.py 2>&1 | grep -v amdgpu.ids | tee $O/${tag}_attn_ts.txt
   ;;
-ab)     # same-box A/B of the headline step: scripts/gpu.sh ab <tag> "ENV=a ENV2=b" "ENV=c" ...   (one bench.py --no-extra run per quoted setting)
+ab)     # same-box A/B of the headline step: scripts/gpu.sh ab <tag> "ENV=a ENV2=b" "ENV=c" ...   (one bench.py --full --no-extra run per quoted setting)
   for setting in "${@:3}"; do
     for rep in 1 2; do
-      env $setting timeout 900 python bench.py --no-extra --no-cpu-baseline --steps 20 --warmup 5 2> $O/${tag}_ab.err | python -c "
+      env $setting timeout 900 python bench.py --full --no-extra --no-cpu-baseline --steps 20 --warmup 5 2> $O/${tag}_ab.err | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
@@ -40,7 +40,7 @@ for l in sys.stdin:
   ;;
 trace)  # concurrency picture of the default multi-stream step: kernel trace of a short bench run -> scripts/overlap_report.py
   rm -rf $O/${tag}_trace; cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$O/${tag}_trace -o t -- python $OLDPWD/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-extra > $OLDPWD/$O/${tag}_trace_bench.txt 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$O/${tag}_trace -o t -- python $OLDPWD/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-extra > $OLDPWD/$O/${tag}_trace_bench.txt 2>&1
   cd $OLDPWD
   f=$(find $O/${tag}_trace -name "t_kernel_trace.csv" | head -1)
   python scripts/overlap_report.py $f --last-ms 250 > $O/${tag}_overlap.txt 2>&1; tail -60 $O/${tag}_overlap.txt
@@ -74,7 +74,7 @@ final)  # validation of the committed tree: device, full GPU suite (printed erro
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.txt 2>&1; echo "smoke exit $?" >> $O/${T}_smoke.txt; tail -2 $O/${T}_smoke.txt
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc_$c
-    MUSE_CONV_PERSIST=0 timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o p -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-prefetch > $O/pmc_$c.log 2>&1
+    MUSE_CONV_PERSIST=0 timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o p -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-prefetch > $O/pmc_$c.log 2>&1
     echo "$c exit $?"
   done
   f=$(find $O/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1); w=$(find $O/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
@@ -84,13 +84,13 @@ final)  # validation of the committed tree: device, full GPU suite (printed erro
   REPS=3 WHICH=nn,nt,grp,conv timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_mfma -o p -- python scripts/gemm_probe.py > $O/pmc_mfma.log 2>&1
   python scripts/pmc_fold.py $O/pmc_mfma | tee $O/${T}_pmc_mfma_clock.txt | tail -14
   find $O/pmc_mfma -name "*.csv" -size +2M -delete
-  timeout 1800 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err; echo "bench exit $?"; tail -c 400 $O/${T}_bench.err
+  timeout 1800 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err; echo "bench exit $?"; tail -c 400 $O/${T}_bench.err
   python scripts/bench_summary.py $O/${T}_bench.json
   rm -rf $O/prof_serial
-  MUSE_WGRAD_STREAM=0 MUSE_CONV_PERSIST=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial -o s -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --no-prefetch > $O/${T}_prof.txt 2>&1
+  MUSE_WGRAD_STREAM=0 MUSE_CONV_PERSIST=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_serial -o s -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra --no-prefetch > $O/${T}_prof.txt 2>&1
   f=$(find $O/prof_serial -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${T}_kernel_stats.csv && head -14 "$f" | cut -c1-170
   find $O/prof_serial -name "*kernel_trace*" -size +8M -delete
-  MUSE_BENCH_RCCL_DEBUG=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --no-extra --no-cpu-baseline 2>$O/${T}_dp1.err > $O/${T}_dp1.out
+  MUSE_BENCH_RCCL_DEBUG=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --full --no-extra --no-cpu-baseline 2>$O/${T}_dp1.err > $O/${T}_dp1.out
   python -c "
 import json
 ls=[l for l in open('$O/${T}_dp1.out') if l.strip()]

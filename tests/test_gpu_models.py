@@ -1156,7 +1156,7 @@ def test_bench_under_torchrun_single_rank():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", str(29800 + os.getpid() % 100), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=600)
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 100 and line["config"]["parallelism"] == "dp1" and line["roofline"]["frac"] > 0
@@ -1177,7 +1177,7 @@ def test_bench_two_rank_protocol_on_one_gpu():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(29900 + os.getpid() % 90), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                          "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=900)
+                          "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines[:3]
@@ -1192,6 +1192,34 @@ def test_bench_two_rank_protocol_on_one_gpu():
     assert len(pb) == round(comm["buckets_per_step"]) and sum(b["bytes"] for b in pb) == comm["bytes_per_step"]
     assert all(0.0 <= b["hidden_fraction"] <= 1.0 and b["ms"] > 0 for b in pb)
     assert 1.0 < line["extra"]["loss"] < 10.0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """bench.py without --full: the headline fields and none of the --full blocks; --dump-outputs writes the last timed step's arrays
+    (float32, finite, at most 64 MB in all), and the loss among them is the line's loss"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    d = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines[:3]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "images/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+    assert line["roofline"] is None and "cpu_baseline" not in line and "transformer_fwd_bwd_ms" not in line["extra"]
+    assert sorted(os.listdir(d)) == ["adamw_exp_avg_sample.npy", "loss.npy", "mask_prob.npy", "transformer_params_sample.npy"]
+    arrays = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["mask_prob"].shape == (64,) and arrays["transformer_params_sample"].shape == arrays["adamw_exp_avg_sample"].shape == (1 << 20,)
+    assert abs(float(arrays["loss"][0]) - line["extra"]["loss"]) <= 1e-4 and np.abs(arrays["adamw_exp_avg_sample"]).max() > 0
 
 
 def test_get_soft_code_matches_oracle():
