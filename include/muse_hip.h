@@ -304,8 +304,9 @@ int muse_split_f32_to_bf16_cat3(const float* in, void* out, int64_t rows, int32_
                                 int32_t lo_pos, void* stream);
 int muse_cast_f32_to_bf16(const float* in, void* out, int64_t n, void* stream);
 /* out = half(in * scale): the operand image of a MUSE_F16 product (round to nearest even, subnormals kept; a finite value beyond half's
- * range becomes inf - the product turns NaN rather than silently wrong).  stats: NULL or int32[2], incremented by [0] the finite
- * elements that overflowed, [1] the non-zero elements rounded to zero. */
+ * range becomes inf - the product turns NaN rather than silently wrong).  stats: NULL or int32[2], incremented by [0] the number of
+ * ELEMENTS whose half is inf or NaN (an inf / NaN input and an f32-overflowing in * scale included), [1] the number of finite non-zero
+ * inputs whose half is +-0. */
 int muse_cast_f32_to_f16(const float* in, void* out, int64_t n, float scale, int32_t* stats, void* stream);
 /* What the producer entry points below that write operand images next to (or instead of) their f32 result - muse_glu_fwd_x3 / _bwd_x3,
  * muse_norm_adaln_fwd_x3 / _bwd_x3, muse_attention_x3_fwd / _bwd / _merge - write as that image.  half = 0 (default): the (hi, lo) bf16
@@ -316,8 +317,8 @@ int muse_cast_f32_to_f16(const float* in, void* out, int64_t n, float scale, int
  * incremented per 4-element group that holds an inf / NaN half (muse_cast_f32_to_f16's overflow counter: a dynamic gradient scale backs
  * off on it).  Process state (host code sets it around a pass: muse/ops.py f32_gemms_as_f16), not thread safe. */
 int muse_operand_images(int32_t half, float grad_scale, int32_t* stats);
-/* Overflow guard of the "f16" mode for the multi-tensor optimizer kernels (muse_adamw_multi, muse_adamw_multi_groups): while flag is
- * non-NULL those kernels read *flag (device int32: the overflow counter muse_operand_images / muse_cast_f32_to_f16 increment) and leave
+/* Overflow guard of the "f16" mode for the optimizer kernels (muse_adamw_flat, muse_adamw_flat_groups, muse_adamw_multi,
+ * muse_adamw_multi_groups): while flag is non-NULL those kernels read *flag (device int32: the overflow counter muse_operand_images / muse_cast_f32_to_f16 increment) and leave
  * parameters and moments untouched when it is non-zero - GradScaler's found_inf without a host round trip.  Process state; NULL = off. */
 int muse_adamw_skip_flag(const int32_t* flag);
 int muse_cast_bf16_to_f32(const void* in, float* out, int64_t n, void* stream);

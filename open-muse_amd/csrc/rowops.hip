@@ -1398,13 +1398,20 @@ extern "C" int muse_cross_entropy_bwd(const void* logits, int32_t dtype, const i
   return (int)hipGetLastError();
 }
 
+// Overflow guard of the "f16" compute mode (muse_adamw_skip_flag): when set, every AdamW kernel (flat, flat groups, multi-tensor) reads *skip first and leave every
+// tensor untouched if it is non-zero - the gradients of a backward pass whose operand images overflowed half's range are NaN, and the
+// update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host round trip).  Process state like
+// muse_operand_images; NULL (default) = no guard.
+static const int* g_adamw_skip = nullptr;
+extern "C" int muse_adamw_skip_flag(const int32_t* flag) { g_adamw_skip = (const int*)flag; return 0; }
 // =================================================================================================================
 // AdamW over a flat f32 buffer; optional bf16 shadow refresh.  7 x 4 B per parameter of HBM traffic (+2 B shadow).
 // =================================================================================================================
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
                                                     float b2, float eps, float decay, float omb1, float omb2,
-                                                    float step_size, float bc2_sqrt, float gscale) {
+                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
+  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard: muse_adamw_skip_flag)
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float pp[4], gg[4], mm[4], vv[4];
@@ -1444,7 +1451,7 @@ extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, voi
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
   const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                     (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale);
+                     (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, g_adamw_skip);
   return (int)hipGetLastError();
 }
 
@@ -1452,12 +1459,6 @@ extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, voi
 // a flat buffer: MaskGiTUViT has ~500, and 500 launches of 9 us each were 4 % of its step).  The table is 6 x int64 per tensor:
 // {p, g, m, v, p_bf16 or 0, n}; `chunk_first[t]` = index of tensor t's first 4096-element chunk (exclusive prefix sum, nt + 1
 // entries); block b owns chunk b: binary search -> (tensor, offset).  Same arithmetic, same order, as adamw_kernel.
-// Overflow guard of the "f16" compute mode (muse_adamw_skip_flag): when set, the multi-tensor kernels read *skip first and leave every
-// tensor untouched if it is non-zero - the gradients of a backward pass whose operand images overflowed half's range are NaN, and the
-// update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host round trip).  Process state like
-// muse_operand_images; NULL (default) = no guard.
-static const int* g_adamw_skip = nullptr;
-extern "C" int muse_adamw_skip_flag(const int32_t* flag) { g_adamw_skip = (const int*)flag; return 0; }
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
                                                           float b2, float eps, float decay, float omb1, float omb2,
                                                           float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
@@ -1591,7 +1592,8 @@ __device__ __forceinline__ void adam_update1(float& pp, float gr, float& mm, flo
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
                                                            const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
-                                                           AdamGroups G, float gscale) {
+                                                           AdamGroups G, float gscale, const int* __restrict__ skip) {
+  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard: muse_adamw_skip_flag)
   const long c0 = (long)blockIdx.x * 4096, c1 = c0 + 4096 < n ? c0 + 4096 : n;
   auto seg_of = [&](long pos) {   // smallest s with seg_end[s] > pos (positions beyond the last end: the last segment)
     int lo = 0, hi = nseg - 1;
@@ -1640,7 +1642,7 @@ extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float*
   const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
   if (rc) return rc;
   hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale);
+                     (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, g_adamw_skip);
   return (int)hipGetLastError();
 }
 // Multi-tensor form with groups: `table` is 7 x int64 per tensor {p, g, m, v, p_bf16 or 0, n, group | lo_plane_distance << 8}
@@ -1790,16 +1792,18 @@ extern "C" int muse_cast_f32_to_bf16(const float* in, void* out, int64_t n, void
 }
 // f32 -> IEEE half operand image of the "f16" compute mode (muse_gemm dtype MUSE_F16): out = half(in * scale), round to nearest even,
 // subnormals kept; a finite in * scale beyond half's range becomes inf (the product, and the step's loss, turn NaN: loud - the same
-// bits the producer kernels write, common.h store_image4).  stats (optional, int32[2], accumulated with atomics by the waves that see
-// one): [0] finite elements that overflowed, [1] non-zero elements that became zero - the caller's gradient scale was too large / too small.
+// bits the producer kernels write, common.h store_image4).  stats (optional, int32[2], ELEMENT counts added with one atomic per wave
+// that has any): [0] elements whose half is inf or NaN - the exponent test of store_image4, so an input that already is inf / NaN and
+// a finite in * scale that overflows f32 count as well; [1] finite non-zero inputs whose half is +-0.  [0] > 0: the gradient scale
+// was too large (or the gradients are not finite); [1]: too small.  (store_image4 counts 4-element groups into the same [0].)
 __global__ void cast_f2h_kernel(const float* __restrict__ in, _Float16* __restrict__ out, long n, float scale, int* __restrict__ stats) {
   const long n4 = n >> 2;
-  bool sat = false, und = false;
+  int sat = 0, und = 0;
   auto cv = [&](float x) -> _Float16 {
-    const float v = x * scale;
-    const _Float16 h = (_Float16)v;
-    sat = sat || (fabsf(v) <= 3.0e38f && fabsf((float)h) > 65504.f);
-    und = und || (x != 0.f && (float)h == 0.f);
+    const _Float16 h = (_Float16)(x * scale);
+    const unsigned short b = __builtin_bit_cast(unsigned short, h);
+    sat += (b & 0x7c00u) == 0x7c00u;
+    und += x != 0.f && (b & 0x7fffu) == 0u;       // (x NaN / inf: its half is NaN / inf, never zero)
     return h;
   };
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -1810,10 +1814,14 @@ __global__ void cast_f2h_kernel(const float* __restrict__ in, _Float16* __restri
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const long i = (n4 << 2) + threadIdx.x; out[i] = cv(in[i]); }
   if (stats) {
-    const unsigned long long bs = __ballot(sat), bu = __ballot(und);
-    if ((threadIdx.x & 63) == 0) {
-      if (bs) atomicAdd(stats, __popcll(bs));
-      if (bu) atomicAdd(stats + 1, __popcll(bu));
+    // rare: the wave sums its lanes' counts only when one of them is non-zero
+    if (__ballot(sat != 0)) {
+      for (int o = 32; o > 0; o >>= 1) sat += __shfl_xor(sat, o);
+      if ((threadIdx.x & 63) == 0) atomicAdd(stats, sat);
+    }
+    if (__ballot(und != 0)) {
+      for (int o = 32; o > 0; o >>= 1) und += __shfl_xor(und, o);
+      if ((threadIdx.x & 63) == 0) atomicAdd(stats + 1, und);
     }
   }
 }

@@ -251,7 +251,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
     def _apply(self, fn, recurse=True):
         out = super()._apply(fn, recurse)
         if self._general:
-            self._wcache, self._wcache_owner = {}, {}
+            self._drop_weight_copies()
             return out
         if self._flat is not None:
             p0 = self._param_order()[0]
@@ -263,7 +263,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         out = super().load_state_dict(state_dict, strict=strict, assign=False)
         if self._general:
-            self._wcache, self._wcache_owner = {}, {}
+            self._drop_weight_copies()
             return out
         if not self._flat_ok():
             self._build_flat()
@@ -287,6 +287,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
             self._cd_request = torch.float32                  # (tape_ops.set_compute_dtype)
             self.__dict__["_f32_split3"] = dtype == "bf16x3"
             self.__dict__["_f32_f16"] = dtype == "f16"
+            self._drop_weight_copies()
             return self
         if dtype == "f16":      # the flat engine's f32 mode with every weight GEMM as one IEEE-half product (_flat_gemm_mode)
             self.compute_dtype = torch.float32
@@ -299,6 +300,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
             self._cd_request = dtype          # (the tape helpers read self.compute_dtype: resolved at every forward)
             self.__dict__["_f32_split3"] = False
             self.__dict__["_f32_f16"] = False
+            self._drop_weight_copies()
             return self
         self.compute_dtype = dtype
         self.__dict__["_f32_f16"] = False
@@ -317,6 +319,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
         images = self.__dict__.get("_f16_images")
         if images is None:
             images = self.__dict__["_f16_images"] = ops.F16Images(recent=0)
+            images.owner = weakref.ref(self)
         images.clear()
         images.backward, images.keep = bool(backward), False
         if backward:
@@ -354,7 +357,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
     def mark_weights_changed(self):
         """call after writing the f32 master weights behind autograd's back (`p.data.copy_`, a raw kernel on flat_params())"""
         self._shadow_fresh = False
-        self._wcache, self._wcache_owner = {}, {}
+        self._drop_weight_copies()
 
     def _note_shadow_refreshed(self, fresh: bool):
         """FusedAdamW has just rewritten the master weights and (if `fresh`) the bf16 copy in the same kernel"""
@@ -365,7 +368,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
     def train(self, mode: bool = True):
         if mode != self.training:
             self._shadow_fresh = False   # EMA copy_to()/restore() around evaluation write p.data (reference modeling_ema.py)
-            self._wcache, self._wcache_owner = {}, {}
+            self._drop_weight_copies()
         return nn.Module.train(self, mode)
 
     def _wgrad_side_stream(self, dev):
@@ -432,7 +435,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
             cd = self._resolve_cd()
             if cd != self.compute_dtype:
                 self.compute_dtype = cd
-                self._wcache, self._wcache_owner = {}, {}
+                self._drop_weight_copies()
             if encoder_hidden_states is not None and not self.config.add_cross_attention:
                 # (layers without a cross-attention block: the reference fails on the missing module, :886-889; same error as the flat engine)
                 raise ValueError("this model was built without cross attention (add_cross_attention=False)")

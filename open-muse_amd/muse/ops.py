@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import weakref
 
 import torch
 
@@ -188,12 +189,15 @@ def gemm(A, B, C_, M, N, K, *, la=0, lb=0, lda, ldb, ldc, a_off=0, b_off=0, c_of
 # of two (exact) and the product's alpha carries 1 / (s_a s_b).  Forward operands (normalised activations, weights) use s = 1; every
 # GRADIENT operand of a backward pass uses the pass's `grad_scale` (per-token loss gradients are ~1 / tokens: far below half's normal
 # range unscaled).  A finite element beyond +-65504 / s becomes inf - the product and the step's gradients turn NaN rather than silently
-# wrong - and is counted, by the cast kernel and by every producer kernel; non-zero elements a cast rounds to zero are counted too
-# (F16Images.stats()).  The fp16-training recipe applies on top: TapeOps.f16_update_grad_scale() halves the scale and has the caller
-# skip the step.  Products the 256^2 half kernels refuse stay in exact f32.
+# wrong - and is counted (F16Images.stats()[0]): the cast kernel counts every ELEMENT whose half is inf or NaN (an input that already was
+# one included), the producer kernels (common.h store_image4) every 4-element GROUP that holds one; the cast kernel also counts the
+# finite non-zero elements it rounds to +-0 ([1]).  The fp16-training recipe applies on top: TapeOps.f16_update_grad_scale() halves the
+# scale and has the caller skip the step, or muse.FusedAdamW skips it on the device.  Products the 256^2 half kernels refuse stay in exact f32.
 _F32_AS_F16 = [False]
 _F16_IMAGES = [None]
-_F16_GUARD = [None]     # the F16Images of the last f16 BACKWARD pass: muse.FusedAdamW guards its update with that pass's overflow counter
+# the F16Images of f16 BACKWARD passes whose overflow counter no optimizer step has consumed yet: muse.FusedAdamW guards its update
+# with the counter of a pass of the model whose parameters it steps (F16Images.owner) - never with another model's
+_F16_GUARDS = weakref.WeakSet()
 # operand dtypes of a product the mode converts: f32 tensors, or an f32 tensor against an operand that already IS a half image (a
 # weight's copy kept across steps: tape_ops._wb)
 _F16_MODE_PAIRS = {(torch.float32, torch.float32), (torch.float32, torch.float16), (torch.float16, torch.float32)}
@@ -212,6 +216,7 @@ class F16Images:
         self.hits = self.misses = self.produced = 0
         self._stats = None
         self._snaps, self._free, self.totals = [], [], [0, 0]      # counter copies in flight (pinned buffer, event), free ones, running totals
+        self.owner = None      # weakref to the model whose passes these are (the optimizer steps that honour its overflow guard)
 
     def clear(self):
         self.persist.clear()
@@ -229,8 +234,9 @@ class F16Images:
         return self._stats
 
     def stats(self, reset=True):
-        """(operand elements / 4-element groups that overflowed half's range, non-zero elements rounded to zero by a cast) since the
-        last reset - one device read (plus what optimizer steps have already taken off the device counters: after_optimizer_step)"""
+        """(operand images with an inf / NaN half - elements of a cast, 4-element groups of a producer kernel -, finite non-zero
+        elements a cast rounded to +-0) since the last reset - one device read (plus what optimizer steps have already taken off the
+        device counters: after_optimizer_step)"""
         self.consume_snapshots(block=True)
         v = [0, 0] if self._stats is None else self._stats.tolist()
         out = (int(v[0]) + self.totals[0], int(v[1]) + self.totals[1])
@@ -338,7 +344,7 @@ class f32_gemms_as_f16:
         if self.on or self.prev[0]:
             self._tell_kernels(self.prev[0], self.prev[1])
         if self.on and self.images is not None and self.images.backward:
-            _F16_GUARD[0] = self.images          # (the optimizer step that follows skips its update if this pass overflowed)
+            _F16_GUARDS.add(self.images)         # (the owner's optimizer step that follows skips its update if this pass overflowed)
         return False
 
 

@@ -9,6 +9,7 @@ the reference's autocast regime), `config.layer_norm_eps`, `wgrad_stream`, `_sid
 from __future__ import annotations
 
 import os
+import weakref
 
 import torch
 
@@ -84,7 +85,7 @@ class TapeOps:
         self.__dict__["_f32_split3"] = dtype == "bf16x3"
         self.__dict__["_f32_f16"] = dtype == "f16"
         self.compute_dtype = torch.float32 if dtype in ("bf16x3", "f16") else dtype
-        self._wcache, self._wcache_owner = {}, {}
+        self._drop_weight_copies()
         self.__dict__["_wgen"] = self.__dict__.get("_wgen", 0) + 1      # (a kept decoding graph reads the old weight copies: generate2 re-captures)
         return self
 
@@ -96,6 +97,7 @@ class TapeOps:
             images = self.__dict__.get("_f16_images")
             if images is None:
                 images = self.__dict__["_f16_images"] = ops.F16Images()
+                images.owner = weakref.ref(self)
             images.backward = bool(backward)
             images.keep = bool(backward or self.__dict__.get("_act_cache_on", False))
             if backward:
@@ -142,9 +144,11 @@ class TapeOps:
         if images is not None and images._stats is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
             torch.distributed.all_reduce(images._stats, group=group)
         overflowed, _ = self.f16_stats()
+        if images is not None:
+            ops._F16_GUARDS.discard(images)  # (this call has applied the policy to the pass: the optimizer step does not feed it again)
         return self._f16_scale_policy(overflowed, growth_interval)
 
-    # With muse.FusedAdamW nothing has to be called: its multi-tensor kernel skips the update on the device when the backward pass that
+    # With muse.FusedAdamW nothing has to be called: its kernels skip the update on the device when a backward pass of this model that
     # made the gradients overflowed (muse_adamw_skip_flag), and the next backward pass reads that step's counters - copied to pinned
     # memory behind the update - and moves the scale by the same policy.  f16_auto_scale = False leaves the scale to the caller.
     f16_auto_scale = True
@@ -171,15 +175,25 @@ class TapeOps:
             if images is not None:
                 images.clear()
 
-    def mark_weights_changed(self):
-        """call after writing parameters behind autograd's back (`p.data.copy_`, EMA swap): drops the cached bf16 weights"""
+    def _drop_weight_copies(self):
+        """forget every weight compute copy kept across steps - _wb's bf16 / half copies, _wp's bf16x3 operand planes - and the planes
+        FusedAdamW would go on refreshing (`p._muse_planes`): their validity check (autograd versions) cannot see `p.data` writes, nor
+        optimizer steps taken while the copy was not the one the optimizer refreshed (another compute mode)"""
         self._wcache, self._wcache_owner = {}, {}
+        self.__dict__["_pcache"], self.__dict__["_pcache_owner"] = {}, {}
+        for p in self.parameters():
+            if hasattr(p, "_muse_planes"):
+                del p._muse_planes
+
+    def mark_weights_changed(self):
+        """call after writing parameters behind autograd's back (`p.data.copy_`, EMA swap): drops the cached bf16 weights and operand planes"""
+        self._drop_weight_copies()
         self.__dict__["_wgen"] = self.__dict__.get("_wgen", 0) + 1
         self.__dict__["_gen_graph"] = None
 
     def train(self, mode: bool = True):
         if mode != self.training:
-            self._wcache, self._wcache_owner = {}, {}        # EMA copy_to()/restore() around evaluation write p.data
+            self._drop_weight_copies()                       # EMA copy_to()/restore() around evaluation write p.data
             self.__dict__["_wgen"] = self.__dict__.get("_wgen", 0) + 1
         return super().train(mode)
 

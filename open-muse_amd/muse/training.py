@@ -162,6 +162,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._table = self._chunk_first = self._table_key = self._stage = None   # per-tensor mode: device table of muse_adamw_multi
         self._ranges_done = self._ranges_done_live = None                        # (step, [(begin, end), ...]) applied inside backward
         self._upd_stream, self._upd_used = None, False                           # stream of the per-bucket update (begin_step_in_reducer)
+        self._skip_flag = None  # ("f16" mode: the overflow counter the update in flight is guarded by)
         self.grad_scale = 1.0   # multiplied into the gradient inside the kernel (GradReducer sets 1/world for SUM reductions)
 
     def _all_params(self):
@@ -225,18 +226,22 @@ class FusedAdamW(torch.optim.Optimizer):
         shadow = model._flat_c if model._flat_c is not None and model._flat_c.device == flat.device else None
         done = self._ranges_done
         self._ranges_done = None
-        if done is not None and done[0] == self._step:
-            # backward already applied this step's update range by range (begin_step_in_backward); cover what it did not report
-            covered = sorted(done[1])
-            pos = 0
-            for b, e in covered:
-                if b > pos:
-                    self._apply(model, pos, b, shadow)
-                pos = max(pos, e)
-            if pos < flat.numel():
-                self._apply(model, pos, flat.numel(), shadow)
-        else:
-            self._apply(model, 0, flat.numel(), shadow)
+        guards = self._f16_guard_on(flat.device)     # ("f16" mode: as in _step_per_tensor - the update is skipped on the device on overflow)
+        try:
+            if done is not None and done[0] == self._step:
+                # backward already applied this step's update range by range (begin_step_in_backward); cover what it did not report
+                covered = sorted(done[1])
+                pos = 0
+                for b, e in covered:
+                    if b > pos:
+                        self._apply(model, pos, b, shadow)
+                    pos = max(pos, e)
+                if pos < flat.numel():
+                    self._apply(model, pos, flat.numel(), shadow)
+            else:
+                self._apply(model, 0, flat.numel(), shadow)
+        finally:
+            self._f16_guard_off(guards)
         model._note_shadow_refreshed(shadow is not None)
         return loss
 
@@ -263,8 +268,11 @@ class FusedAdamW(torch.optim.Optimizer):
         weight-gradient stream) - the HBM-bound update hides behind the MFMA-bound dX chain of the earlier layers instead of
         following backward.  Element-wise identical to one launch over the whole buffer.  The following step() only advances the
         step count and covers ranges backward did not report.  Valid when nothing sits between backward and step(): no gradient
-        clipping, no gradient accumulation, no all-reduce (muse.TrainStep checks this and arms it)."""
+        clipping, no gradient accumulation, no all-reduce (muse.TrainStep checks this and arms it).  Never for a model in the "f16"
+        compute mode: its update waits for the whole backward pass's overflow guard (step())."""
         self._check_not_partial()
+        if model.__dict__.get("_f32_f16", False):
+            return False
         flat = model.flat_params()
         self._ensure_flat_state(flat)
         if any((o * 4) % 16 for o in model._offsets):
@@ -307,6 +315,8 @@ class FusedAdamW(torch.optim.Optimizer):
         bit for bit, but measured much slower at one rank: 69.6 vs 61.5 ms per step, profiles/r02_ab_dp1_updstream_*.json - the
         low-priority update is starved until the end of the step and then serialises).  Same validity conditions as
         begin_step_in_backward; call end_step_in_reducer after reducer.finish()."""
+        if model.__dict__.get("_f32_f16", False):
+            return False
         flat = model.flat_params()
         self._ensure_flat_state(flat)
         if any((o * 4) % 16 for o in model._offsets):
@@ -433,13 +443,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # model's next backward pass halves the gradient scale (tape_ops._gemm_mode) - GradScaler's policy without a host round trip
         # (the host does not know about the skip when it happens: self._step advances anyway, so the bias corrections of the following
         #  updates are those of one step later - a factor that tends to 1)
-        guard = ops._F16_GUARD[0]
-        if guard is not None and (guard._stats is None or guard._stats.device != dev):
-            guard = None
-        if guard is not None:
-            if dist.is_available() and dist.is_initialized():
-                dist.all_reduce(guard._stats)        # every rank skips together (GradScaler's found_inf all-reduce)
-            ops.check(ops.lib().muse_adamw_skip_flag(guard._stats.data_ptr()), "muse_adamw_skip_flag")
+        guards = self._f16_guard_on(dev)
         try:
             if multi:
                 ops.adamw_multi_groups(self._table, self._chunk_first, len(rows), self._nchunks, self.param_groups, self._step,
@@ -449,11 +453,43 @@ class FusedAdamW(torch.optim.Optimizer):
                 ops.adamw_multi(self._table, self._chunk_first, len(rows), self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
                                 grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale))
         finally:
-            if guard is not None:
-                ops.check(ops.lib().muse_adamw_skip_flag(None), "muse_adamw_skip_flag")
-                guard.after_optimizer_step()
-                ops._F16_GUARD[0] = None
+            self._f16_guard_off(guards)
         return loss
+
+    def _f16_guard_on(self, dev):
+        """"f16" compute mode: arm the device-side skip of the update that follows with the overflow counter of the backward pass(es)
+        that made these gradients - passes of a model whose parameters this optimizer steps (F16Images.owner); a pass of any other model
+        gates nothing here.  -> the guards to hand to _f16_guard_off once the update is enqueued"""
+        if not ops._F16_GUARDS:
+            return []
+        mine, guards = None, []
+        for images in list(ops._F16_GUARDS):
+            model = images.owner() if images.owner is not None else None
+            if model is None or images._stats is None or images._stats.device != dev:
+                continue
+            if mine is None:
+                mine = {id(q) for q in self._all_params()}
+            if any(id(q) in mine for q in model.parameters()):
+                guards.append(images)
+        if not guards:
+            return []
+        for images in guards:
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(images._stats)        # every rank skips together (GradScaler's found_inf all-reduce)
+        # (one counter the kernel reads; two models stepped by one optimizer: their sum, stream-ordered like the update)
+        self._skip_flag = guards[0]._stats if len(guards) == 1 else torch.stack([g._stats for g in guards]).sum(0, dtype=torch.int32)
+        ops.check(ops.lib().muse_adamw_skip_flag(self._skip_flag.data_ptr()), "muse_adamw_skip_flag")
+        return guards
+
+    def _f16_guard_off(self, guards):
+        """the guarded update is enqueued: disarm, and take each pass's counters off the device for its model's scale policy"""
+        if not guards:
+            return
+        ops.check(ops.lib().muse_adamw_skip_flag(None), "muse_adamw_skip_flag")
+        self._skip_flag = None
+        for images in guards:
+            images.after_optimizer_step()
+            ops._F16_GUARDS.discard(images)
 
     # ---- checkpointing in torch.optim.AdamW's layout ----------------------------------------------------------------
     def _flat_offsets(self, model):

@@ -1817,3 +1817,60 @@ def test_small_batch_forward_products_split_k(M, N, K, out_dtype, monkeypatch):
     monkeypatch.setattr(ops, "SKINNY", 2)
     y2 = ops.linear(x, w, out_dtype=out_dtype)
     assert rel_err(y2, x.double() @ w.double().t()) < tol
+
+
+def _f16_cast_reference(x, s):
+    """numpy's round-to-nearest-even of the float64 product, and the two counts muse_cast_f32_to_f16 keeps: [0] outputs that are inf
+    or NaN, [1] finite non-zero inputs whose output is +-0"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        h = (x.astype(np.float64) * s).astype(np.float16)
+    bits = h.view(np.uint16)
+    overflowed = int(((bits & 0x7C00) == 0x7C00).sum())
+    flushed = int((np.isfinite(x) & (x != 0) & ((bits & 0x7FFF) == 0)).sum())
+    return bits, overflowed, flushed
+
+
+_CAST_CASES = {
+    # exact boundaries: 65504 is half's largest finite, 65519.996 rounds down to it, 65520 is the tie that rounds to inf
+    "boundaries": (1.0, [65504.0, 65519.996, 65520.0, -65504.0, -65519.996, -65520.0]),
+    # 2^-24 is half's smallest subnormal, 2^-25 the tie to even that rounds to 0, a hair above it rounds up to 2^-24
+    "subnormal_ties": (1.0, [2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -23), -(2.0 ** -25)]),
+    "f32_subnormals": (1.0, [1e-40, -3e-42, 1.4e-45]),
+    "non_finite": (1.0, [float("inf"), float("-inf"), float("nan")]),
+    "f32_overflow": (2.0 ** 16, [1e38, -1e38]),          # x * s overflows f32 itself
+    "clean": (4.0, []),
+}
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 4097, (1 << 20) + 3])
+@pytest.mark.parametrize("case", list(_CAST_CASES))
+def test_cast_f32_to_f16_bits_and_counts_vs_float64(case, n):
+    """muse_cast_f32_to_f16 (the f16 mode's operand images, and the overflow counter FusedAdamW's device-side skip reads) against
+    numpy's float64 reference: every output bit, and both counters as ELEMENT counts - an input that already is inf / NaN and an
+    f32-overflowing x * s are overflows too, -0.0 is not flushed.  Special values sit at random positions among ordinary ones
+    (so the 3-element tail and, at n = 4097 / 2^20 + 3, lanes that convert several offending elements are exercised)."""
+    ops = _ops()
+    s, specials = _CAST_CASES[case]
+    rng = np.random.default_rng(n * 31 + len(case))
+    x = (rng.standard_normal(n) * (8.0 / s)).astype(np.float32)
+    x[rng.random(n) < 0.01] = -0.0
+    if specials:
+        k = min(n, max(len(specials), n // 97))
+        pos = rng.choice(n, size=k, replace=False)
+        x[pos] = np.resize(np.array(specials, dtype=np.float32), k)
+        if n >= 4097:   # several offending elements handled by ONE lane: the 4-element group of lane 0 and its next grid-stride turn
+            x[[0, 1, 3]] = specials[0]
+            stride = 4 * 256 * min(4096, (n // 4 + 255) // 256)
+            if stride + 3 < n:
+                x[stride + 2] = specials[-1]
+    ref_bits, ref_ov, ref_fl = _f16_cast_reference(x, s)
+    stats = torch.zeros(2, dtype=torch.int32, device=DEV)
+    out = ops.cast_to_f16(torch.from_numpy(x).to(DEV), s, stats)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().view(np.uint16)
+    bad = np.nonzero(got != ref_bits)[0]
+    assert bad.size == 0, [(float(x[i]), hex(got[i]), hex(ref_bits[i])) for i in bad[:8]]
+    assert stats.tolist() == [ref_ov, ref_fl], (stats.tolist(), ref_ov, ref_fl)
+    if n >= len(specials):   # (every special value placed: the case really exercises what it names)
+        assert (ref_ov > 0) == (case in ("boundaries", "non_finite", "f32_overflow"))
+        assert (ref_fl > 0) == (case in ("subnormal_ties", "f32_subnormals"))

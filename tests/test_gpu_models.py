@@ -1279,3 +1279,163 @@ def test_train_step_on_pre_encoded_tokens_without_a_tokenizer():
     opt.end_step_in_backward(m2, failed=True)
     with pytest.raises(MuseHipError, match="failed inside backward"):
         opt.step()
+
+
+def _f16_flat_model(scale):
+    """the benched flat engine at config B's width (two layers) in the "f16" mode, started at a gradient scale that overflows"""
+    cfg = dict(W.TRANSFORMER_B, num_hidden_layers=2)
+    m, _ = _build_transformer(cfg, 5, "f16")
+    m.f16_grad_scale = scale
+    ids, labels = W.transformer_inputs(cfg, 2, 6)
+    return m, cfg, ids.to(DEV), labels.to(DEV)
+
+
+def _adamw_f64_reference(opt, model, p0, g, m0, v0):
+    """one torch.optim.AdamW step in float64 on copies of the flat engine's parameters: step count, moments and hyper-parameters of
+    `opt` (`p0`, `g`, `m0`, `v0`: flat buffers before the step) -> the expected flat parameters after it"""
+    order, offs = model._param_order(), model._offsets
+    twin = {id(p): torch.nn.Parameter(p0[o:o + p.numel()].double().cpu().clone()) for p, o in zip(order, offs)}
+    groups = [dict({k: v for k, v in grp.items() if k != "params"}, params=[twin[id(p)] for p in grp["params"]]) for grp in opt.param_groups]
+    ref = torch.optim.AdamW(groups, foreach=False)
+    for p, o in zip(order, offs):
+        t = twin[id(p)]
+        t.grad = g[o:o + p.numel()].double().cpu().clone()
+        ref.state[t] = {"step": torch.tensor(float(opt._step - 1), dtype=torch.float64),
+                        "exp_avg": m0[o:o + p.numel()].double().cpu().clone(), "exp_avg_sq": v0[o:o + p.numel()].double().cpu().clone()}
+    ref.step()
+    return {id(p): twin[id(p)].detach() for p in order}
+
+
+@pytest.mark.parametrize("grouped", [False, True])
+def test_flat_engine_f16_overflow_guard(grouped):
+    """the flat engine's "f16" mode (the benched transformer_f16 leg) under muse.FusedAdamW.  A backward pass whose gradient
+    operands overflow half's range makes NaN gradients: the flat AdamW kernels (adamw_flat / adamw_flat_groups) must skip the update ON
+    THE DEVICE - parameters and both moments bit-identical, everything finite - and the next backward pass must halve the scale.  The
+    first update that is applied equals one float64 torch.optim.AdamW step from the snapshotted gradient and state."""
+    import muse
+    from muse import ops
+    m, cfg, ids, labels = _f16_flat_model(2.0 ** 30)
+    params = muse.grouped_parameters(m, 0.05) if grouped else m.parameters()
+    opt = muse.FusedAdamW(params, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.05, eps=1e-8)
+    assert len(opt.param_groups) == (2 if grouped else 1)
+    halves, launches = [], []
+    inner_gemm, inner_flat, inner_groups = ops.gemm, ops.adamw_flat, ops.adamw_flat_groups
+    ops.gemm = lambda *a, **k: (halves.append(1) if a[0].dtype == torch.float16 else None, inner_gemm(*a, **k))[1]
+    ops.adamw_flat = lambda *a, **k: (launches.append("flat"), inner_flat(*a, **k))[1]
+    ops.adamw_flat_groups = lambda *a, **k: (launches.append("groups"), inner_groups(*a, **k))[1]
+    overflowed_steps, applied = 0, False
+    scale_prev, skipped_prev, ov = None, 0, 0
+    try:
+        for it in range(12):
+            m.zero_grad(set_to_none=True)
+            _, loss = m(input_ids=ids, labels=labels)
+            loss.backward()
+            torch.cuda.synchronize()
+            images = m.__dict__["_f16_images"]
+            scale = images.grad_scale
+            skipped = m.__dict__.get("_f16_skipped_steps", 0)
+            if it > 0 and ov:        # the previous iteration overflowed: this backward pass halved the scale
+                assert scale == scale_prev / 2 and skipped == skipped_prev + 1, (scale, scale_prev, skipped, skipped_prev)
+            elif it > 0:
+                assert scale == scale_prev and skipped == skipped_prev
+            ov = int(images._stats[0])
+            p0 = m.flat_params().clone()
+            g = m.flat_grads().clone()
+            m0 = opt._m.clone() if opt._m is not None else torch.zeros_like(p0)
+            v0 = opt._v.clone() if opt._v is not None else torch.zeros_like(p0)
+            opt.step()
+            torch.cuda.synchronize()
+            assert launches and launches[-1] == ("groups" if grouped else "flat")
+            assert all(bool(torch.isfinite(t).all()) for t in (m.flat_params(), opt._m, opt._v)), it
+            if it == 0:
+                assert ov > 0 and not bool(torch.isfinite(g).all())    # (the start scale really overflows: NaN gradients)
+            if ov:
+                overflowed_steps += 1
+                assert torch.equal(m.flat_params(), p0) and torch.equal(opt._m, m0) and torch.equal(opt._v, v0), it
+            else:
+                assert bool(torch.isfinite(g).all())
+                want = _adamw_f64_reference(opt, m, p0, g, m0, v0)
+                for p in m._param_order():
+                    assert maxrel(p.detach().reshape(-1), want[id(p)]) < 2e-6
+                assert not torch.equal(m.flat_params(), p0)
+                applied = True
+                break
+            scale_prev, skipped_prev = scale, skipped
+    finally:
+        ops.gemm, ops.adamw_flat, ops.adamw_flat_groups = inner_gemm, inner_flat, inner_groups
+    print("flat f16 guard: overflowed steps", overflowed_steps, "-> scale", m.f16_grad_scale, "; half products", len(halves))
+    assert applied and overflowed_steps >= 1 and len(halves) > 0
+
+
+def test_flat_engine_f16_train_step_guard():
+    """the bench path of the transformer_f16 leg: muse.TrainStep + FusedAdamW, four steps from an overflowing gradient scale - the
+    parameters stay finite, at least one update was skipped and the scale came down"""
+    import muse
+    m, cfg, ids, labels = _f16_flat_model(2.0 ** 30)
+    opt = muse.FusedAdamW(m.parameters(), lr=1e-3, betas=(0.9, 0.99), weight_decay=0.01, eps=1e-8)
+    step = muse.TrainStep(None, m, opt)
+    gen = torch.Generator().manual_seed(7)
+    B, S = 4, cfg["num_vq_tokens"]
+    tokens = torch.randint(0, cfg["codebook_size"], (B, S), generator=gen).to(DEV)
+    cls = torch.randint(0, cfg["num_classes"], (B,), generator=gen).to(DEV)
+    before = m.flat_params().clone()
+    for _ in range(4):
+        step(None, cls, torch.rand(B, generator=gen).to(DEV), torch.rand(B, S, generator=gen).to(DEV), image_tokens=tokens)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(m.flat_params()).all())
+    m.zero_grad(set_to_none=True)
+    _, loss = m(input_ids=ids, labels=labels)
+    loss.backward()                                     # (reads the last step's counters)
+    skipped = m.__dict__.get("_f16_skipped_steps", 0)
+    print("flat f16 TrainStep: skipped", skipped, "; scale", m.f16_grad_scale)
+    assert skipped >= 1 and m.f16_grad_scale < 2.0 ** 30
+    assert not torch.equal(m.flat_params(), before) or skipped == 4
+
+
+def test_general_engine_bf16x3_planes_survive_a_mode_round_trip():
+    """the general (text-conditioned) engine at a width where the bf16x3 weight planes are cached (tape_ops._wp): bf16x3 -> bf16 ->
+    bf16x3 with two FusedAdamW steps in bf16.  Back in bf16x3 every cached plane pair is a fresh split of the f32 master and the forward
+    equals a freshly built model's bit for bit; one more bf16x3 step leaves the planes fresh (the optimizer writes them again)."""
+    import muse
+    from muse import ops
+    cfg = dict(W.TRANSFORMER_TEXT_TINY, vocab_size=520, codebook_size=512, hidden_size=256, num_attention_heads=4, intermediate_size=512,
+               max_position_embeddings=128, num_vq_tokens=128, encoder_hidden_size=128)
+    ids, labels, enc = W.transformer_text_inputs(cfg, 2, 77, 8)
+    ids, labels, enc = ids.to(DEV), labels.to(DEV), enc.to(DEV)
+
+    def build():
+        return _build_general(cfg, 9, "bf16x3")
+
+    def step(m, opt):
+        m.zero_grad(set_to_none=True)
+        _, loss = m(input_ids=ids, encoder_hidden_states=enc, labels=labels)
+        loss.backward()
+        opt.step()
+        torch.cuda.synchronize()
+
+    def planes_fresh(m):
+        cache = m.__dict__.get("_pcache", {})
+        assert len(cache) > 0
+        params = {id(p): p for p in m.parameters()}
+        for key, (ver, wp) in cache.items():
+            ws = [params[k] for k in key]
+            assert torch.equal(wp.planes, ops._split_planes_now(torch.cat([w.detach().reshape(w.shape[0], -1) for w in ws]).contiguous()))
+
+    m = build()
+    opt = muse.FusedAdamW(m.parameters(), lr=1e-3, betas=(0.9, 0.99), weight_decay=0.01, eps=1e-8)
+    step(m, opt)
+    planes_fresh(m)
+    m.set_compute_dtype(torch.bfloat16)
+    before = [p.detach().clone() for p in m.parameters()]
+    step(m, opt)
+    step(m, opt)
+    assert any(not torch.equal(p.detach(), b) for p, b in zip(m.parameters(), before))
+    m.set_compute_dtype("bf16x3")
+    fresh = build()
+    fresh.load_state_dict({k: v.detach().clone() for k, v in m.state_dict().items()})
+    la, lossa = m(input_ids=ids, encoder_hidden_states=enc, labels=labels)          # (a training forward: the one that reads the planes)
+    lb, lossb = fresh(input_ids=ids, encoder_hidden_states=enc, labels=labels)
+    assert torch.equal(la, lb) and torch.equal(lossa, lossb)
+    planes_fresh(m)
+    step(m, opt)
+    planes_fresh(m)

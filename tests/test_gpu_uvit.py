@@ -951,3 +951,240 @@ def test_uvit_unfused_routes_still_match_the_reference(golden_dir, batch_mappers
     assert abs(float(loss.detach()) - float(g["loss"])) < 1e-4 * abs(float(g["loss"]))
     loss.backward()
     _grad_check(model, {k[len("grad."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("grad.")}, 5e-4)
+
+
+# ---- the f16 mode's overflow guard and the bf16x3 weight-plane cache across steps -------------------------------------
+_TOY_UVIT = dict(vocab_size=520, hidden_size=256, in_channels=128, block_out_channels=(128,), encoder_hidden_size=128, cond_embed_dim=128,
+                 micro_cond_encode_dim=32, micro_cond_embed_dim=160, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512,
+                 block_num_heads=2, num_res_blocks=1, codebook_size=512, mask_token_id=519)
+
+
+def _toy_uvit_inputs():
+    """the batch of test_f16_mode_optimizer_guard: (ids, enc, cond, micro), labels"""
+    B, S = 2, 256
+    gen = torch.Generator().manual_seed(3)
+    ids = torch.randint(0, 512, (B, S), generator=gen).to(DEV)
+    labels = torch.where(torch.rand(B, S, generator=gen) < 0.5, torch.randint(0, 512, (B, S), generator=gen), torch.full((B, S), -100)).to(DEV)
+    enc, cond = torch.randn(B, 77, 128, generator=gen).to(DEV), torch.randn(B, 128, generator=gen).to(DEV)
+    micro = torch.tensor([[256.0, 256.0, 0.0, 0.0, 6.0]]).repeat(B, 1).to(DEV)
+    return (ids, enc, cond, micro), labels
+
+
+def _toy_uvit(mode, seed=11):
+    import muse
+    torch.manual_seed(seed)
+    model = muse.MaskGiTUViT(**_TOY_UVIT)
+    model.to(DEV).train().set_compute_dtype(mode)
+    return model
+
+
+def _fused_adamw(model):
+    import muse
+    return muse.FusedAdamW(muse.grouped_parameters(model, 0.01), lr=1e-3, betas=(0.9, 0.99), weight_decay=0.01, eps=1e-8)
+
+
+def _check_step_is_float64_adamw(opt, step_fn):
+    """run `step_fn` (one opt.step()) and check every parameter moved as one float64 torch.optim.AdamW step from its gradient and the
+    optimizer's moments / step count (2e-6 of the parameter's largest element, test_adamw_flat_groups_matches_torch_and_flat's bound)"""
+    flat = getattr(opt, "_model", None) is not None
+    ps = opt._all_params()
+    if flat:
+        model = opt._model()
+        offs = dict(zip([id(p) for p in model._param_order()], model._offsets))
+        state = lambda t, p: None if t is None else t[offs[id(p)]:offs[id(p)] + p.numel()].view(p.shape)    # noqa: E731
+    else:
+        state = lambda t, p: None if t is None else t.get(id(p))                                           # noqa: E731
+    twins = {id(p): torch.nn.Parameter(p.detach().double().cpu().clone()) for p in ps}
+    groups = [dict({k: v for k, v in grp.items() if k != "params"}, params=[twins[id(p)] for p in grp["params"]]) for grp in opt.param_groups]
+    ref = torch.optim.AdamW(groups, foreach=False)
+    for p in ps:
+        t = twins[id(p)]
+        t.grad = p.grad.detach().double().cpu().clone()
+        m0, v0 = state(opt._m, p), state(opt._v, p)
+        ref.state[t] = {"step": torch.tensor(float(opt._step), dtype=torch.float64),
+                        "exp_avg": torch.zeros_like(t) if m0 is None else m0.double().cpu().clone(),
+                        "exp_avg_sq": torch.zeros_like(t) if v0 is None else v0.double().cpu().clone()}
+    before = [p.detach().clone() for p in ps]
+    step_fn()
+    torch.cuda.synchronize()
+    ref.step()
+    assert any(not torch.equal(p.detach(), b) for p, b in zip(ps, before)), "the update was not applied"
+    for p in ps:
+        assert rel_err(p, twins[id(p)]) < 2e-6
+
+
+def _backward(model, args, labels):
+    model.zero_grad(set_to_none=True)
+    out = model(*args, labels=labels) if isinstance(args, tuple) else model(input_ids=args, labels=labels)
+    out[1].backward()
+    torch.cuda.synchronize()
+    return float(out[1].detach())
+
+
+def _assert_overflowed_unconsumed(model):
+    images = model.__dict__["_f16_images"]
+    assert int(images._stats[0]) > 0                 # (the pass really overflowed; read without resetting the counter)
+    return images
+
+
+def _flat_transformer(mode, scale=None):
+    import muse
+    import weights as W
+    cfg = dict(W.TRANSFORMER_B, num_hidden_layers=2)
+    m = muse.MaskGitTransformer(**cfg)
+    m.load_state_dict(W.fill_state_dict(W.transformer_shapes(cfg), 5, "transformer"))
+    m.to(DEV).train().set_compute_dtype(mode)
+    if scale is not None:
+        m.f16_grad_scale = scale
+    ids, labels = W.transformer_inputs(cfg, 2, 6)
+    return m, ids.to(DEV), labels.to(DEV)
+
+
+@pytest.mark.parametrize("other", ["uvit_f32", "flat_f32"])
+def test_f16_guard_belongs_to_the_model_that_made_it(other):
+    """(a) an f16 U-ViT runs a backward pass that overflows and takes NO optimizer step; then a different model (the f32 U-ViT / the
+    flat transformer) runs a step of its own FusedAdamW: that update is applied and equals a float64 torch.optim.AdamW step.  (b) The
+    f16 model's own next optimizer step is still skipped, and its next backward pass halves the scale."""
+    args, labels = _toy_uvit_inputs()
+    f16 = _toy_uvit("f16")
+    opt16 = _fused_adamw(f16)
+    _backward(f16, args, labels)                     # default scale: this toy model overflows (test_f16_mode_optimizer_guard)
+    _assert_overflowed_unconsumed(f16)
+    scale0 = f16.f16_grad_scale_for(f16.__dict__.get("_loss_rows", 1))
+    if other == "uvit_f32":
+        m2 = _toy_uvit(torch.float32, seed=12)
+        _backward(m2, args, labels)
+    else:
+        m2, ids, lab2 = _flat_transformer(torch.float32)
+        _backward(m2, ids, lab2)
+    opt2 = _fused_adamw(m2)
+    _check_step_is_float64_adamw(opt2, opt2.step)
+    before = [p.detach().clone() for p in f16.parameters()]
+    opt16.step()
+    torch.cuda.synchronize()
+    assert all(torch.equal(p.detach(), b) for p, b in zip(f16.parameters(), before))
+    _backward(f16, args, labels)
+    assert f16.__dict__.get("_f16_skipped_steps", 0) == 1 and f16.f16_grad_scale == scale0 / 2
+
+
+def test_f16_guard_of_the_flat_engine_belongs_to_it():
+    """(c) the same with the flat engine as the f16 model: its overflowed pass gates neither the f32 U-ViT's step nor anything but its
+    own next step (skipped on the device), after which its scale halves"""
+    f16, ids, labels = _flat_transformer("f16", 2.0 ** 30)
+    opt16 = _fused_adamw(f16)
+    _backward(f16, ids, labels)
+    _assert_overflowed_unconsumed(f16)
+    args, lab2 = _toy_uvit_inputs()
+    m2 = _toy_uvit(torch.float32, seed=12)
+    _backward(m2, args, lab2)
+    opt2 = _fused_adamw(m2)
+    _check_step_is_float64_adamw(opt2, opt2.step)
+    before = f16.flat_params().clone()
+    opt16.step()
+    torch.cuda.synchronize()
+    assert torch.equal(f16.flat_params(), before)
+    _backward(f16, ids, labels)
+    assert f16.__dict__.get("_f16_skipped_steps", 0) == 1 and f16.f16_grad_scale == 2.0 ** 29
+
+
+def test_f16_update_grad_scale_with_fused_adamw_applies_the_policy_once():
+    """f16_update_grad_scale() after backward, then FusedAdamW.step(): the explicit call has applied GradScaler's policy to the pass, the
+    optimizer's counter snapshot must not feed it a second time.  growth_interval 3 at a scale this toy model does not overflow at:
+    the scale doubles after exactly steps 3 and 6 of seven."""
+    args, labels = _toy_uvit_inputs()
+    model = _toy_uvit("f16")
+    model.f16_grad_scale, model.f16_growth_interval = 2.0 ** 12, 3
+    opt = _fused_adamw(model)
+    scales = []
+    for _ in range(7):
+        _backward(model, args, labels)
+        assert model.f16_update_grad_scale(growth_interval=3)      # (nothing overflowed: every step is applied)
+        opt.step()
+        torch.cuda.synchronize()
+        scales.append(model.f16_grad_scale)
+    images = model.__dict__["_f16_images"]
+    assert images.misses + images.produced > 0                     # (half operand images were made: the mode ran)
+    assert scales == [2.0 ** 12] * 2 + [2.0 ** 13] * 3 + [2.0 ** 14] * 2, scales
+    assert model.__dict__.get("_f16_skipped_steps", 0) == 0
+
+
+def _assert_planes_fresh(model):
+    from muse import ops
+    cache = model.__dict__.get("_pcache", {})
+    assert len(cache) > 0
+    params = {id(p): p for p in model.parameters()}
+    for key, (ver, wp) in cache.items():
+        ws = [params[k] for k in key]
+        fresh = ops._split_planes_now(torch.cat([w.detach().reshape(w.shape[0], -1) for w in ws], dim=0).contiguous())
+        assert torch.equal(wp.planes, fresh), "stale bf16x3 operand planes"
+
+
+def _assert_forward_is_a_fresh_models(model, make, args, labels):
+    """the next forward of `model` gives the logits and loss - bit for bit - of a freshly built model loaded with its state_dict, in the
+    same compute mode and train / eval state"""
+    fresh = make()
+    fresh.load_state_dict({k: v.detach().clone() for k, v in model.state_dict().items()})
+    fresh.train(model.training)
+    la, lossa = model(*args, labels=labels)         # (a training forward: the one that reads the cached planes)
+    lb, lossb = fresh(*args, labels=labels)
+    assert torch.equal(la, lb) and torch.equal(lossa, lossb)
+    _assert_planes_fresh(model)
+
+
+def _write_two_weights(model):
+    """p.data writes on a q|k|v member and on a single Linear whose planes are cached"""
+    keys = list(model.__dict__.get("_pcache", {}))
+    qkv, single = [k for k in keys if len(k) == 3], [k for k in keys if len(k) == 1]
+    assert qkv and single
+    params = {id(p): p for p in model.parameters()}
+    with torch.no_grad():
+        for p in (params[qkv[0][1]], params[single[0][0]]):
+            p.data.copy_(p.data * 0.75 + 0.01)
+
+
+@pytest.mark.parametrize("how", ["mark_weights_changed", "train_eval"])
+def test_bf16x3_planes_follow_p_data_writes(how):
+    """bf16x3 mode (weight operand planes cached across steps, tape_ops._wp): a `p.data.copy_()` write followed by
+    mark_weights_changed() - or by a train() -> eval() transition (what EMA copy_to / restore does) - must not leave the old planes
+    serving the weight GEMMs"""
+    args, labels = _toy_uvit_inputs()
+    model = _toy_uvit("bf16x3")
+    opt = _fused_adamw(model)
+    _backward(model, args, labels)
+    opt.step()
+    _write_two_weights(model)
+    if how == "mark_weights_changed":
+        model.mark_weights_changed()
+    else:
+        model.eval()                                 # (EMA copy_to / restore around an evaluation: train -> eval -> train)
+        assert not model.__dict__.get("_pcache") and all(getattr(p, "_muse_planes", None) is None for p in model.parameters())
+        model.train()
+    _assert_forward_is_a_fresh_models(model, lambda: _toy_uvit("bf16x3", seed=1), args, labels)
+
+
+@pytest.mark.parametrize("other", [torch.bfloat16, "f16"])
+def test_bf16x3_planes_survive_a_mode_round_trip(other):
+    """bf16x3 -> `other` -> bf16x3 with two FusedAdamW steps in `other` (whose weight copy is the one the optimizer refreshes there):
+    back in bf16x3 the planes are those of the updated weights, and one more bf16x3 step leaves them fresh - the optimizer writes
+    them again"""
+    args, labels = _toy_uvit_inputs()
+    model = _toy_uvit("bf16x3")
+    opt = _fused_adamw(model)
+    _backward(model, args, labels)
+    opt.step()
+    _assert_planes_fresh(model)
+    model.set_compute_dtype(other)
+    if other == "f16":
+        model.f16_grad_scale = 2.0 ** 12                  # (a scale this toy model does not overflow at: both steps are applied)
+    before = [p.detach().clone() for p in model.parameters()]
+    for _ in range(2):
+        _backward(model, args, labels)
+        opt.step()
+    torch.cuda.synchronize()
+    assert any(not torch.equal(p.detach(), b) for p, b in zip(model.parameters(), before))
+    model.set_compute_dtype("bf16x3")
+    _assert_forward_is_a_fresh_models(model, lambda: _toy_uvit("bf16x3", seed=1), args, labels)
+    _backward(model, args, labels)
+    opt.step()
+    torch.cuda.synchronize()
+    _assert_planes_fresh(model)
