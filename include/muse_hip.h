@@ -250,6 +250,18 @@ int muse_cross_entropy_fwd(const void* logits, int32_t dtype, const int64_t* lab
 int muse_cross_entropy_bwd(const void* logits, int32_t dtype, const int64_t* labels, const float* lse,
                            const float* loss_out, const float* grad_out, void* dlogits, int32_t dl_dtype, int64_t rows,
                            int32_t vocab, int64_t ld, float label_smoothing, void* stream);
+/* soft_target_cross_entropy (training/train_maskgit_imagenet.py:101-117) on the class-conditional layout.  logits f32 [rows, ld]
+ * with rows = B * seq1 (seq1 = S + 1, position 0 = class token), labels int64 [rows], soft f32 [B * S, K], K <= ld: only the first
+ * K columns take part.  Row r = (b, s) is active iff s >= 1 and labels[r] != -100; its soft row is b * S + s - 1.
+ * fwd: row_loss / lse / psum per row (0 for inactive rows), row_loss = psum * lse - sum(p * l); then
+ * loss_out = (sum(row_loss) / n_active, n_active), one block in a fixed order.
+ * bwd: dlogits [rows, ldo] (MUSE_F32 or MUSE_BF16) = grad_out[0] / loss_out[1] * (softmax * psum - p) on the first K columns of
+ * active rows, exact 0 on every other element of [0, ldo); no host synchronisation. */
+int muse_soft_ce_fwd(const float* logits, const int64_t* labels, const float* soft, float* row_loss, float* lse, float* psum,
+                     float* loss_out, int64_t rows, int32_t seq1, int32_t K, int64_t ld, void* stream);
+int muse_soft_ce_bwd(const float* logits, const int64_t* labels, const float* soft, const float* lse, const float* psum,
+                     const float* loss_out, const float* grad_out, void* dlogits, int32_t dl_dtype, int64_t rows, int32_t seq1,
+                     int32_t K, int64_t ld, int64_t ldo, void* stream);
 
 /* AdamW over one flat f32 buffer (torch.optim.AdamW / apex FusedAdam(adam_w_mode) semantics,
  * training/train_maskgit_imagenet.py:242-261,438); optionally refreshes the bf16 compute copy of the weights. */

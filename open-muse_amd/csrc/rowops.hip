@@ -1398,6 +1398,189 @@ extern "C" int muse_cross_entropy_bwd(const void* logits, int32_t dtype, const i
   return (int)hipGetLastError();
 }
 
+// =================================================================================================================
+// Soft-target cross entropy (soft_target_cross_entropy of training/train_maskgit_imagenet.py).  logits [B*S1, ld] f32 with
+// S1 = S + 1; row r is (b, s) = (r / S1, r % S1) and is ACTIVE iff s >= 1 and labels[r] != -100; its soft row is b*S + s - 1 of
+// soft [B*S, K] (K <= ld).  Only the first K columns take part.  row loss = psum * lse - sum(p * l), psum = sum(p).
+// One wave per row.  NCH > 0: K == NCH * 256, the row is held in registers (VEC: 16-byte loads at 4 * (lane + 64 j), else
+// dwords at lane + 64 i, for rows whose stride is not a multiple of 4 floats); NCH == 0: any K, two passes over memory.
+// =================================================================================================================
+__device__ __forceinline__ bool soft_row_active(long row, int S1, const int64_t* labels, long& srow) {
+  const long b = row / S1;
+  const int s = (int)(row - b * S1);
+  srow = b * (S1 - 1) + s - 1;
+  return s >= 1 && labels[row] != -100;
+}
+
+template <int NCH, bool VEC>
+__device__ __forceinline__ void soft_row_load(const float* __restrict__ xr, const float* __restrict__ pr, int lane, float (&x)[NCH * 4],
+                                              float (&p)[NCH * 4]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int c = (j * 64 + lane) * 4;
+      const f32x4 a = *(const f32x4*)(xr + c), q = *(const f32x4*)(pr + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { x[j * 4 + e] = a[e]; p[j * 4 + e] = q[e]; }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NCH * 4; ++i) { x[i] = xr[i * 64 + lane]; p[i] = pr[i * 64 + lane]; }
+  }
+}
+
+template <int NCH, bool VEC>
+__global__ __launch_bounds__(256) void soft_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                          const float* __restrict__ soft, float* __restrict__ row_loss,
+                                                          float* __restrict__ lse_o, float* __restrict__ psum_o, long rows, int S1,
+                                                          int K, long ld) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  long srow;
+  if (!soft_row_active(row, S1, labels, srow)) {   // masked_fill(padding_mask, 0): nothing of the row is read
+    if (lane == 0) { row_loss[row] = 0.f; lse_o[row] = 0.f; psum_o[row] = 0.f; }
+    return;
+  }
+  const float* xr = logits + row * ld;
+  const float* pr = soft + srow * (long)K;
+  float m = -INFINITY, sp = 0.f, spl = 0.f, se = 0.f;
+  if constexpr (NCH > 0) {
+    float x[NCH * 4], p[NCH * 4];
+    soft_row_load<NCH, VEC>(xr, pr, lane, x, p);
+#pragma unroll
+    for (int i = 0; i < NCH * 4; ++i) { m = fmaxf(m, x[i]); sp += p[i]; spl += p[i] * x[i]; }
+    m = wave_max(m);
+#pragma unroll
+    for (int i = 0; i < NCH * 4; ++i) se += expf(x[i] - m);
+  } else {
+    for (int c = lane; c < K; c += 64) { const float v = xr[c], q = pr[c]; m = fmaxf(m, v); sp += q; spl += q * v; }
+    m = wave_max(m);
+    for (int c = lane; c < K; c += 64) se += expf(xr[c] - m);
+  }
+  se = wave_sum(se);
+  sp = wave_sum(sp);
+  spl = wave_sum(spl);
+  if (lane == 0) {
+    const float lse = m + logf(se);
+    lse_o[row] = lse;
+    psum_o[row] = sp;
+    row_loss[row] = sp * lse - spl;
+  }
+}
+
+// loss_out = (sum of row_loss over active rows / n_active, n_active): one block, fixed order (bitwise reproducible)
+__global__ __launch_bounds__(1024) void soft_ce_reduce_kernel(const float* __restrict__ row_loss, const int64_t* __restrict__ labels,
+                                                              float* __restrict__ out, long rows, int S1) {
+  __shared__ double ssum[16];
+  __shared__ int scnt[16];
+  double s = 0.0; int n = 0;
+  for (long r = threadIdx.x; r < rows; r += 1024) {
+    long srow;
+    if (soft_row_active(r, S1, labels, srow)) { s += (double)row_loss[r]; ++n; }
+  }
+  s = wave_sum_d(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) { ssum[threadIdx.x >> 6] = s; scnt[threadIdx.x >> 6] = n; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0; int c = 0;
+    for (int i = 0; i < 16; ++i) { t += ssum[i]; c += scnt[i]; }
+    out[0] = (float)(t / (double)c);  // n_active = 0 -> nan, as the reference's division
+    out[1] = (float)c;
+  }
+}
+
+extern "C" int muse_soft_ce_fwd(const float* logits, const int64_t* labels, const float* soft, float* row_loss, float* lse, float* psum,
+                                float* loss_out, int64_t rows, int32_t seq1, int32_t K, int64_t ld, void* stream) {
+  if (rows <= 0 || seq1 < 2 || rows % seq1 != 0 || K <= 0 || K > ld) return MUSE_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)((rows + 3) / 4));
+  const bool vec = ld % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)soft & 15) == 0;
+#define SCF(N, VEC) hipLaunchKernelGGL((soft_ce_fwd_kernel<N, VEC>), grid, dim3(256), 0, s, logits, labels, soft, row_loss, lse, psum, (long)rows, seq1, K, (long)ld)
+  if (K == 1024 && vec) SCF(4, true);
+  else if (K == 1024) SCF(4, false);
+  else if (K == 512 && vec) SCF(2, true);
+  else if (K == 256 && vec) SCF(1, true);
+  else SCF(0, false);
+#undef SCF
+  hipLaunchKernelGGL(soft_ce_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float*)row_loss, labels, loss_out, (long)rows, seq1);
+  return (int)hipGetLastError();
+}
+
+// d loss / d logits = g / n_active * (exp(l - lse) * psum - p) on the first K columns of active rows; every other element of the
+// row [0, ldo) is written as an exact 0 (columns >= K, rows with s = 0, label -100).  g and n_active are read on the device.
+template <int NCH, bool VEC, typename TO>
+__global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                          const float* __restrict__ soft, const float* __restrict__ lse,
+                                                          const float* __restrict__ psum, const float* __restrict__ loss_out,
+                                                          const float* __restrict__ gout, TO* __restrict__ dl, long rows, int S1,
+                                                          int K, long ld, long ldo) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  TO* dr = dl + row * ldo;
+  long srow;
+  const bool active = soft_row_active(row, S1, labels, srow);
+  int c0 = 0;   // first column still to be written (as 0)
+  if (active) {
+    const float g = gout[0] / loss_out[1];
+    const float l = lse[row], ps = psum[row];
+    const float* xr = logits + row * ld;
+    const float* pr = soft + srow * (long)K;
+    if constexpr (NCH > 0) {
+      float x[NCH * 4], p[NCH * 4];
+      soft_row_load<NCH, VEC>(xr, pr, lane, x, p);
+      if constexpr (VEC) {
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+          float v[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = g * (expf(x[j * 4 + e] - l) * ps - p[j * 4 + e]);
+          V4<TO>::store(dr + (j * 64 + lane) * 4, v);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NCH * 4; ++i) Elem<TO>::store(dr + i * 64 + lane, g * (expf(x[i] - l) * ps - p[i]));
+      }
+    } else {
+      for (int c = lane; c < K; c += 64) Elem<TO>::store(dr + c, g * (expf(xr[c] - l) * ps - pr[c]));
+    }
+    c0 = K;
+  }
+  if (VEC && c0 % 4 == 0) {
+    const float z[4] = {0.f, 0.f, 0.f, 0.f};
+    for (long c = c0 + lane * 4; c < ldo; c += 256) V4<TO>::store(dr + c, z);
+  } else {
+    for (long c = c0 + lane; c < ldo; c += 64) Elem<TO>::store(dr + c, 0.f);
+  }
+}
+
+extern "C" int muse_soft_ce_bwd(const float* logits, const int64_t* labels, const float* soft, const float* lse, const float* psum,
+                                const float* loss_out, const float* grad_out, void* dlogits, int32_t dl_dtype, int64_t rows, int32_t seq1,
+                                int32_t K, int64_t ld, int64_t ldo, void* stream) {
+  if (rows <= 0 || seq1 < 2 || rows % seq1 != 0 || K <= 0 || K > ld || K > ldo) return MUSE_ERR_BAD_ARG;
+  if (dl_dtype != MUSE_F32 && dl_dtype != MUSE_BF16) return MUSE_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)((rows + 3) / 4));
+  // 16-byte (f32) / 8-byte (bf16) stores need every output row to start on that boundary
+  const bool vec = ld % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)soft & 15) == 0 &&
+                   ((uintptr_t)dlogits & (dl_dtype == MUSE_F32 ? 15 : 7)) == 0;
+#define SCB(N, VEC, TO) hipLaunchKernelGGL((soft_ce_bwd_kernel<N, VEC, TO>), grid, dim3(256), 0, s, logits, labels, soft, lse, psum, loss_out, grad_out, (TO*)dlogits, (long)rows, seq1, K, (long)ld, (long)ldo)
+#define SCB_T(TO)                                   \
+  if (K == 1024 && vec) SCB(4, true, TO);           \
+  else if (K == 1024) SCB(4, false, TO);            \
+  else if (K == 512 && vec) SCB(2, true, TO);       \
+  else if (K == 256 && vec) SCB(1, true, TO);       \
+  else SCB(0, false, TO);
+  if (dl_dtype == MUSE_F32) { SCB_T(float) }
+  else { SCB_T(bf16_t) }
+#undef SCB_T
+#undef SCB
+  return (int)hipGetLastError();
+}
+
 // Overflow guard of the "f16" compute mode (muse_adamw_skip_flag): when set, every AdamW kernel (flat, flat groups, multi-tensor) reads *skip first and leave every
 // tensor untouched if it is non-zero - the gradients of a backward pass whose operand images overflowed half's range are NaN, and the
 // update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host round trip).  Process state like

@@ -97,6 +97,9 @@ SIGNATURES = {
                                c_void_p],
     "muse_cross_entropy_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int,
                                c_i64, c_float, c_void_p],
+    "muse_soft_ce_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_void_p],
+    "muse_soft_ce_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int,
+                         c_i64, c_i64, c_void_p],
     "muse_adamw_flat": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float,
                         c_float, c_int, c_float, c_void_p],
     "muse_adamw_multi": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p],

@@ -1526,6 +1526,48 @@ def cross_entropy_bwd(logits, labels, lse, loss_out, grad_out, label_smoothing, 
     return dl
 
 
+def _soft_ce_check(logits, labels, soft, seq1):
+    require_gpu(logits, labels, soft)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype != torch.float32:
+        raise _hip.MuseHipError("soft_ce: logits must be f32 [rows, ld] with unit column stride")
+    rows, K = logits.shape[0], soft.shape[-1]
+    if (labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != rows or soft.dtype != torch.float32
+            or not soft.is_contiguous() or seq1 < 2 or rows % seq1 or soft.numel() != rows // seq1 * (seq1 - 1) * K
+            or K > logits.shape[1]):
+        raise _hip.MuseHipError(f"soft_ce: labels int64 [{rows}] and soft f32 [B*S, K <= {logits.shape[1]}] expected, got "
+                           f"{labels.dtype} {tuple(labels.shape)} / {soft.dtype} {tuple(soft.shape)} with S + 1 = {seq1}")
+    return rows, K
+
+
+def soft_ce_fwd(logits, labels, soft, seq1):
+    """soft-target cross entropy over the first K = soft.shape[-1] columns of logits [B*seq1, ld] (row stride ld; position 0 of every
+    sequence and label -100 rows are left out) -> (loss_out[2] = (mean loss, n_active), lse[rows], psum[rows])"""
+    rows, K = _soft_ce_check(logits, labels, soft, seq1)
+    dev = logits.device
+    row_loss = torch.empty(rows, dtype=torch.float32, device=dev)
+    lse = torch.empty(rows, dtype=torch.float32, device=dev)
+    psum = torch.empty(rows, dtype=torch.float32, device=dev)
+    loss_out = torch.empty(2, dtype=torch.float32, device=dev)
+    check(lib().muse_soft_ce_fwd(logits.data_ptr(), labels.data_ptr(), soft.data_ptr(), row_loss.data_ptr(), lse.data_ptr(),
+                                 psum.data_ptr(), loss_out.data_ptr(), rows, seq1, K, logits.stride(0), stream()), "muse_soft_ce_fwd")
+    return loss_out, lse, psum
+
+
+def soft_ce_bwd(logits, labels, soft, seq1, lse, psum, loss_out, grad_out, out_dtype=torch.float32, width=None):
+    """d(loss)/d(logits) of soft_ce_fwd as a new [rows, width] tensor (width defaults to logits' column count): the gradient on the
+    first K columns of active rows, exact zeros everywhere else.  grad_out: the incoming scalar gradient, on the device."""
+    rows, K = _soft_ce_check(logits, labels, soft, seq1)
+    require_gpu(lse, psum, loss_out, grad_out)
+    width = logits.shape[1] if width is None else int(width)
+    if width < K:
+        raise _hip.MuseHipError(f"soft_ce_bwd: output width {width} < K = {K}")
+    dl = torch.empty((rows, width), dtype=out_dtype, device=logits.device)
+    check(lib().muse_soft_ce_bwd(logits.data_ptr(), labels.data_ptr(), soft.data_ptr(), lse.data_ptr(), psum.data_ptr(),
+                                 loss_out.data_ptr(), grad_out.data_ptr(), dl.data_ptr(), dt(dl), rows, seq1, K, logits.stride(0),
+                                 width, stream()), "muse_soft_ce_bwd")
+    return dl
+
+
 def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
     require_gpu(p, g, m, v)
     e0 = _prof_begin()

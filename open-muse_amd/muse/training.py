@@ -23,17 +23,26 @@ from ._hip import MuseHipError
 
 @torch.no_grad()
 def prepare_inputs_and_labels(vq_model, pixel_values, class_ids, mask_id, min_masking_rate: float = 0.0, timesteps=None,
-                              noise=None, generator=None, image_tokens=None, codebook_size=None):
-    """-> (input_ids [B,S+1], labels [B,S+1], soft_targets=None, mask_prob [B]).
+                              noise=None, generator=None, image_tokens=None, codebook_size=None, use_soft_code_target=False,
+                              soft_code_temp=1.0, use_stochastic_code=False):
+    """-> (input_ids [B,S+1], labels [B,S+1], soft_targets, mask_prob [B]).
 
     `timesteps` [B] and `noise` [B,S] are the two torch.rand draws of the reference (:375, :381); pass them in for
     bit-reproducible masks (parity tests), otherwise they are drawn on the GPU.  With pre-encoded `image_tokens` the
-    tokenizer is not touched: `vq_model` may be None when `codebook_size` (the class-token offset, :388) is given."""
+    tokenizer is not touched: `vq_model` may be None when `codebook_size` (the class-token offset, :388) is given.
+
+    `use_soft_code_target` (config.training.use_soft_code_target, :364-367): tokens and soft_targets [B, S, codebook] come from
+    `vq_model.get_soft_code(pixel_values, soft_code_temp, use_stochastic_code)`; otherwise soft_targets is None."""
+    if use_soft_code_target and image_tokens is not None:
+        raise ValueError("prepare_inputs_and_labels: use_soft_code_target needs the images - pre-encoded image_tokens carry no soft codes")
     if codebook_size is None:
         if vq_model is None:
             raise ValueError("prepare_inputs_and_labels: without a vq_model pass codebook_size (the class-token offset)")
         codebook_size = vq_model.num_embeddings
-    if image_tokens is None:
+    soft_targets = None
+    if use_soft_code_target:
+        soft_targets, image_tokens = vq_model.get_soft_code(pixel_values, temp=soft_code_temp, stochastic=use_stochastic_code)
+    elif image_tokens is None:
         image_tokens = vq_model.get_code(pixel_values)      # == vq_model.encode(pixel_values)[1] (:369) without the unused z_q
     B, S = image_tokens.shape
     dev = image_tokens.device
@@ -44,7 +53,52 @@ def prepare_inputs_and_labels(vq_model, pixel_values, class_ids, mask_id, min_ma
     input_ids, labels, mask_prob = ops.mask_sample(image_tokens.contiguous(), class_ids.contiguous(),
                                                    timesteps.float().contiguous(), noise.float().contiguous(), int(mask_id),
                                                    int(codebook_size), float(min_masking_rate))
-    return input_ids, labels, None, mask_prob
+    return input_ids, labels, soft_targets, mask_prob
+
+
+class _SoftTargetCE(torch.autograd.Function):
+    """muse_soft_ce_fwd / muse_soft_ce_bwd on logits [B, S+1, V]: the loss and, in backward, g_logits shaped like logits"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, soft_targets):
+        B, S1, V = logits.shape
+        x = logits.reshape(B * S1, V)
+        lab = labels.contiguous().view(-1)
+        soft = soft_targets.contiguous()
+        loss_out, lse, psum = ops.soft_ce_fwd(x, lab, soft, S1)
+        ctx.save_for_backward(x, lab, soft, lse, psum, loss_out)
+        ctx.shape = (B, S1, V)
+        return loss_out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, lab, soft, lse, psum, loss_out = ctx.saved_tensors
+        dl = ops.soft_ce_bwd(x, lab, soft, ctx.shape[1], lse, psum, loss_out, g.reshape(1).to(torch.float32).contiguous())
+        return dl.view(ctx.shape), None, None
+
+
+def soft_target_cross_entropy(logits, labels, soft_targets):
+    """soft_target_cross_entropy of training/train_maskgit_imagenet.py:101-117 (the class-conditional MaskGitTransformer's
+    loss under config.training.use_soft_code_target): position 0 (the class token) of logits [B, S+1, V] and labels [B, S+1] is
+    dropped, logits are cut to their first K = soft_targets.shape[-1] columns, and sum(-soft_targets * log_softmax) over the rows
+    whose label is not -100, divided by the number of those rows (0 rows: nan, like the reference).  Two HIP kernels; backward
+    returns d(loss)/d(logits) shaped like logits, zero outside the first K columns of counted rows.  f32 logits / targets only."""
+    ops.require_gpu(logits, labels, soft_targets)
+    if logits.dtype != torch.float32 or soft_targets.dtype != torch.float32:
+        raise MuseHipError(f"soft_target_cross_entropy: f32 logits and soft_targets only (got {logits.dtype} / {soft_targets.dtype})")
+    if labels.dtype != torch.int64:
+        raise ValueError(f"soft_target_cross_entropy: labels must be int64 (got {labels.dtype})")
+    if (logits.dim() != 3 or labels.dim() != 2 or soft_targets.dim() != 3 or tuple(labels.shape) != tuple(logits.shape[:2])
+            or logits.shape[1] < 2 or tuple(soft_targets.shape[:2]) != (logits.shape[0], logits.shape[1] - 1)
+            or not 0 < soft_targets.shape[2] <= logits.shape[2]):
+        raise ValueError(f"soft_target_cross_entropy: expected logits [B, S+1, V], labels [B, S+1] and soft_targets [B, S, K <= V]; got "
+                         f"{tuple(logits.shape)}, {tuple(labels.shape)} and {tuple(soft_targets.shape)}")
+    # "f16" compute mode: the gradient operand scale is bounded by the loss's row count (tape_ops.f16_grad_scale_for) - the same bound
+    # the engine records for its own cross entropy, set here for the model whose logits these are
+    model = getattr(logits.grad_fn, "model", None)
+    if model is not None and hasattr(model, "f16_grad_scale_for"):
+        model.__dict__["_loss_rows"] = logits.shape[0] * logits.shape[1]
+    return _SoftTargetCE.apply(logits, labels, soft_targets)
 
 
 def mask_or_random_replace_tokens(image_tokens, mask_id, config, mask_schedule=None, is_train=True, *, timesteps=None, noise=None,
@@ -901,18 +955,32 @@ class TrainStep:
     enqueued on a second HIP stream before this step's forward (the software analogue of the reference's dataloader workers
     running ahead of the loop; the token ids are bit-identical to encoding inline).  The convolution blocks and the
     transformer's GEMM / HBM-bound kernels then share the chip: each fills the CUs and memory cycles the other leaves idle
-    (tile seams, short grids).  The next call picks the tokens up when it is given the same tensor as `pixel_values`."""
+    (tile seams, short grids).  The next call picks the tokens up when it is given the same tensor as `pixel_values`.
+
+    `use_soft_code_target` / `soft_code_temp` / `use_stochastic_code` (config.training, :364-367, :421-424): the tokens and the soft
+    targets come from `vq_model.get_soft_code`, and the step is `logits = model(input_ids)`, `soft_target_cross_entropy(logits,
+    labels, soft_targets)`, backward, AdamW (class-conditional MaskGitTransformer only).  The prefetch then carries both."""
 
     def __init__(self, vq_model, model, optimizer, reducer: Optional[GradReducer] = None, label_smoothing: float = 0.0,
-                 min_masking_rate: float = 0.0):
+                 min_masking_rate: float = 0.0, use_soft_code_target: bool = False, soft_code_temp: float = 1.0,
+                 use_stochastic_code: bool = False):
         self.vq_model, self.model, self.optimizer, self.reducer = vq_model, model, optimizer, reducer
         self.label_smoothing, self.min_masking_rate = label_smoothing, min_masking_rate
-        self._pf = None          # (pixel tensor, tokens, ready event) of the prefetched batch
+        self.use_soft_code_target, self.soft_code_temp = bool(use_soft_code_target), float(soft_code_temp)
+        self.use_stochastic_code = bool(use_stochastic_code)
+        self._pf = None          # (pixel tensor, tokens or (soft targets, tokens), ready event) of the prefetched batch
         self._pf_stream = None
         self.compute_priority = -1   # stream priority of the step while a prefetch is in flight (None: stay on the caller's stream)
         self.optimizer_in_backward = os.environ.get("MUSE_OPT_IN_BACKWARD", "1") != "0"
         self.optimizer_in_reducer = os.environ.get("MUSE_OPT_IN_REDUCER", "1") != "0"
         self._hp_stream, self._in_hp = None, False
+
+    @torch.no_grad()
+    def _encode(self, pixel_values):
+        """tokens, or (soft targets, tokens) in the soft-target mode"""
+        if self.use_soft_code_target:
+            return self.vq_model.get_soft_code(pixel_values, temp=self.soft_code_temp, stochastic=self.use_stochastic_code)
+        return self.vq_model.get_code(pixel_values)
 
     @torch.no_grad()
     def _prefetch(self, pixel_values):
@@ -926,11 +994,11 @@ class TrainStep:
         side.wait_stream(main)                      # the images (and the previous use of the tokenizer's buffers) are ready
         with torch.cuda.stream(side), ops.conv_persistent(False):
             # (beside the step the launch-per-tile convolution: a persistent workgroup would hold its CU against the step's stream)
-            tokens = self.vq_model.get_code(pixel_values)
+            codes = self._encode(pixel_values)
             ev = torch.cuda.Event()
             ev.record(side)
         pixel_values.record_stream(side)
-        self._pf = (pixel_values, tokens, ev)
+        self._pf = (pixel_values, codes, ev)
 
     def __call__(self, pixel_values, class_ids, timesteps=None, noise=None, image_tokens=None, next_pixel_values=None):
         """image_tokens [B, S] int64: pre-encoded VQ tokens (muse.pre_encode; the reference's scripts/pre_encode.py regime) -
@@ -955,11 +1023,17 @@ class TrainStep:
             loss.record_stream(cur)
             mask_prob.record_stream(cur)
             return loss, mask_prob
+        if self.use_soft_code_target and image_tokens is not None:
+            raise ValueError("TrainStep: use_soft_code_target needs the images - pre-encoded image_tokens carry no soft codes")
+        soft = None
         if image_tokens is None and self._pf is not None and self._pf[0] is pixel_values:
-            _, image_tokens, ev = self._pf
+            _, codes, ev = self._pf
+            soft, image_tokens = codes if self.use_soft_code_target else (None, codes)
             main = torch.cuda.current_stream(image_tokens.device)
             main.wait_event(ev)
             image_tokens.record_stream(main)
+            if soft is not None:
+                soft.record_stream(main)
         elif self._pf is not None and image_tokens is None:
             # the prefetch is keyed by tensor IDENTITY: a different tensor object here means this batch is tokenised a second time
             warnings.warn("TrainStep: the prefetched batch is discarded - `pixel_values` is not the tensor object that was passed as "
@@ -967,13 +1041,22 @@ class TrainStep:
         self._pf = None
         if next_pixel_values is not None:
             if image_tokens is None:   # first step of a run: this batch inline, then the next one on the side stream
-                image_tokens = self.vq_model.get_code(pixel_values)
+                codes = self._encode(pixel_values)
+                soft, image_tokens = codes if self.use_soft_code_target else (None, codes)
             self._prefetch(next_pixel_values)
-        input_ids, labels, _, mask_prob = prepare_inputs_and_labels(
+        inline_soft = self.use_soft_code_target and image_tokens is None      # encode (soft codes and tokens) right here
+        input_ids, labels, soft_inline, mask_prob = prepare_inputs_and_labels(
             self.vq_model, pixel_values, class_ids, self.model.config.mask_token_id, self.min_masking_rate, timesteps, noise,
             image_tokens=image_tokens,
-            codebook_size=None if self.vq_model is not None else self.model.config.codebook_size)
-        _, loss = self.model(input_ids=input_ids, labels=labels, label_smoothing=self.label_smoothing)
+            codebook_size=None if self.vq_model is not None else self.model.config.codebook_size,
+            use_soft_code_target=inline_soft, soft_code_temp=self.soft_code_temp, use_stochastic_code=self.use_stochastic_code)
+        if soft_inline is not None:
+            soft = soft_inline
+        if self.use_soft_code_target:
+            logits = self.model(input_ids=input_ids)
+            loss = soft_target_cross_entropy(logits, labels, soft)
+        else:
+            _, loss = self.model(input_ids=input_ids, labels=labels, label_smoothing=self.label_smoothing)
         # AdamW inside backward (FusedAdamW.begin_step_in_backward): only when nothing sits between the two - no reducer here
         armed = (self.optimizer_in_backward and self.reducer is None and isinstance(self.optimizer, FusedAdamW)
                  and getattr(self.model, "wgrad_stream", False) and hasattr(self.model, "grad_ready_hook")
