@@ -167,10 +167,12 @@ int muse_attention_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo
  * (<= 2^-16 relative per product), softmax and accumulation in f32.  head_dim 64, seq_q = 256, seq_kv in 225..256 or 65..96
  * (self-attention of config 4's 16 x 16 grid; its 77 text states); anything else: MUSE_ERR_UNSUPPORTED (the caller keeps the
  * materialised route: muse_gemm batched + muse_softmax_*).  lse is f32 [batch*heads, 256]. */
-int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, void* stream);
+int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale, int32_t* stats,
+                          void* stream);
 int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
                           int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
-                          void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo, void* stream);
+                          void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo, int32_t half,
+                          float scale, int32_t* stats, void* stream);
 /* (dq / dk / dv may be NULL when their planes are given: a gradient that only weight GEMMs read exists as planes alone.)
  * (*_planes, optional: the result ALSO as the bf16 operand planes of the products that read it - muse_gemm_x3 - so that no split pass
  *  runs over it: the hi plane is addressed exactly like the f32 tensor (same strides, in elements), the lo plane sits *_lo elements
@@ -181,11 +183,12 @@ int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo
  * softmax - context and lse [seq_q/256][batch*heads][256] written once (o_planes as for muse_attention_x3_fwd).  _bwd_stream: dQ per
  * query block over the streamed key blocks (it also writes dO.O per query into dsum, a workspace shaped like lse), then dK / dV per
  * key block over the streamed query blocks; every gradient written once (f32 and / or operand images, as for muse_attention_x3_bwd). */
-int muse_attention_x3_fwd_stream(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, void* stream);
+int muse_attention_x3_fwd_stream(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale,
+                                 int32_t* stats, void* stream);
 int muse_attention_x3_bwd_stream(const muse_attn_desc* d, const float* d_o, int64_t lddo, int64_t bsdo, const float* lse, float* dsum,
                                  float* dq, int64_t lddq, int64_t bsdq, float* dk, int64_t lddk, int64_t bsdk, float* dv, int64_t lddv,
                                  int64_t bsdv, void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
-                                 void* stream);
+                                 int32_t half, float scale, int32_t* stats, void* stream);
 /* Block-by-block form of the longer sequences (round 6; reference modeling_transformer_v2.py:757-792 at the 1024 tokens of BASELINE config 4):
  * muse_attention_x3_fwd / _bwd run per (256 query rows, <= 256 keys) block pair, these two put the pieces together.
  * _merge: part[j] [batch*seq, heads*64] f32 (j < nk <= 8, part_stride elements apart) = key block j's softmax times its values, lp[j]
@@ -193,7 +196,8 @@ int muse_attention_x3_bwd_stream(const muse_attn_desc* d, const float* d_o, int6
  *   lse [seq/256][batch*heads][256] and optionally out's (hi, lo) bf16 operand planes (out_planes, lo plane out_lo elements behind).
  * muse_sum_parts_strided: out[r, 0..cols) (row pitch ldo, += when accumulate) = sum over j < n of parts[j*part_stride + r*cols + c]. */
 int muse_attention_x3_merge(const float* part, int64_t part_stride, const float* lp, int64_t lp_stride, int32_t nk, float* out, float* lse,
-                            void* out_planes, int64_t out_lo, int32_t batch, int32_t seq, int32_t heads, void* stream);
+                            void* out_planes, int64_t out_lo, int32_t batch, int32_t seq, int32_t heads, int32_t half, float scale,
+                            int32_t* stats, void* stream);
 int muse_sum_parts_strided(const float* parts, int64_t part_stride, int32_t n, int64_t rows, int32_t cols, float* out, int64_t ldo,
                            int32_t accumulate, void* stream);
 /* packed self-attention: qkv [B*S, 3*H] (q | k | v, H = heads*head_dim: the fused QKV projection), ctx [B*S, H], dqkv [B*S, 3*H] */
@@ -208,8 +212,10 @@ int muse_glu_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64
 /* The f32 GLU of the "bf16x3" compute mode: the same f32 results, written ALSO as the (hi, lo) bf16 operand planes muse_gemm_x3 reads
  * (planes = [2][rows][cols] bf16, hi plane first; the bits muse_split_f32_to_bf16x2 would produce from the f32 result).  h / dab may be
  * NULL: planes only (a result that nothing but weight GEMMs reads - the GLU output and its input gradient inside an MLP). */
-int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, void* stream);
-int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, void* stream);
+int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, int32_t half, float scale, int32_t* stats,
+                    void* stream);
+int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, int32_t half, float scale,
+                    int32_t* stats, void* stream);
 /* Fused middle of the NormFormer GLU MLP (muse/modeling_transformer.py:789-797), one pass over ab = [rows, 2*inter]:
  *   fwd: h = gelu_erf(a) * b, hm = LayerNorm(h) * w (mean/rstd saved);
  *   bwd: dh = LN'(dhm) never leaves the CU, dab = (dh*b*gelu'(a), dh*gelu(a)); dw_partial [ceil(rows/R), inter] f32 with
@@ -266,7 +272,7 @@ int muse_soft_ce_bwd(const float* logits, const int64_t* labels, const float* so
 /* AdamW over one flat f32 buffer (torch.optim.AdamW / apex FusedAdam(adam_w_mode) semantics,
  * training/train_maskgit_imagenet.py:242-261,438); optionally refreshes the bf16 compute copy of the weights. */
 int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                    float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void* stream);
+                    float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream);
 /* Exponential moving average of the weights, every tracked tensor in ONE launch (EMAModel.step, reference muse/modeling_ema.py:118-137,
  * called behind the optimizer step at training/train_muse.py:779-780): shadow = shadow - one_minus_decay * (shadow - param), the three
  * f32 roundings of the reference's tensor expression kept.  `table` (device): 4 x int64 per tensor {shadow, param, n, mode}, mode 0 =
@@ -278,7 +284,8 @@ int muse_ema_multi(const int64_t* table, const int32_t* chunk_first, int32_t num
  * 6 x int64 per tensor {p, g, m, v, p_bf16 or 0, n}; `chunk_first` (device, num_tensors + 1 x int32): exclusive prefix sum of
  * ceil(n / 4096); num_chunks = chunk_first[num_tensors]. */
 int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
-                     float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void* stream);
+                     float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip,
+                     void* stream);
 /* AdamW with PARAMETER GROUPS (training/train_muse.py:425-445 builds two: weight decay on the matrices, none on bias / LayerNorm /
  * embedding weights; torch.optim semantics - each group its own lr / betas / eps / weight_decay).  `group_hyper` (HOST memory, read
  * during the call): ngroups <= 8 rows of {lr, beta1, beta2, eps, weight_decay}.
@@ -288,12 +295,15 @@ int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t n
  * _multi_groups: muse_adamw_multi's table with a seventh column, the tensor's group in its low 8 bits; above them (optional, round 6) the
  *   element distance from p_bf16 to a second bf16 plane: p_bf16 then receives hi = bf16(p) and that plane lo = bf16(p - hi), the
  *   bf16x3 operand planes of the updated weight (muse_gemm_x3 reads them next step; 0 = plain bf16 copy).
- * A one-group call is bit-identical to muse_adamw_flat / muse_adamw_multi. */
+ * A one-group call is bit-identical to muse_adamw_flat / muse_adamw_multi.
+ * skip (every AdamW entry point; the overflow guard of the "f16" mode): NULL = unguarded; else a device int32 (the overflow counter the
+ * producer entry points and muse_cast_f32_to_f16 increment) read by the kernel, which leaves parameters and moments untouched when it
+ * is non-zero - GradScaler's found_inf without a host round trip. */
 int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
                            const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
-                           int32_t ngroups, int32_t step, float grad_scale, void* stream);
+                           int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream);
 int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                            const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, void* stream);
+                            const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream);
 /* out[i] (+)= sum over s < nslices of ws[s*stride + i]: reduction of split-K partial results (n, stride % 4 == 0) */
 int muse_sum_slices(const float* ws, float* out, int32_t nslices, int64_t n, int64_t stride, int32_t accumulate, void* stream);
 /* njobs <= 16 reductions in ONE launch, each bit-identical to the single-job kernel it stands for: kind 0 = muse_sum_slices
@@ -320,19 +330,15 @@ int muse_cast_f32_to_bf16(const float* in, void* out, int64_t n, void* stream);
  * ELEMENTS whose half is inf or NaN (an inf / NaN input and an f32-overflowing in * scale included), [1] the number of finite non-zero
  * inputs whose half is +-0. */
 int muse_cast_f32_to_f16(const float* in, void* out, int64_t n, float scale, int32_t* stats, void* stream);
-/* What the producer entry points below that write operand images next to (or instead of) their f32 result - muse_glu_fwd_x3 / _bwd_x3,
- * muse_norm_adaln_fwd_x3 / _bwd_x3, muse_attention_x3_fwd / _bwd / _merge - write as that image.  half = 0 (default): the (hi, lo) bf16
- * planes of the "bf16x3" mode, as documented with each.  half = 1 ("f16" mode): ONE IEEE-half image [rows][cols] at the plane pointer =
- * half(result * s), the bits muse_cast_f32_to_f16 makes of the f32 result, with s = 1 for forward results and s = grad_scale (a power
- * of two) for the gradients the backward entry points produce; lo-plane distances are ignored; muse_attention_x3_fwd / _bwd also COMPUTE in
- * that format (one half plane per operand, one half MFMA per K step; dO and dS times grad_scale, results divided by it); stats (device int32[2] or NULL): [0] is
- * incremented per 4-element group that holds an inf / NaN half (muse_cast_f32_to_f16's overflow counter: a dynamic gradient scale backs
- * off on it).  Process state (host code sets it around a pass: muse/ops.py f32_gemms_as_f16), not thread safe. */
-int muse_operand_images(int32_t half, float grad_scale, int32_t* stats);
-/* Overflow guard of the "f16" mode for the optimizer kernels (muse_adamw_flat, muse_adamw_flat_groups, muse_adamw_multi,
- * muse_adamw_multi_groups): while flag is non-NULL those kernels read *flag (device int32: the overflow counter muse_operand_images / muse_cast_f32_to_f16 increment) and leave
- * parameters and moments untouched when it is non-zero - GradScaler's found_inf without a host round trip.  Process state; NULL = off. */
-int muse_adamw_skip_flag(const int32_t* flag);
+/* (half, scale, stats): the last three arguments before `stream` of the producer entry points that write operand images next to (or
+ * instead of) their f32 result - muse_glu_fwd_x3 / _bwd_x3, muse_norm_adaln_fwd_x3 / _bwd_x3, muse_attention_x3_fwd / _bwd / _fwd_stream /
+ * _bwd_stream / _merge - say what that image is.  half = 0: the (hi, lo) bf16 planes of the "bf16x3" mode, as documented with each.
+ * half = 1 ("f16" mode): ONE IEEE-half image [rows][cols] at the plane pointer = half(result * scale), the bits muse_cast_f32_to_f16 makes
+ * of the f32 result; the caller passes scale = 1 for forward results and the pass's gradient scale for the gradients the backward entry
+ * points produce (a power of two either way, else MUSE_ERR_BAD_ARG); lo-plane distances are ignored; the muse_attention_x3_* entry points
+ * also COMPUTE in that format, planes or not (one half plane per operand, one half MFMA per K step; dO and dS times scale, results divided
+ * by it); stats (device int32[2], NULL unless half): [0] is incremented per 4-element group that holds an inf / NaN half
+ * (muse_cast_f32_to_f16's overflow counter: a dynamic gradient scale backs off on it). */
 int muse_cast_bf16_to_f32(const void* in, float* out, int64_t n, void* stream);
 
 /* prepare_inputs_and_labels (training/train_maskgit_imagenet.py:371-394) given the two uniform draws.
@@ -431,13 +437,12 @@ int muse_groupnorm_nchunk(int32_t HW);
  * by muse_conv2d_nhwc_split2, without the write and re-read of the two planes.  Shapes: muse_conv2d_nhwc_gn_split2_ok (3x3, H and W
  * multiples of 16, Cin a multiple of 64); others return MUSE_ERR_UNSUPPORTED.  bias / residual / gn_partial as for _split2. */
 int muse_conv2d_nhwc_gn_split2_ok(int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS);
-/* muse_conv2d_nhwc_gn_split2's persistent form (one workgroup per CU walks the tiles; bit-identical; 6-8 % faster when the convolution has
- * the chip to itself, slower for a step that shares the chip with it): mode 1 on (default unless MUSE_CONV_PERSIST=0), 0 off, -1 query;
- * returns the mode in force.  A host-side switch read at launch time (round 6). */
-int muse_conv_persistent(int32_t mode);
+/* persistent = 1: the persistent form may run (one workgroup per CU walks the tiles; bit-identical; 6-8 % faster when the convolution
+ * has the chip to itself, slower for a step that shares the chip with it); 0: the launch-per-tile kernel (round 6). */
 int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
                                const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
-                               int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, void* stream);
+                               int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
+                               void* stream);
 int muse_groupnorm_scale_shift(const double* partial, int32_t nchunk, const float* gamma, const float* beta, float* scale,
                                float* shift, int32_t batch, int32_t HW, int32_t C, int32_t groups, float eps, void* stream);
 /* Encoder.conv_in (muse/modeling_maskgit_vqgan.py:175; taming :380): 3x3, padding 1, Cin <= 4 image channels -> Cout, as a direct
@@ -544,10 +549,11 @@ int muse_norm_adaln_bwd(const float* dm, const float* dpre, const float* v, cons
 /* "bf16x3" mode forms: the f32 result AND its (hi, lo) bf16 operand planes [2][rows][cols] (what muse_split_f32_to_bf16x2 makes of it),
  * so that the products reading m / dv (muse_gemm_x3) need no split pass */
 int muse_norm_adaln_fwd_x3(const float* x, const float* res, const float* w, const float* ss, float* pre, float* m, void* planes,
-                           int32_t batch, int64_t rows_per_batch, int32_t cols, float eps, int32_t mode, void* stream);
+                           int32_t batch, int64_t rows_per_batch, int32_t cols, float eps, int32_t mode, int32_t half, float scale,
+                           int32_t* stats, void* stream);
 int muse_norm_adaln_bwd_x3(const float* dm, const float* dpre, const float* v, const float* w, const float* ss, float* dv, void* planes,
                            float* dw_partial, float* dss_partial, int32_t batch, int64_t rows_per_batch, int32_t cols, float eps,
-                           int32_t mode, void* stream);
+                           int32_t mode, int32_t half, float scale, int32_t* stats, void* stream);
 int muse_colsum_segments(const float* part, float* out, int32_t nseg, int32_t seg_rows, int32_t cols, void* stream);
 int muse_adaln_bwd(const float* dy, const float* x, const float* ss, float* dx, float* dss, int32_t batch,
                    int64_t rows_per_batch, int32_t C, void* stream);

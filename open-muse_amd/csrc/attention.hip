@@ -711,7 +711,7 @@ static int fwd_launch_k(AttnParams P, int chunk_rows, int nchunk, int ntile, int
   size_t lds = 2 * (size_t)MAXT * 16 * C::RS;
   if (shared) lds = max_sz(lds, (size_t)NW * 16 * (HD + 2) * 4);
   auto k = attn_fwd_kernel<HD, MAXT, NW, FULL>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_max_dynamic_lds((const void*)k, lds);
   hipLaunchKernelGGL(k, dim3(batch * P.nh * nchunk), dim3(NW * 64), lds, st, P);
   return (int)hipGetLastError();
 }
@@ -744,14 +744,14 @@ static int attn_fwd_launch(const AttnParams& P, int batch, hipStream_t st) {
 template <int HD, int NW>
 static int bwd_launch_dq(const AttnParams& P, const Plan& pl, int items, hipStream_t st) {
   auto k = attn_bwd_dq_kernel<HD, NW>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  set_max_dynamic_lds((const void*)k, pl.lds);
   hipLaunchKernelGGL(k, dim3(items), dim3(NW * 64), pl.lds, st, P);
   return (int)hipGetLastError();
 }
 template <int HD, int NW>
 static int bwd_launch_dkv(const AttnParams& P, const Plan& pl, int items, hipStream_t st) {
   auto k = attn_bwd_dkv_kernel<HD, NW>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  set_max_dynamic_lds((const void*)k, pl.lds);
   hipLaunchKernelGGL(k, dim3(items), dim3(NW * 64), pl.lds, st, P);
   return (int)hipGetLastError();
 }

@@ -447,13 +447,8 @@ static bool enabled() {
   return !(e && e[0] == '0');
 }
 static int num_cus() {
-  static int v = []() {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
-    return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }();
-  return v;
+  const int v = device_cus();
+  return v > 0 ? v : 256;
 }
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 static bool shape_ok(const AttnParams& P, int head_dim) {
@@ -472,7 +467,7 @@ int attn2_fwd_try(const AttnParams& P, int head_dim, int batch, hipStream_t st) 
   constexpr int HD = 48;
   const size_t lds = 2 * (size_t)Cfg<HD>::IMG + NW * MAXSH * FWD_PW * 4;
   auto launch = [&](auto k) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_max_dynamic_lds((const void*)k, lds);
     hipLaunchKernelGGL(k, dim3(batch * P.nh), dim3(NW * 64), lds, st, P, num_cus(), env_int("MUSE_ATTN2_STAGGER_FWD", 6000));
   };
   if (P.sq > 256) launch(fwd_kernel<HD, true>);
@@ -488,7 +483,7 @@ int attn2_bwd_try(const AttnParams& P, int head_dim, int batch, hipStream_t st) 
   constexpr int NWB = ATT2_BWD_NW;
   const size_t lds = 2 * (size_t)Cfg<HD>::IMG + 2 * Cfg<HD>::ROWS * 4 + NWB * MAXSH * BWD_PW * 4;
   auto launch = [&](auto k) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_max_dynamic_lds((const void*)k, lds);
     hipLaunchKernelGGL(k, dim3(batch * P.nh), dim3(NWB * 64), lds, st, P, num_cus(), env_int("MUSE_ATTN2_STAGGER_BWD", 0));
   };
   if (P.sq > 256) launch(bwd_kernel<HD, true, NWB>);

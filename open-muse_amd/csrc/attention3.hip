@@ -20,7 +20,7 @@
 //   * a block product is three MFMAs per K step (lo*hi, hi*lo, hi*hi: small terms first); P and dS are split in registers;
 //   * four planes of 256 rows are 147 KB: ONE 8-wave workgroup per CU and head, each wave owns one 32-query block (forward,
 //     backward phase 1) / one 32-key block (backward phase 2).
-// H16 (round 6, the "f16" compute mode: muse_operand_images(1, ..)): the same kernels with ONE IEEE-half plane per operand and one
+// H16 (round 6, the "f16" compute mode: half = 1): the same kernels with ONE IEEE-half plane per operand and one
 // v_mfma_f32_32x32x16_f16 per K step - half's 10-bit mantissa is the TF32 operand format, like the mode's GEMMs.  Two planes are 74 KB:
 // two workgroups share a CU and overlap each other's phases.  Gradient operands (dO, dS) are converted times the pass's power-of-two
 // gradient scale S and the results handed back divided by it: dO S, -dsum S -> S (dP - dsum) -> S dS -> S dQ, S dK; P^T (dO S) = S dV.
@@ -47,7 +47,7 @@ struct Params {
   float alpha;
   // optional: the same results ALSO as (hi, lo) bf16 operand planes for the products that read them (muse_gemm_x3): hi plane pointers
   // addressed like the f32 tensors (same strides, in elements), the lo plane lo_* elements behind
-  // ("f16" compute mode, img_format(): lo_* = -1 and the pointers receive ONE IEEE-half image half(x * img_scale) instead)
+  // ("f16" compute mode, half = 1: lo_* = -1 and the pointers receive ONE IEEE-half image half(x * img_scale) instead)
   bf16_t *outp, *dqp, *dkp, *dvp;
   long lo_out, lo_dq, lo_dk, lo_dv;
   float img_scale;
@@ -550,7 +550,7 @@ static Params base(const muse_attn_desc* d) {
 }
 template <typename K>
 static int launch(K k, const Params& P, int heads_total, size_t lds, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_max_dynamic_lds((const void*)k, lds);
   hipLaunchKernelGGL(k, dim3(heads_total), dim3(NT), lds, st, P);
   MUSE_CHECK_LAUNCH();
   return 0;
@@ -558,7 +558,7 @@ static int launch(K k, const Params& P, int heads_total, size_t lds, hipStream_t
 
 template <typename K>
 static int launch2(K k, const Params& P, int heads_total, int ny, size_t lds, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_max_dynamic_lds((const void*)k, lds);
   hipLaunchKernelGGL(k, dim3(heads_total, ny), dim3(NT), lds, st, P);
   MUSE_CHECK_LAUNCH();
   return 0;
@@ -575,15 +575,17 @@ static int check_stream(const muse_attn_desc* d) {
 
 }  // namespace attn3
 
-extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, void* stream) {
+extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale, int32_t* stats,
+                                     void* stream) {
   using namespace attn3;
   const int rc = check(d);
   if (rc) return rc;
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (o_planes && ((((uintptr_t)o_planes) & 7) || (o_lo & 3) || o_lo <= 0)) return MUSE_ERR_ALIGN;
   if (d->batch <= 0) return 0;
   Params P = base(d);
   P.out = (float*)d->o; P.lse = lse;
-  const ImgFormat f = img_format(false);
   P.outp = (bf16_t*)o_planes; P.lo_out = f.lo_sign < 0 ? -1 : o_lo; P.img_scale = f.scale; P.img_stats = f.stats;
   const int nkb = nkb_of(d->seq_kv);
   if (f.lo_sign < 0) {      // the "f16" compute mode is on: the core's products are single half products like the mode's GEMMs
@@ -599,8 +601,10 @@ extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* 
 extern "C" int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
                                      int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
                                      void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
-                                     void* stream) {
+                                     int32_t half, float scale, int32_t* stats, void* stream) {
   using namespace attn3;
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (((((uintptr_t)dq_planes) | ((uintptr_t)dk_planes) | ((uintptr_t)dv_planes)) & 7) || ((dq_lo | dk_lo | dv_lo) & 3)) return MUSE_ERR_ALIGN;
   const int rc = check(d);
   if (rc) return rc;
@@ -614,7 +618,6 @@ extern "C" int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, i
   P.dq = (float*)dq; P.lddq = lddq; P.bdq = bsdq;
   P.dk = (float*)dk; P.lddk = lddk; P.bdk = bsdk;
   P.dv = (float*)dv; P.lddv = lddv; P.bdv = bsdv;
-  const ImgFormat f = img_format(true);
   P.dqp = (bf16_t*)dq_planes; P.dkp = (bf16_t*)dk_planes; P.dvp = (bf16_t*)dv_planes; P.img_scale = f.scale; P.img_stats = f.stats;
   P.lo_dq = f.lo_sign < 0 ? -1 : dq_lo; P.lo_dk = f.lo_sign < 0 ? -1 : dk_lo; P.lo_dv = f.lo_sign < 0 ? -1 : dv_lo;
   P.gscale = f.lo_sign < 0 ? f.scale : 1.f;
@@ -630,15 +633,17 @@ extern "C" int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, i
 
 // ---- streaming forms: whole multiples of 256 queries AND keys (self-attention of the longer sequences) ---------------------------------------------
 // d describes the FULL sequences (seq_q, seq_kv multiples of 256; batch strides of the whole tensors).  lse [seq_q / 256][batch * heads][256].
-extern "C" int muse_attention_x3_fwd_stream(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, void* stream) {
+extern "C" int muse_attention_x3_fwd_stream(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale,
+                                            int32_t* stats, void* stream) {
   using namespace attn3;
   const int rc = check_stream(d);
   if (rc) return rc;
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (o_planes && ((((uintptr_t)o_planes) & 7) || (o_lo & 3) || o_lo <= 0)) return MUSE_ERR_ALIGN;
   if (d->batch <= 0) return 0;
   Params P = base(d);
   P.out = (float*)d->o; P.lse = lse;
-  const ImgFormat f = img_format(false);
   P.outp = (bf16_t*)o_planes; P.lo_out = f.lo_sign < 0 ? -1 : o_lo; P.img_scale = f.scale; P.img_stats = f.stats;
   P.nqb = d->seq_q / SQ; P.nkj = d->seq_kv / SQ;
   if (f.lo_sign < 0) return launch2(fwd_stream_kernel<true>, P, d->batch * d->heads, P.nqb, 2 * (size_t)PLANE, (hipStream_t)stream);
@@ -649,8 +654,10 @@ extern "C" int muse_attention_x3_fwd_stream(const muse_attn_desc* d, float* lse,
 extern "C" int muse_attention_x3_bwd_stream(const muse_attn_desc* d, const float* d_o, int64_t lddo, int64_t bsdo, const float* lse, float* dsum,
                                             float* dq, int64_t lddq, int64_t bsdq, float* dk, int64_t lddk, int64_t bsdk, float* dv, int64_t lddv,
                                             int64_t bsdv, void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
-                                            void* stream) {
+                                            int32_t half, float scale, int32_t* stats, void* stream) {
   using namespace attn3;
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (((((uintptr_t)dq_planes) | ((uintptr_t)dk_planes) | ((uintptr_t)dv_planes)) & 7) || ((dq_lo | dk_lo | dv_lo) & 3)) return MUSE_ERR_ALIGN;
   const int rc = check_stream(d);
   if (rc) return rc;
@@ -664,7 +671,6 @@ extern "C" int muse_attention_x3_bwd_stream(const muse_attn_desc* d, const float
   P.dq = dq; P.lddq = lddq; P.bdq = bsdq;
   P.dk = dk; P.lddk = lddk; P.bdk = bsdk;
   P.dv = dv; P.lddv = lddv; P.bdv = bsdv;
-  const ImgFormat f = img_format(true);
   P.dqp = (bf16_t*)dq_planes; P.dkp = (bf16_t*)dk_planes; P.dvp = (bf16_t*)dv_planes; P.img_scale = f.scale; P.img_stats = f.stats;
   P.lo_dq = f.lo_sign < 0 ? -1 : dq_lo; P.lo_dk = f.lo_sign < 0 ? -1 : dk_lo; P.lo_dv = f.lo_sign < 0 ? -1 : dv_lo;
   P.gscale = f.lo_sign < 0 ? f.scale : 1.f;
@@ -737,13 +743,15 @@ __global__ __launch_bounds__(256) void sum_parts_kernel(SumParams P) {
 }  // namespace attn3m
 
 extern "C" int muse_attention_x3_merge(const float* part, int64_t part_stride, const float* lp, int64_t lp_stride, int32_t nk, float* out, float* lse,
-                                       void* out_planes, int64_t out_lo, int32_t batch, int32_t seq, int32_t heads, void* stream) {
+                                       void* out_planes, int64_t out_lo, int32_t batch, int32_t seq, int32_t heads, int32_t half, float scale,
+                                       int32_t* stats, void* stream) {
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (nk < 1 || nk > attn3m::MAXB || batch <= 0 || seq <= 0 || (seq & 255) || heads <= 0) return nk < 1 || nk > attn3m::MAXB || (seq & 255) ? MUSE_ERR_UNSUPPORTED : 0;
   if ((((uintptr_t)part) | ((uintptr_t)out)) & 15 || (part_stride & 3) || (out_planes && ((((uintptr_t)out_planes) & 7) || (out_lo & 3) || out_lo <= 0)))
     return MUSE_ERR_ALIGN;
   attn3m::MergeParams P;
   P.part = part; P.lp = lp; P.out = out; P.lse = lse; P.planes = (bf16_t*)out_planes;
-  const ImgFormat f = img_format(false);
   P.part_stride = part_stride; P.lp_stride = lp_stride; P.lo = f.lo_sign < 0 ? -1 : out_lo; P.img_scale = f.scale; P.img_stats = f.stats; P.nk = nk; P.B = batch; P.S = seq; P.nh = heads;
   const long rows = (long)batch * seq;
   hipLaunchKernelGGL(attn3m::merge_kernel, dim3((unsigned)(rows < 65536 ? rows : 65536)), dim3(256), 0, (hipStream_t)stream, P);

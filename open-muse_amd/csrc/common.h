@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <map>
+#include <mutex>
+#include <utility>
 
 typedef unsigned short bf16_t;  // raw bfloat16 storage
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -51,9 +54,15 @@ __device__ __forceinline__ void split4_values(float x0, float x1, float x2, floa
 //   lo_off < 0   "f16" mode: ONE IEEE-half image, half(x * scale) with scale a power of two (1 for forward results, the backward pass's
 //                gradient scale for gradients) - the bits muse_cast_f32_to_f16 makes of the f32 result; an overflow becomes inf (the
 //                product turns NaN: loud) and is counted in *stats (the host's dynamic gradient scale backs off on it)
-// Which of the two the *_x3 entry points write is process state set by muse_operand_images (rowops.hip); launchers ask img_format().
+// Which of the two the *_x3 entry points write is their (half, scale, stats) arguments; launchers build the ImgFormat with image_format().
 struct ImgFormat { long lo_sign; float scale; int* stats; };      // lo_sign: -1 = half image, +1 = bf16 planes
-ImgFormat img_format(bool gradient);
+// false on a bad argument: half not 0 / 1, or scale no positive power of two.  stats is read only when half.
+inline bool image_format(int32_t half, float scale, int32_t* stats, ImgFormat* f) {
+  int e = 0;
+  if ((half != 0 && half != 1) || !(scale > 0.f) || frexpf(scale, &e) != 0.5f) return false;
+  *f = ImgFormat{half ? -1L : 1L, half ? scale : 1.f, half ? (int*)stats : nullptr};
+  return true;
+}
 __device__ __forceinline__ void store_image4(bf16_t* p, long lo_off, float scale, int* stats, float x0, float x1, float x2, float x3) {
   if (lo_off < 0) {
     asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
@@ -134,3 +143,29 @@ template <bool FAST> __device__ __forceinline__ float gelu_erf_grad_t(float x) {
 }
 
 #define MUSE_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// ---- per-device launch state (host) ------------------------------------------------------------------------------------------------
+// The dynamic-LDS limit is an attribute of a kernel ON A DEVICE and the CU count a property of the device: both are kept per device, so a
+// process that drives several GPUs launches every kernel with its attribute and sizes grids for the device it launches on.  Thread safe.
+inline std::mutex& launch_state_mutex() { static std::mutex m; return m; }
+// the current device's CU count (0 when it cannot be queried)
+inline int device_cus() {
+  static std::map<int, int> cus;
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  std::lock_guard<std::mutex> lk(launch_state_mutex());
+  auto it = cus.find(dev);
+  if (it != cus.end()) return it->second;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return cus[dev] = n;
+}
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) of `kernel` on the current device: once per (device, kernel), again only when a launch
+// asks for more than was set.  A failure stays the launch's error (hipGetLastError behind it).
+inline void set_max_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::map<std::pair<int, const void*>, size_t> done;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return;
+  std::lock_guard<std::mutex> lk(launch_state_mutex());
+  size_t& have = done[{dev, kernel}];
+  if (have < bytes && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) have = bytes;
+}

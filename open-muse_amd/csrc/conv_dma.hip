@@ -1143,33 +1143,21 @@ extern "C" int muse_conv2d_nhwc_split2(const void* in_hi, const void* in_lo, con
   }
   p.M = (int)M; p.N = Cout; p.K = 9 * Cin; p.H = H; p.W = W; p.Cin = Cin;
   const int ntm = (p.M + cdma::BM - 1) / cdma::BM, ntn = (p.N + cdma::BN - 1) / cdma::BN;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)cdma::conv_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cdma::LDS_BYTES);
-    attr_set = true;
-  }
   static const int use_slab = []() { const char* e = getenv("MUSE_CONV_SLAB"); return e ? atoi(e) : 1; }();
   if (use_slab && (H % 16) == 0 && (W % 16) == 0 && (Cin % 64) == 0) {   // patch-slab kernel (K order: chunk, tap, channel)
-    static bool slab_attr = false;
-    if (!slab_attr) {
-      (void)hipFuncSetAttribute((const void*)cslab::conv_slab_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cslab::LDS_BYTES);
-      slab_attr = true;
-    }
+    set_max_dynamic_lds((const void*)cslab::conv_slab_kernel<false>, cslab::LDS_BYTES);
     const int nslab = (p.M >> 8) * ntn;
     if (use_slab >= 2 && (long)p.M * p.N * 4 < (1L << 32) - 64) {   // persistent: one block per CU walks its tiles (32-bit output offsets)
-      static int ncu = 0;
-      if (!ncu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MUSE_ERR_UNSUPPORTED;
-        ncu = prop.multiProcessorCount;
-        (void)hipFuncSetAttribute((const void*)cslab::conv_slab_persist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cslab::P_LDS_BYTES);
-      }
+      const int ncu = device_cus();
+      if (!ncu) return MUSE_ERR_UNSUPPORTED;
+      set_max_dynamic_lds((const void*)cslab::conv_slab_persist_kernel<false>, cslab::P_LDS_BYTES);
       hipLaunchKernelGGL(cslab::conv_slab_persist_kernel<false>, dim3(nslab < ncu ? nslab : ncu), dim3(512), cslab::P_LDS_BYTES, (hipStream_t)stream, p);
       return (int)hipGetLastError();
     }
     hipLaunchKernelGGL(cslab::conv_slab_kernel<false>, dim3(nslab), dim3(512), cslab::LDS_BYTES, (hipStream_t)stream, p);
     return (int)hipGetLastError();
   }
+  set_max_dynamic_lds((const void*)cdma::conv_dma_kernel, cdma::LDS_BYTES);
   hipLaunchKernelGGL(cdma::conv_dma_kernel, dim3(ntm * ntn), dim3(512), cdma::LDS_BYTES, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }
@@ -1178,15 +1166,10 @@ extern "C" int muse_conv2d_nhwc_split2(const void* in_hi, const void* in_lo, con
 // gn_scale / gn_shift [batch][Cin] the per-image affine form of the normalisation (muse_groupnorm_scale_shift).  Same result, bit
 // for bit, as muse_groupnorm_silu_nhwc_split followed by muse_conv2d_nhwc_split2.  Patch-slab shapes only (H, W multiples of 16,
 // Cin a multiple of 64, Cin <= 2048); anything else returns MUSE_ERR_UNSUPPORTED and the caller keeps the two-kernel route.
-// Persistent form of the fused convolution on / off for the launches that follow on this host thread's behalf (mode 0 / 1; -1 = query).
-// Default: MUSE_CONV_PERSIST, else ON - the persistent kernel is 6-8 % faster whenever the convolution has the chip to itself (a tokenizer
-// or decoder pass on its own: BASELINE config 5, inline tokenizing, pre-encoding).  muse.TrainStep switches it OFF around the tokenizer
-// pass it enqueues BESIDE a train step: there a workgroup that holds its CU for a whole launch costs the step 2.2 ms (profiles/r06_ceiling.md).
-extern "C" int muse_conv_persistent(int32_t mode) {
-  static int state = []() { const char* e = getenv("MUSE_CONV_PERSIST"); return e ? atoi(e) : 1; }();
-  if (mode >= 0) state = mode;
-  return state;
-}
+// `persistent` (0 / 1): the persistent form of the kernel may run.  The caller's choice (muse/ops.py conv_persistent): the persistent
+// kernel is 6-8 % faster whenever the convolution has the chip to itself (a tokenizer or decoder pass on its own: BASELINE config 5, inline
+// tokenizing, pre-encoding); muse.TrainStep switches it OFF around the tokenizer pass it enqueues BESIDE a train step: there a workgroup that
+// holds its CU for a whole launch costs the step 2.2 ms (profiles/r06_ceiling.md).
 extern "C" int muse_conv2d_nhwc_gn_split2_ok(int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS) {
   const long M = (long)batch * H * W;
   return KS == 3 && (H % 16) == 0 && (W % 16) == 0 && (Cin % 64) == 0 && Cin <= 2048 && (Cout % 4) == 0 && M > 0 &&
@@ -1194,7 +1177,8 @@ extern "C" int muse_conv2d_nhwc_gn_split2_ok(int32_t batch, int32_t H, int32_t W
 }
 extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
                                           const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
-                                          int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, void* stream) {
+                                          int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
+                                          void* stream) {
   const long M = (long)batch * H * W;
   if (M <= 0 || Cout <= 0) return 0;
   if (!muse_conv2d_nhwc_gn_split2_ok(batch, H, W, Cin, Cout, KS)) return MUSE_ERR_UNSUPPORTED;
@@ -1212,22 +1196,16 @@ extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale,
   const int ntn = (p.N + cslab::BN - 1) / cslab::BN;
   // persistent form (round 6): one workgroup per CU walks the tiles, the K loop's look-ahead runs on into the next tile.  Taken when a
   // CU gets at least MUSE_CONV_PERSIST_MIN tiles (default 2), Cin <= 256 (two scale / shift tables behind the LDS map) and the output
-  // stays below 4 GiB (32-bit store offsets).  MUSE_CONV_PERSIST=0 keeps the launch-per-tile kernel; MUSE_CONV_PERSIST_GRID sets the
-  // number of workgroups (default: one per CU).
-  const int persist = muse_conv_persistent(-1);
-  if (persist && Cin <= cslab::P_GSS_MAX_CIN && (long)p.M * p.N * 4 < (1L << 32) - 64) {
-    static int ncu = 0, grid = 0, min_tiles = 2, min_given = 0;
-    if (!ncu) {
-      int dev = 0; hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MUSE_ERR_UNSUPPORTED;
-      (void)hipFuncSetAttribute((const void*)cslab::conv_slab_persist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, cslab::P_LDS_BYTES_GN);
-      const char* e = getenv("MUSE_CONV_PERSIST_GRID");
-      grid = e ? atoi(e) : prop.multiProcessorCount;
-      if (grid < 1) grid = 1;
-      const char* m = getenv("MUSE_CONV_PERSIST_MIN");
-      if (m) { min_tiles = atoi(m); min_given = 1; }
-      ncu = prop.multiProcessorCount;
-    }
+  // stays below 4 GiB (32-bit store offsets).  persistent = 0 keeps the launch-per-tile kernel; MUSE_CONV_PERSIST_GRID sets the
+  // number of workgroups (default: one per CU of the device).
+  if (persistent && Cin <= cslab::P_GSS_MAX_CIN && (long)p.M * p.N * 4 < (1L << 32) - 64) {
+    static const int grid_env = []() { const char* e = getenv("MUSE_CONV_PERSIST_GRID"); return e ? (atoi(e) < 1 ? 1 : atoi(e)) : 0; }();
+    static const char* const min_env = getenv("MUSE_CONV_PERSIST_MIN");
+    static const int min_tiles = min_env ? atoi(min_env) : 2, min_given = min_env != nullptr;
+    const int ncu = device_cus();
+    if (!ncu) return MUSE_ERR_UNSUPPORTED;
+    const int grid = grid_env ? grid_env : ncu;
+    set_max_dynamic_lds((const void*)cslab::conv_slab_persist_kernel<true>, cslab::P_LDS_BYTES_GN);
     const int nslab = (p.M >> 8) * ntn;
     // MUSE_CONV_PERSIST_TILES=k: workgroups of k tiles each (grid = tiles / k) instead of one workgroup per CU for the whole launch - a CU
     // is handed back to the dispatcher (and to the other streams' kernels) every k tiles
@@ -1242,12 +1220,7 @@ extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale,
       return (int)hipGetLastError();
     }
   }
-  constexpr int lds = cslab::LDS_BYTES + 2 * 2048 * 4;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)cslab::conv_slab_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+  set_max_dynamic_lds((const void*)cslab::conv_slab_kernel<true>, cslab::LDS_BYTES + 2 * 2048 * 4);
   hipLaunchKernelGGL(cslab::conv_slab_kernel<true>, dim3((p.M >> 8) * ntn), dim3(512), cslab::LDS_BYTES + 2 * Cin * 4, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }

@@ -201,7 +201,7 @@ extern "C" int muse_conv2d_nhwc_split(const float* in, const void* w_hi, const v
   if (p.M <= 0 || p.N <= 0) return 0;
   const int ntm = (p.M + 127) / 128, ntn = (p.N + 127) / 128;
   const size_t lds = 4 * 128 * 160;
-  (void)hipFuncSetAttribute((const void*)conv_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_max_dynamic_lds((const void*)conv_split_kernel, lds);
   hipLaunchKernelGGL(conv_split_kernel, dim3(ntm * ntn), dim3(256), lds, (hipStream_t)stream, sp);
   return (int)hipGetLastError();
 }

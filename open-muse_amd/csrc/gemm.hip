@@ -157,11 +157,7 @@ extern "C" int muse_gemm_group(const muse_gemm_desc* d, int32_t n, int32_t split
   if (rc) return rc;
   const bool half_ops = d[0].dtype == MUSE_F16;
   auto kern = half_ops ? g256::kernel_group<float, 1, 1, true, true> : g256::kernel_group<float, 1, 1, true>;
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[half_ops]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, g256::LDS_BYTES);
-    attr_set[half_ops] = true;
-  }
+  set_max_dynamic_lds((const void*)kern, g256::LDS_BYTES);
   hipLaunchKernelGGL(kern, dim3(gp.tile_start[n], split_k, 1), dim3(512), g256::LDS_BYTES, (hipStream_t)stream, gp);
   return (int)hipGetLastError();
 }

@@ -905,11 +905,7 @@ static inline int launch_gemm256_lb(const GemmParams& p, int batch, hipStream_t 
   const int ntm = (p.M + 255) / 256, ntn = (p.N + 255) / 256;
   constexpr int lds = BKV == 64 ? g256::LDS_BYTES : g256::LDS_BYTES32;
   auto kern = g256::kernel<TC, AL, BL, BKV, SPREAD, H>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
+  set_max_dynamic_lds((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, p.split_k > 1 ? p.split_k : 1, batch), dim3(512), lds, stream, p);
   return (int)hipGetLastError();
 }
@@ -917,11 +913,7 @@ template <typename TC, int AL, int BL>
 static inline int launch_gemm256_x3_l(const GemmParams& p, hipStream_t stream) {
   const int ntm = (p.M + 255) / 256, ntn = (p.N + 255) / 256;
   auto kern = g256::kernel_x3<TC, AL, BL>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, g256::LDS_BYTES_X3);
-    attr_set = true;
-  }
+  set_max_dynamic_lds((const void*)kern, g256::LDS_BYTES_X3);
   hipLaunchKernelGGL(kern, dim3(ntm * ntn, p.split_k > 1 ? p.split_k : 1, 1), dim3(512), g256::LDS_BYTES_X3, stream, p);
   return (int)hipGetLastError();
 }

@@ -554,11 +554,7 @@ static inline int launch_gemm_st(const GemmParams& p, int batch, hipStream_t str
   constexpr size_t ctile = BM == 128 ? (size_t)(sizeof(TC) == 4 ? 64 : 128) * (128 * sizeof(TC) + 16) : 0;  // staged C rows
   constexpr size_t lds = tiles > ctile ? tiles : ctile;
   auto kern = gemm_kernel<T, TC, AL, BL, BM, NSTAGE, ALoader, BLoader>;
-  static bool attr_set = false;  // one flag per template instantiation
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  set_max_dynamic_lds((const void*)kern, lds);
   hipLaunchKernelGGL(kern, grid, dim3(BM * 2), lds, stream, p);
   return (int)hipGetLastError();
 }

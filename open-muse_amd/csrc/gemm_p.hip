@@ -18,7 +18,6 @@ struct Slots {
   int n = 0;
   int cus = 0;
   bool failed = false;
-  bool attr_set[5] = {false, false, false, false, false};
 };
 std::mutex g_mu;
 Slots g_slots[kMaxDev];
@@ -42,7 +41,7 @@ Slots* slots_of_current_device() {
   return &S;
 }
 
-unsigned* counters_for(hipStream_t s, int* cus, Slots** out) {
+unsigned* counters_for(hipStream_t s, int* cus) {
   std::lock_guard<std::mutex> lk(g_mu);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
@@ -50,7 +49,6 @@ unsigned* counters_for(hipStream_t s, int* cus, Slots** out) {
   Slots* S = slots_of_current_device();
   if (!S) return nullptr;
   *cus = S->cus;
-  *out = S;
   for (int i = 0; i < S->n; ++i)
     if (S->streams[i] == s) return S->base + i * 16;
   if (S->n == 64) return nullptr;
@@ -84,8 +82,7 @@ bool eligible(const GemmParams& p, int la, int lb, int batch) {
 template <typename TC, int AL, int BL, bool H = false>
 int launch(const GemmParams& p, hipStream_t stream) {
   int cus = 0;
-  Slots* S = nullptr;
-  unsigned* counters = counters_for(stream, &cus, &S);
+  unsigned* counters = counters_for(stream, &cus);
   if (!counters || cus < 8) {
     if (getenv("MUSE_G256P_DEBUG")) fprintf(stderr, "[g256p] no queue slot (counters %p, %d CUs)\n", (void*)counters, cus);
     return -1;
@@ -112,11 +109,7 @@ int launch(const GemmParams& p, hipStream_t stream) {
   a.staux = staux;
   a.stagger = stagger;
   auto kern = g256p::kernel<TC, AL, BL, H>;
-  constexpr int form = H ? 4 : (sizeof(TC) == 4 ? 2 : 0) + BL;      // the dynamic-LDS attribute is per function AND per device
-  if (!S->attr_set[form]) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, g256p::LDS_BYTES_P);
-    S->attr_set[form] = true;
-  }
+  set_max_dynamic_lds((const void*)kern, g256p::LDS_BYTES_P);
   hipLaunchKernelGGL(kern, dim3(8 * nbx), dim3(512), g256p::LDS_BYTES_P, stream, a);
   return (int)hipGetLastError();
 }

@@ -981,20 +981,6 @@ static inline int ew_grid(long n) { long g = (n + 255) / 256; return (int)(g > 4
 // products of its input projection) - the separate split pass (read 4 + write 4 bytes per element) becomes 4 written bytes here.
 // planes: [2][rows][cols] bf16, hi plane first; split4 is the split muse_split_f32_to_bf16x2 applies, so the planes are its bits.
 // (ImgFormat: the "f16" mode's half image instead - common.h store_image4)
-static int g_img_half = 0;
-static float g_img_grad_scale = 1.f;
-static int* g_img_stats = nullptr;
-ImgFormat img_format(bool gradient) {
-  return ImgFormat{g_img_half ? -1L : 1L, (g_img_half && gradient) ? g_img_grad_scale : 1.f, g_img_half ? g_img_stats : nullptr};
-}
-extern "C" int muse_operand_images(int32_t half, float grad_scale, int32_t* stats) {
-  int e = 0;
-  if ((half != 0 && half != 1) || !(grad_scale > 0.f) || frexpf(grad_scale, &e) != 0.5f) return MUSE_ERR_BAD_ARG;   // a power of two
-  g_img_half = half;
-  g_img_grad_scale = grad_scale;
-  g_img_stats = half ? (int*)stats : nullptr;
-  return 0;
-}
 __device__ __forceinline__ void store_planes4(bf16_t* hi, long plane, const ImgFormat& f, long idx, const float (&o)[4]) {
   store_image4(hi + idx, plane, f.scale, f.stats, o[0], o[1], o[2], o[3]);
 }
@@ -1032,22 +1018,24 @@ __global__ void glu_bwd_x3_kernel(const float* __restrict__ ab, const float* __r
     store_planes4(planes, plane, f, r * 2 * inter + inter + c, db);
   }
 }
-extern "C" int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, void* stream) {
-  if (inter % 4) return MUSE_ERR_BAD_ARG;
+extern "C" int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, int32_t half, float scale, int32_t* stats,
+                               void* stream) {
+  ImgFormat f;
+  if (inter % 4 || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (rows <= 0) return 0;
   if (!planes) return MUSE_ERR_BAD_ARG;
   if ((((uintptr_t)ab) | ((uintptr_t)h)) & 15 || (((uintptr_t)planes) & 7) || ((rows * inter) & 3)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL(glu_fwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, h, (bf16_t*)planes, (long)rows, inter,
-                     img_format(false));
+  hipLaunchKernelGGL(glu_fwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, h, (bf16_t*)planes, (long)rows, inter, f);
   return (int)hipGetLastError();
 }
-extern "C" int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, void* stream) {
-  if (inter % 4) return MUSE_ERR_BAD_ARG;
+extern "C" int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, int32_t half, float scale,
+                               int32_t* stats, void* stream) {
+  ImgFormat f;
+  if (inter % 4 || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   if (rows <= 0) return 0;
   if (!planes) return MUSE_ERR_BAD_ARG;
   if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL(glu_bwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, dh, dab, (bf16_t*)planes, (long)rows, inter,
-                     img_format(true));
+  hipLaunchKernelGGL(glu_bwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, dh, dab, (bf16_t*)planes, (long)rows, inter, f);
   return (int)hipGetLastError();
 }
 // bf16, inter % 8 == 0: eight columns of one row per thread (16-byte accesses), rows walked by blockIdx.y - no 64-bit index
@@ -1581,12 +1569,10 @@ extern "C" int muse_soft_ce_bwd(const float* logits, const int64_t* labels, cons
   return (int)hipGetLastError();
 }
 
-// Overflow guard of the "f16" compute mode (muse_adamw_skip_flag): when set, every AdamW kernel (flat, flat groups, multi-tensor) reads *skip first and leave every
-// tensor untouched if it is non-zero - the gradients of a backward pass whose operand images overflowed half's range are NaN, and the
-// update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host round trip).  Process state like
-// muse_operand_images; NULL (default) = no guard.
-static const int* g_adamw_skip = nullptr;
-extern "C" int muse_adamw_skip_flag(const int32_t* flag) { g_adamw_skip = (const int*)flag; return 0; }
+// Overflow guard of the "f16" compute mode (the `skip` argument of every AdamW entry point): when non-NULL, every AdamW kernel (flat, flat
+// groups, multi-tensor) reads *skip first and leaves every tensor untouched if it is non-zero - the gradients of a backward pass whose operand
+// images overflowed half's range are NaN, and the update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host
+// round trip).  NULL = no guard.
 // =================================================================================================================
 // AdamW over a flat f32 buffer; optional bf16 shadow refresh.  7 x 4 B per parameter of HBM traffic (+2 B shadow).
 // =================================================================================================================
@@ -1594,7 +1580,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
                                                     float b2, float eps, float decay, float omb1, float omb2,
                                                     float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard: muse_adamw_skip_flag)
+  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float pp[4], gg[4], mm[4], vv[4];
@@ -1624,7 +1610,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void* stream) {
+                               float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
   if (n <= 0) return 0;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
@@ -1634,7 +1620,7 @@ extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, voi
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
   const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                     (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, g_adamw_skip);
+                     (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
   return (int)hipGetLastError();
 }
 
@@ -1725,7 +1711,7 @@ extern "C" int muse_ema_multi(const int64_t* table, const int32_t* chunk_first, 
 }
 
 extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, void* stream) {
+                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
   if (num_tensors <= 0 || num_chunks <= 0) return 0;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
@@ -1734,7 +1720,7 @@ extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
   const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
   hipLaunchKernelGGL(adamw_multi_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first, num_tensors,
-                     beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, g_adamw_skip);
+                     beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
   return (int)hipGetLastError();
 }
 
@@ -1776,7 +1762,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
                                                            float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
                                                            const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
                                                            AdamGroups G, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard: muse_adamw_skip_flag)
+  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
   const long c0 = (long)blockIdx.x * 4096, c1 = c0 + 4096 < n ? c0 + 4096 : n;
   auto seg_of = [&](long pos) {   // smallest s with seg_end[s] > pos (positions beyond the last end: the last segment)
     int lo = 0, hi = nseg - 1;
@@ -1816,7 +1802,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
 }
 extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
                                       const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
-                                      int32_t ngroups, int32_t step, float grad_scale, void* stream) {
+                                      int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
   if (n <= 0) return 0;
   if (nseg < 1 || !seg_end || !seg_group) return MUSE_ERR_BAD_ARG;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
@@ -1825,14 +1811,14 @@ extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float*
   const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
   if (rc) return rc;
   hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, g_adamw_skip);
+                     (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, skip);
   return (int)hipGetLastError();
 }
 // Multi-tensor form with groups: `table` is 7 x int64 per tensor {p, g, m, v, p_bf16 or 0, n, group | lo_plane_distance << 8}
 // (lo_plane_distance < 0: p_bf16 receives an IEEE-half copy).
 __global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
                                                                  AdamGroups G, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard: muse_adamw_skip_flag)
+  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
   int lo = 0, hi = nt;
   while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
   const long* e = table + (long)lo * 7;
@@ -1884,13 +1870,14 @@ __global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __r
   }
 }
 extern "C" int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                                       const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, void* stream) {
+                                       const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip,
+                                       void* stream) {
   if (num_tensors <= 0 || num_chunks <= 0) return 0;
   AdamGroups G;
   const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
   if (rc) return rc;
   hipLaunchKernelGGL(adamw_multi_groups_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
-                     num_tensors, G, grad_scale, g_adamw_skip);
+                     num_tensors, G, grad_scale, skip);
   return (int)hipGetLastError();
 }
 

@@ -717,9 +717,10 @@ extern "C" int muse_norm_adaln_fwd(const float* x, const float* res, const float
 }
 // "bf16x3" mode: m as f32 AND as the (hi, lo) operand planes [2][rows][cols] of the products that read it
 extern "C" int muse_norm_adaln_fwd_x3(const float* x, const float* res, const float* w, const float* ss, float* pre, float* m, void* planes,
-                                      int32_t batch, int64_t rows_per_batch, int32_t cols, float eps, int32_t mode, void* stream) {
-  if (!planes) return MUSE_ERR_BAD_ARG;      // (m may be NULL: the planes only - a result that nothing but weight GEMMs reads)
-  const ImgFormat f = img_format(false);     // ("f16" mode: planes receives ONE half image [rows][cols] instead)
+                                      int32_t batch, int64_t rows_per_batch, int32_t cols, float eps, int32_t mode, int32_t half, float scale,
+                                      int32_t* stats, void* stream) {
+  ImgFormat f;                               // ("f16" mode: planes receives ONE half image [rows][cols] instead)
+  if (!planes || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;    // (m may be NULL: the planes only - a result that nothing but weight GEMMs reads)
   return norm_adaln_fwd_launch(x, res, w, ss, pre, m, planes, f.lo_sign * (long)batch * rows_per_batch * cols, f.scale, f.stats, batch, rows_per_batch, cols, eps,
                                mode, stream);
 }
@@ -854,9 +855,9 @@ extern "C" int muse_norm_adaln_bwd(const float* dm, const float* dpre, const flo
 // "bf16x3" mode: dv as f32 AND as the (hi, lo) operand planes [2][rows][cols] of the dX / dW products that read it
 extern "C" int muse_norm_adaln_bwd_x3(const float* dm, const float* dpre, const float* v, const float* w, const float* ss, float* dv,
                                       void* planes, float* dw_partial, float* dss_partial, int32_t batch, int64_t rows_per_batch,
-                                      int32_t cols, float eps, int32_t mode, void* stream) {
-  if (!planes) return MUSE_ERR_BAD_ARG;
-  const ImgFormat f = img_format(true);      // ("f16" mode: ONE half image of dv, scaled by the backward pass's gradient scale)
+                                      int32_t cols, float eps, int32_t mode, int32_t half, float scale, int32_t* stats, void* stream) {
+  ImgFormat f;                               // ("f16" mode: ONE half image of dv, scaled by the backward pass's gradient scale)
+  if (!planes || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
   return norm_adaln_bwd_launch(dm, dpre, v, w, ss, dv, planes, f.lo_sign * (long)batch * rows_per_batch * cols, f.scale, f.stats, dw_partial, dss_partial, batch, rows_per_batch,
                                cols, eps, mode, stream);
 }

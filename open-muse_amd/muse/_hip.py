@@ -41,6 +41,9 @@ class AttnDesc(C.Structure):
     ]
 
 
+# (half, scale, stats): the operand-image format the producer entry points (*_x3) write - ops._image_args
+_IMG = (c_int, c_float, c_void_p)
+
 # name -> argtypes (every function returns int unless listed in _RESTYPES)
 SIGNATURES = {
     "muse_version": [],
@@ -66,21 +69,22 @@ SIGNATURES = {
     "muse_attention_fwd_ex": [C.POINTER(AttnDesc), c_void_p, c_void_p],
     "muse_attention_bwd_ex": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                               c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p],
-    "muse_attention_x3_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, c_void_p],
+    "muse_attention_x3_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_bwd": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
-                              c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p],
-    "muse_attention_x3_fwd_stream": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, c_void_p],
+                              c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, *_IMG, c_void_p],
+    "muse_attention_x3_fwd_stream": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_bwd_stream": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
-                                     c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p],
-    "muse_attention_x3_merge": [c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p],
+                                     c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, *_IMG, c_void_p],
+    "muse_attention_x3_merge": [c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, *_IMG,
+                                c_void_p],
     "muse_sum_parts_strided": [c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p],
     "muse_attention_fwd": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "muse_attention_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                            c_void_p],
     "muse_glu_fwd": [c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_glu_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
-    "muse_glu_fwd_x3": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
-    "muse_glu_bwd_x3": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p],
+    "muse_glu_fwd_x3": [c_void_p, c_void_p, c_void_p, c_i64, c_int, *_IMG, c_void_p],
+    "muse_glu_bwd_x3": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, *_IMG, c_void_p],
     "muse_ffn_mid_rows_per_block": [],
     "muse_ffn_mid_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
     "muse_ffn_mid_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -101,12 +105,13 @@ SIGNATURES = {
     "muse_soft_ce_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int,
                          c_i64, c_i64, c_void_p],
     "muse_adamw_flat": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float,
-                        c_float, c_int, c_float, c_void_p],
-    "muse_adamw_multi": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p],
+                        c_float, c_int, c_float, c_void_p, c_void_p],
+    "muse_adamw_multi": [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p,
+                         c_void_p],
     "muse_ema_multi": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p],
     "muse_adamw_flat_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p,
-                               c_int, c_int, c_float, c_void_p],
-    "muse_adamw_multi_groups": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p],
+                               c_int, c_int, c_float, c_void_p, c_void_p],
+    "muse_adamw_multi_groups": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p],
     "muse_gemm_group_ok": [c_void_p, c_int, c_int],
     "muse_gemm_group": [c_void_p, c_int, c_int, c_void_p],
     "muse_sum_multi": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
@@ -120,8 +125,6 @@ SIGNATURES = {
     "muse_cast_f32_to_bf16": [c_void_p, c_void_p, c_i64, c_void_p],
     "muse_cast_bf16_to_f32": [c_void_p, c_void_p, c_i64, c_void_p],
     "muse_cast_f32_to_f16": [c_void_p, c_void_p, c_i64, c_float, c_void_p, c_void_p],
-    "muse_operand_images": [c_int, c_float, c_void_p],
-    "muse_adamw_skip_flag": [c_void_p],
     "muse_mask_sample": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64,
                          c_i64, c_float, c_void_p],
     "muse_sample_step": [c_void_p, c_void_p, c_float, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p, C.c_uint64, C.c_uint32,
@@ -138,8 +141,7 @@ SIGNATURES = {
                                 c_int, c_int, c_int, c_int, c_void_p],
     "muse_conv_in_direct": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "muse_conv2d_nhwc_gn_split2_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
-    "muse_conv_persistent": [c_int],
-    "muse_conv2d_nhwc_gn_split2": [c_void_p] * 9 + [c_int] * 7 + [c_void_p],
+    "muse_conv2d_nhwc_gn_split2": [c_void_p] * 9 + [c_int] * 8 + [c_void_p],
     "muse_groupnorm_scale_shift": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "muse_groupnorm_silu_nhwc_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                        c_int, c_float, c_int, c_void_p],
@@ -169,8 +171,8 @@ SIGNATURES = {
     "muse_adaln_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_norm_adaln_fwd": [c_void_p] * 7 + [c_int, c_i64, c_int, c_float, c_int, c_void_p],
     "muse_norm_adaln_bwd": [c_void_p] * 9 + [c_int, c_i64, c_int, c_float, c_int, c_void_p],
-    "muse_norm_adaln_fwd_x3": [c_void_p] * 7 + [c_int, c_i64, c_int, c_float, c_int, c_void_p],
-    "muse_norm_adaln_bwd_x3": [c_void_p] * 9 + [c_int, c_i64, c_int, c_float, c_int, c_void_p],
+    "muse_norm_adaln_fwd_x3": [c_void_p] * 7 + [c_int, c_i64, c_int, c_float, c_int, *_IMG, c_void_p],
+    "muse_norm_adaln_bwd_x3": [c_void_p] * 9 + [c_int, c_i64, c_int, c_float, c_int, *_IMG, c_void_p],
     "muse_colsum_segments": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "muse_silu_bwd": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "muse_dwconv3x3_bwd_nchunk": [c_i64],

@@ -323,29 +323,32 @@ class f32_gemms_as_f16:
         self.on = bool(on)
         self.images = images if images is not None else (F16Images() if on else None)
 
-    @staticmethod
-    def _tell_kernels(on, images):
-        # the producer kernels (*_x3 entry points) write half images with this pass's gradient scale while the mode is on
-        live = on and images is not None
-        check(lib().muse_operand_images(1 if on else 0, float(images.grad_scale) if live else 1.0, images._ensure_stats().data_ptr() if live else None),
-              "muse_operand_images")
-
     def __enter__(self):
         self.prev = (_F32_AS_F16[0], _F16_IMAGES[0])
         _F32_AS_F16[0] = self.on
         if self.on:
             _F16_IMAGES[0] = self.images
-        if self.on or self.prev[0]:
-            self._tell_kernels(self.on, self.images)
         return self
 
     def __exit__(self, *exc):
         _F32_AS_F16[0], _F16_IMAGES[0] = self.prev
-        if self.on or self.prev[0]:
-            self._tell_kernels(self.prev[0], self.prev[1])
         if self.on and self.images is not None and self.images.backward:
             _F16_GUARDS.add(self.images)         # (the owner's optimizer step that follows skips its update if this pass overflowed)
         return False
+
+
+def _image_args(gradient, *planes):
+    """(half, scale, stats) of a producer entry point (*_x3) in the running pass: half = 1 in an "f16" pass (the kernel writes ONE IEEE-half
+    image, and the x3 attention kernels compute in half), scale = the pass's gradient scale for a backward result (`gradient`), 1 for a
+    forward one, stats = the pass's overflow counter.  A plane tensor given must have the mode's dtype (half: float16, else bfloat16)."""
+    half = _F32_AS_F16[0]
+    for p in planes:
+        if p is not None and p.dtype != (torch.float16 if half else torch.bfloat16):
+            raise _hip.MuseHipError(f"operand image of dtype {p.dtype} in a{'n f16' if half else ' bf16x3'} pass")
+    if not half:
+        return 0, 1.0, None
+    im = _F16_IMAGES[0]
+    return 1, im.grad_scale if gradient else 1.0, im._ensure_stats().data_ptr()
 
 
 def cast_to_f16(t, scale=1.0, stats=None):
@@ -510,7 +513,7 @@ class Planes:
         self.shape = torch.Size(planes.shape[1:])
         self.device = planes.device
         # "f16" mode: ONE IEEE-half image [1, rows, cols] = half(x * scale); the scale is the one the producer kernel applied - the
-        # running pass's gradient scale for a backward result, 1 for a forward one (muse_operand_images)
+        # running pass's gradient scale for a backward result, 1 for a forward one (_image_args)
         self.half = planes.dtype == torch.float16
         im = _F16_IMAGES[0]
         self.scale = (im.grad_scale if (im is not None and im.backward) else 1.0) if self.half else 1.0
@@ -1180,26 +1183,29 @@ def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
         # softmax (csrc/attention3.hip fwd_stream_kernel) - q read once, the context and its log-sum-exp written once, no partials
         planes = x3_new_planes(ctx)
         d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
-        check(lib().muse_attention_x3_fwd_stream(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel() if planes is not None else 0, stream()),
-              "muse_attention_x3_fwd_stream")
+        check(lib().muse_attention_x3_fwd_stream(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel() if planes is not None else 0,
+                                                 *_image_args(False, planes), stream()), "muse_attention_x3_fwd_stream")
         x3_put_planes(ctx, planes)
     elif nk == 1:
         planes = x3_new_planes(ctx)          # ctx feeds the output projection: every block writes its rows of the operand planes too
+        img = _image_args(False, planes)
         for qi in range(nq):
             d = _x3_block_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha, qi, 0, kb)
             pp = None if planes is None else planes.data_ptr() + qi * 256 * H * 2
-            check(lib().muse_attention_x3_fwd(C.byref(d), lse[qi].data_ptr(), pp, ctx.numel() if planes is not None else 0, stream()), "muse_attention_x3_fwd")
+            check(lib().muse_attention_x3_fwd(C.byref(d), lse[qi].data_ptr(), pp, ctx.numel() if planes is not None else 0, *img, stream()),
+                  "muse_attention_x3_fwd")
         x3_put_planes(ctx, planes)
     else:
         part = torch.empty((nk, B * Sq, H), dtype=torch.float32, device=dev)
         lp = torch.empty((nk, nq, B * nh, 256), dtype=torch.float32, device=dev)
+        img = _image_args(False)
         for kj in range(nk):
             for qi in range(nq):
                 d = _x3_block_desc(q, k, v, part[kj], B, Sq, Skv, nh, hd, alpha, qi, kj, kb)
-                check(lib().muse_attention_x3_fwd(C.byref(d), lp[kj, qi].data_ptr(), None, 0, stream()), "muse_attention_x3_fwd")
+                check(lib().muse_attention_x3_fwd(C.byref(d), lp[kj, qi].data_ptr(), None, 0, *img, stream()), "muse_attention_x3_fwd")
         planes = x3_new_planes(ctx)          # ctx feeds the output projection: its operand planes come out of the merge kernel
         check(lib().muse_attention_x3_merge(part.data_ptr(), part[0].numel(), lp.data_ptr(), lp[0].numel(), nk, ctx.data_ptr(), lse.data_ptr(),
-                                            ptr(planes), ctx.numel(), B, Sq, nh, stream()), "muse_attention_x3_merge")
+                                            ptr(planes), ctx.numel(), B, Sq, nh, *_image_args(False, planes), stream()), "muse_attention_x3_merge")
         x3_put_planes(ctx, planes)
     _prof_end(e0, "attn_fwd_bf16x3", 4.0 * B * nh * Sq * Skv * hd)
     return ctx, lse
@@ -1221,6 +1227,7 @@ def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha,
     dqp = [dq] if dqs is None else list(dqs)
     dkp = [dk] if dks is None else list(dks)
     dvp = [dv] if dvs is None else list(dvs)
+    img = _image_args(True)
     e0 = _prof_begin()
     for qi in range(nq):
         for kj in range(nk):
@@ -1228,7 +1235,7 @@ def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha,
             (pq, ldq_), (pk, ldk_), (pv, ldv_) = _row_view(dqp[kj], H), _row_view(dkp[qi], H), _row_view(dvp[qi], H)
             check(lib().muse_attention_x3_bwd(C.byref(d), pdo + qi * 256 * lddo * 4, lddo, Sq * lddo, lse[qi].data_ptr(),
                                               pq + qi * 256 * ldq_ * 4, ldq_, Sq * ldq_, pk + kj * 256 * ldk_ * 4, ldk_, Skv * ldk_,
-                                              pv + kj * 256 * ldv_ * 4, ldv_, Skv * ldv_, None, 0, None, 0, None, 0, stream()), "muse_attention_x3_bwd")
+                                              pv + kj * 256 * ldv_ * 4, ldv_, Skv * ldv_, None, 0, None, 0, None, 0, *img, stream()), "muse_attention_x3_bwd")
     for stack, g, rows in ((dqs, dq, B * Sq), (dks, dk, B * Skv), (dvs, dv, B * Skv)):
         if stack is not None:
             pg, ldg = _row_view(g, H)
@@ -1254,7 +1261,7 @@ def attention_x3_fwd(q, k, v, B, Sq, Skv, nh, hd, alpha):
     d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
     planes = x3_new_planes(ctx)          # ctx feeds the output projection: its operand planes come out of the kernel
     e0 = _prof_begin()
-    check(lib().muse_attention_x3_fwd(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel(), stream()), "muse_attention_x3_fwd")
+    check(lib().muse_attention_x3_fwd(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel(), *_image_args(False, planes), stream()), "muse_attention_x3_fwd")
     _prof_end(e0, "attn_fwd_bf16x3", 4.0 * B * nh * Sq * Skv * hd)
     x3_put_planes(ctx, planes)
     return ctx, lse
@@ -1294,20 +1301,21 @@ def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None
         if ent is None or ent[0] is None:
             pl += [None, 0]
         else:
-            if ent[0].stride() != ref.stride() or ent[0].shape != ref.shape or ent[0].dtype != (torch.float16 if _F32_AS_F16[0] else torch.bfloat16):
+            if ent[0].stride() != ref.stride() or ent[0].shape != ref.shape:
                 raise _hip.MuseHipError("attention_x3_bwd: a hi-plane view must mirror its gradient view")
             pl += [ent[0].data_ptr(), int(ent[1])]
+    img = _image_args(True, *(e[0] for e in planes if e is not None))
     if streamed:
         # dQ per query block over the streamed key blocks (it also leaves dO . O per query in dsum), then dK / dV per key block over the
         # streamed query blocks: every gradient written once (bwd_dq_stream_kernel / bwd_dkv_stream_kernel)
         dsum = torch.empty_like(lse)
-        check(lib().muse_attention_x3_bwd_stream(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), dsum.data_ptr(), *args, *pl, stream()),
+        check(lib().muse_attention_x3_bwd_stream(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), dsum.data_ptr(), *args, *pl, *img, stream()),
               "muse_attention_x3_bwd_stream")
         for t in (dq, dk, dv):
             if t is not None:
                 _touched(t)
     else:
-        check(lib().muse_attention_x3_bwd(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), *args, *pl, stream()), "muse_attention_x3_bwd")
+        check(lib().muse_attention_x3_bwd(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), *args, *pl, *img, stream()), "muse_attention_x3_bwd")
     _prof_end(e0, "attn_bwd_bf16x3", 10.0 * B * nh * Sq * Skv * hd)
     return dq, dk, dv
 
@@ -1362,7 +1370,7 @@ def x3_new_planes(t):
 
 def planes_alloc(shape, device):
     """the operand-image tensor a producer kernel of the running step writes for a [rows, cols] result: [2, rows, cols] bf16 (hi, lo
-    planes, "bf16x3" mode) or [1, rows, cols] IEEE half ("f16" mode: muse_operand_images tells the kernels which)"""
+    planes, "bf16x3" mode) or [1, rows, cols] IEEE half ("f16" mode: _image_args tells the kernels which)"""
     if _F32_AS_F16[0]:
         return torch.empty((1,) + tuple(shape), dtype=torch.float16, device=device)
     return torch.empty((2,) + tuple(shape), dtype=torch.bfloat16, device=device)
@@ -1381,13 +1389,14 @@ def glu_fwd(ab, planes_only=False):
         if not (planes_only_ok(rows, two_i // 2) and ab.dtype == torch.float32 and ab.is_contiguous()):
             raise _hip.MuseHipError("glu_fwd(planes_only=True) outside planes_only_ok")
         planes = planes_alloc((rows, two_i // 2), ab.device)
-        check(lib().muse_glu_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, stream()), "muse_glu_fwd_x3")
+        check(lib().muse_glu_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(False, planes), stream()), "muse_glu_fwd_x3")
         return Planes(planes)
     h = torch.empty((rows, two_i // 2), dtype=ab.dtype, device=ab.device)
     im = _x3_producing(ab)
     if im is not None and (two_i // 2) % 8 == 0:
         planes = planes_alloc((rows, two_i // 2), ab.device)
-        check(lib().muse_glu_fwd_x3(ab.data_ptr(), h.data_ptr(), planes.data_ptr(), rows, two_i // 2, stream()), "muse_glu_fwd_x3")
+        check(lib().muse_glu_fwd_x3(ab.data_ptr(), h.data_ptr(), planes.data_ptr(), rows, two_i // 2, *_image_args(False, planes), stream()),
+              "muse_glu_fwd_x3")
         im.put_planes(h, planes)
         return h
     check(lib().muse_glu_fwd(ab.data_ptr(), h.data_ptr(), dt(ab), rows, two_i // 2, stream()), "muse_glu_fwd")
@@ -1401,13 +1410,15 @@ def glu_bwd(ab, dh, planes_only=False):
         if not (planes_only_ok(rows, two_i) and ab.dtype == torch.float32 and dh.dtype == torch.float32 and ab.is_contiguous() and dh.is_contiguous()):
             raise _hip.MuseHipError("glu_bwd(planes_only=True) outside planes_only_ok")
         planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, stream()), "muse_glu_bwd_x3")
+        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(True, planes), stream()),
+              "muse_glu_bwd_x3")
         return Planes(planes)
     dab = torch.empty_like(ab)
     im = _x3_producing(ab)
     if im is not None and dh.dtype == torch.float32 and dh.is_contiguous() and two_i % 16 == 0:
         planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), planes.data_ptr(), rows, two_i // 2, stream()), "muse_glu_bwd_x3")
+        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), planes.data_ptr(), rows, two_i // 2, *_image_args(True, planes),
+                                    stream()), "muse_glu_bwd_x3")
         im.put_planes(dab, planes)
         return dab
     check(lib().muse_glu_bwd(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), dt(ab), rows, two_i // 2, stream()), "muse_glu_bwd")
@@ -1568,19 +1579,21 @@ def soft_ce_bwd(logits, labels, soft, seq1, lse, psum, loss_out, grad_out, out_d
     return dl
 
 
-def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+# skip (every adamw_*): None, or the device int32 overflow counter of an "f16" backward pass - the kernel leaves parameters and moments
+# untouched when it is non-zero (training.FusedAdamW's guard)
+def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None):
     require_gpu(p, g, m, v)
     e0 = _prof_begin()
     check(lib().muse_adamw_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
-                                beta2, eps, weight_decay, step, grad_scale, stream()), "muse_adamw_flat")
+                                beta2, eps, weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_flat")
     _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
 
 
-def adamw_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+def adamw_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None):
     """one AdamW launch over a device-side table of tensors (muse_adamw_multi; training.FusedAdamW builds the table)"""
     require_gpu(table, chunk_first)
     check(lib().muse_adamw_multi(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
-                                 weight_decay, step, grad_scale, stream()), "muse_adamw_multi")
+                                 weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_multi")
 
 
 def ema_multi(table, chunk_first, num_tensors, num_chunks, one_minus_decay):
@@ -1602,7 +1615,7 @@ def _group_hyper(groups):
     return (ctypes.c_float * len(flat))(*flat)
 
 
-def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step, grad_scale=1.0):
+def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step, grad_scale=1.0, skip=None):
     """AdamW on elements [base, base + p.numel()) of a flat buffer whose segments belong to different parameter groups
     (muse_adamw_flat_groups); p, g, m, v, p_bf16 are the slices starting at `base`; `groups`: torch param_groups-like dicts"""
     require_gpu(p, g, m, v, seg_end, seg_group)
@@ -1611,18 +1624,18 @@ def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step
     e0 = _prof_begin()
     check(lib().muse_adamw_flat_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
                                        seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()),
-                                       ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), stream()),
+                                       ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
           "muse_adamw_flat_groups")
     _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
 
 
-def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step, grad_scale=1.0):
+def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step, grad_scale=1.0, skip=None):
     """muse_adamw_multi with a group column in the table (7 x int64 per tensor)"""
     require_gpu(table, chunk_first)
     import ctypes
     hy = _group_hyper(groups)
     check(lib().muse_adamw_multi_groups(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
-                                        ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), stream()),
+                                        ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
           "muse_adamw_multi_groups")
 
 
@@ -1854,20 +1867,25 @@ def upsample2x_split(x, B, H, W, C):
     return hi, lo
 
 
+# the fused GroupNorm convolution may take its persistent kernel (one workgroup per CU walks the tiles: 6-8 % faster when the convolution
+# has the chip to itself - a tokenizer or decoder pass on its own).  Default MUSE_CONV_PERSIST, else on; conv_persistent scopes it.
+_CONV_PERSISTENT = [os.environ.get("MUSE_CONV_PERSIST", "1") != "0"]
+
+
 class conv_persistent:
-    """with ops.conv_persistent(False): ... - the fused convolutions launched inside run on the launch-per-tile kernel (muse_conv_persistent):
-    what a tokenizer pass enqueued BESIDE a train step wants (muse.TrainStep); restored on exit"""
+    """with ops.conv_persistent(False): ... - the fused convolutions launched inside run on the launch-per-tile kernel: what a tokenizer
+    pass enqueued BESIDE a train step wants (muse.TrainStep); restored on exit"""
 
     def __init__(self, on):
-        self.on = 1 if on else 0
+        self.on = bool(on)
 
     def __enter__(self):
-        self.prev = lib().muse_conv_persistent(-1)
-        lib().muse_conv_persistent(self.on)
+        self.prev = _CONV_PERSISTENT[0]
+        _CONV_PERSISTENT[0] = self.on
         return self
 
     def __exit__(self, *exc):
-        lib().muse_conv_persistent(self.prev)
+        _CONV_PERSISTENT[0] = self.prev
         return False
 
 
@@ -1900,7 +1918,7 @@ def conv2d_nhwc_gn_split2(x, scale, shift, w_hi, w_lo, B, H, W, Cin, Cout, bias=
     e0 = _prof_begin()
     check(lib().muse_conv2d_nhwc_gn_split2(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr(), ptr(bias),
                                            ptr(residual), out.data_ptr(), ptr(part), gn_groups if part is not None else 0,
-                                           B, H, W, Cin, Cout, 3, stream()), "muse_conv2d_nhwc_gn_split2")
+                                           B, H, W, Cin, Cout, 3, int(_CONV_PERSISTENT[0]), stream()), "muse_conv2d_nhwc_gn_split2")
     _prof_end(e0, "conv_bf16x3_dma", 2.0 * B * H * W * Cout * 9 * Cin)
     if e0 is not None:
         PROF_BYTES["conv_bf16x3_dma"] = PROF_BYTES.get("conv_bf16x3_dma", 0.0) + _nbytes(x, w_hi, w_lo, residual, out)
@@ -2185,7 +2203,7 @@ def norm_adaln_fwd(x, w, ss, batch, eps, mode, residual=None, out_dtype=torch.fl
             raise _hip.MuseHipError("norm_adaln_fwd(planes_only=True) outside planes_only_ok")
         planes = planes_alloc((rows, cols), x.device)
         check(lib().muse_norm_adaln_fwd_x3(x.data_ptr(), ptr(residual), ptr(w), ss.data_ptr(), pre.data_ptr(), None, planes.data_ptr(),
-                                           batch, rows // batch, cols, eps, mode, stream()), "muse_norm_adaln_fwd_x3")
+                                           batch, rows // batch, cols, eps, mode, *_image_args(False, planes), stream()), "muse_norm_adaln_fwd_x3")
         return Planes(planes), pre
     m = torch.empty((rows, cols), dtype=out_dtype, device=x.device)
     f32 = out_dtype == torch.float32
@@ -2193,7 +2211,7 @@ def norm_adaln_fwd(x, w, ss, batch, eps, mode, residual=None, out_dtype=torch.fl
     if im is not None and cols % 8 == 0:        # "bf16x3" mode: m feeds weight GEMMs - its operand planes come out of this kernel
         planes = planes_alloc((rows, cols), x.device)
         check(lib().muse_norm_adaln_fwd_x3(x.data_ptr(), ptr(residual), ptr(w), ss.data_ptr(), pre.data_ptr(), m.data_ptr(), planes.data_ptr(),
-                                           batch, rows // batch, cols, eps, mode, stream()), "muse_norm_adaln_fwd_x3")
+                                           batch, rows // batch, cols, eps, mode, *_image_args(False, planes), stream()), "muse_norm_adaln_fwd_x3")
         im.put_planes(m, planes)
         return m, pre
     check(lib().muse_norm_adaln_fwd(x.data_ptr(), ptr(residual), ptr(w), ss.data_ptr(), pre.data_ptr(), m.data_ptr() if f32 else None,
@@ -2214,7 +2232,8 @@ def norm_adaln_bwd(dm, v, w, ss, batch, eps, mode, dpre=None, also_bf16=False, d
     if im is not None and cols % 8 == 0:        # "bf16x3" mode: dv is the dY of the weight GEMMs below - planes from this kernel
         planes = planes_alloc((rows, cols), v.device)
         check(lib().muse_norm_adaln_bwd_x3(dm.data_ptr(), ptr(dpre), v.data_ptr(), ptr(w), ss.data_ptr(), dv.data_ptr(), planes.data_ptr(),
-                                           part.data_ptr(), spart.data_ptr(), batch, rows // batch, cols, eps, mode, stream()), "muse_norm_adaln_bwd_x3")
+                                           part.data_ptr(), spart.data_ptr(), batch, rows // batch, cols, eps, mode, *_image_args(True, planes),
+                                           stream()), "muse_norm_adaln_bwd_x3")
         im.put_planes(dv, planes)
     else:
         check(lib().muse_norm_adaln_bwd(dm.data_ptr(), ptr(dpre), v.data_ptr(), ptr(w), ss.data_ptr(), dv.data_ptr(), ptr(dvb), part.data_ptr(),

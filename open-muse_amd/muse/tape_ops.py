@@ -149,7 +149,7 @@ class TapeOps:
         return self._f16_scale_policy(overflowed, growth_interval)
 
     # With muse.FusedAdamW nothing has to be called: its kernels skip the update on the device when a backward pass of this model that
-    # made the gradients overflowed (muse_adamw_skip_flag), and the next backward pass reads that step's counters - copied to pinned
+    # made the gradients overflowed (the `skip` argument of ops.adamw_*), and the next backward pass reads that step's counters - copied to pinned
     # memory behind the update - and moves the scale by the same policy.  f16_auto_scale = False leaves the scale to the caller.
     f16_auto_scale = True
     f16_growth_interval = 2000

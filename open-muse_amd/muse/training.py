@@ -216,7 +216,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self._table = self._chunk_first = self._table_key = self._stage = None   # per-tensor mode: device table of muse_adamw_multi
         self._ranges_done = self._ranges_done_live = None                        # (step, [(begin, end), ...]) applied inside backward
         self._upd_stream, self._upd_used = None, False                           # stream of the per-bucket update (begin_step_in_reducer)
-        self._skip_flag = None  # ("f16" mode: the overflow counter the update in flight is guarded by)
         self.grad_scale = 1.0   # multiplied into the gradient inside the kernel (GradReducer sets 1/world for SUM reductions)
 
     def _all_params(self):
@@ -280,7 +279,7 @@ class FusedAdamW(torch.optim.Optimizer):
         shadow = model._flat_c if model._flat_c is not None and model._flat_c.device == flat.device else None
         done = self._ranges_done
         self._ranges_done = None
-        guards = self._f16_guard_on(flat.device)     # ("f16" mode: as in _step_per_tensor - the update is skipped on the device on overflow)
+        guards, skip = self._f16_guard_on(flat.device)     # ("f16" mode: as in _step_per_tensor - the update is skipped on the device on overflow)
         try:
             if done is not None and done[0] == self._step:
                 # backward already applied this step's update range by range (begin_step_in_backward); cover what it did not report
@@ -288,28 +287,31 @@ class FusedAdamW(torch.optim.Optimizer):
                 pos = 0
                 for b, e in covered:
                     if b > pos:
-                        self._apply(model, pos, b, shadow)
+                        self._apply(model, pos, b, shadow, skip)
                     pos = max(pos, e)
                 if pos < flat.numel():
-                    self._apply(model, pos, flat.numel(), shadow)
+                    self._apply(model, pos, flat.numel(), shadow, skip)
             else:
-                self._apply(model, 0, flat.numel(), shadow)
+                self._apply(model, 0, flat.numel(), shadow, skip)
         finally:
             self._f16_guard_off(guards)
         model._note_shadow_refreshed(shadow is not None)
         return loss
 
-    def _apply(self, model, b, e, shadow):
+    def _apply(self, model, b, e, shadow, skip=None):
         flat, g = model.flat_params(), model.flat_grads()
+        # (the guard only when there is one: an unguarded update stays the call it always was, so a stand-in for ops.adamw_flat /
+        #  adamw_flat_groups written without the keyword - a host-logic test, a CPU restatement of the kernel - keeps working)
+        guard = {} if skip is None else {"skip": skip}
         if len(self.param_groups) > 1:
             seg_end, seg_group = self._segments(model)
             ops.adamw_flat_groups(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], b,
-                                  seg_end, seg_group, self.param_groups, self._step_for_apply, grad_scale=float(self.grad_scale))
+                                  seg_end, seg_group, self.param_groups, self._step_for_apply, grad_scale=float(self.grad_scale), **guard)
             return
         grp = self.param_groups[0]
         ops.adamw_flat(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], float(grp["lr"]),
                        grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], self._step_for_apply,
-                       grad_scale=float(self.grad_scale))
+                       grad_scale=float(self.grad_scale), **guard)
 
     @property
     def _step_for_apply(self):
@@ -497,25 +499,25 @@ class FusedAdamW(torch.optim.Optimizer):
         # model's next backward pass halves the gradient scale (tape_ops._gemm_mode) - GradScaler's policy without a host round trip
         # (the host does not know about the skip when it happens: self._step advances anyway, so the bias corrections of the following
         #  updates are those of one step later - a factor that tends to 1)
-        guards = self._f16_guard_on(dev)
+        guards, skip = self._f16_guard_on(dev)
         try:
             if multi:
                 ops.adamw_multi_groups(self._table, self._chunk_first, len(rows), self._nchunks, self.param_groups, self._step,
-                                       grad_scale=float(self.grad_scale))
+                                       grad_scale=float(self.grad_scale), skip=skip)
             else:
                 grp = self.param_groups[0]
                 ops.adamw_multi(self._table, self._chunk_first, len(rows), self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
-                                grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale))
+                                grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale), skip=skip)
         finally:
             self._f16_guard_off(guards)
         return loss
 
     def _f16_guard_on(self, dev):
-        """"f16" compute mode: arm the device-side skip of the update that follows with the overflow counter of the backward pass(es)
-        that made these gradients - passes of a model whose parameters this optimizer steps (F16Images.owner); a pass of any other model
-        gates nothing here.  -> the guards to hand to _f16_guard_off once the update is enqueued"""
+        """"f16" compute mode: the device-side skip of the update that follows is the overflow counter of the backward pass(es) that
+        made these gradients - passes of a model whose parameters this optimizer steps (F16Images.owner); a pass of any other model gates
+        nothing here.  -> (the guards to hand to _f16_guard_off once the update is enqueued, the counter the update's kernel reads or None)"""
         if not ops._F16_GUARDS:
-            return []
+            return [], None
         mine, guards = None, []
         for images in list(ops._F16_GUARDS):
             model = images.owner() if images.owner is not None else None
@@ -526,21 +528,16 @@ class FusedAdamW(torch.optim.Optimizer):
             if any(id(q) in mine for q in model.parameters()):
                 guards.append(images)
         if not guards:
-            return []
+            return [], None
         for images in guards:
             if dist.is_available() and dist.is_initialized():
                 dist.all_reduce(images._stats)        # every rank skips together (GradScaler's found_inf all-reduce)
         # (one counter the kernel reads; two models stepped by one optimizer: their sum, stream-ordered like the update)
-        self._skip_flag = guards[0]._stats if len(guards) == 1 else torch.stack([g._stats for g in guards]).sum(0, dtype=torch.int32)
-        ops.check(ops.lib().muse_adamw_skip_flag(self._skip_flag.data_ptr()), "muse_adamw_skip_flag")
-        return guards
+        skip = guards[0]._stats if len(guards) == 1 else torch.stack([g._stats for g in guards]).sum(0, dtype=torch.int32)
+        return guards, skip
 
     def _f16_guard_off(self, guards):
-        """the guarded update is enqueued: disarm, and take each pass's counters off the device for its model's scale policy"""
-        if not guards:
-            return
-        ops.check(ops.lib().muse_adamw_skip_flag(None), "muse_adamw_skip_flag")
-        self._skip_flag = None
+        """the guarded update is enqueued: take each pass's counters off the device for its model's scale policy"""
         for images in guards:
             images.after_optimizer_step()
             ops._F16_GUARDS.discard(images)

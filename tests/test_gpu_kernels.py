@@ -1652,7 +1652,7 @@ def test_f16_mode_weight_gradient_with_k_split():
 
 @pytest.mark.parametrize("B,Sq,Skv,nh,packed", [(3, 256, 256, 4, True), (2, 256, 77, 3, False), (2, 256, 240, 2, False), (1, 512, 512, 2, True), (1, 512, 77, 2, False)])
 def test_fused_attention_f16_mode(B, Sq, Skv, nh, packed):
-    """attention3.hip H16: inside an f16 step (muse_operand_images) the fused attention core runs every product as ONE half MFMA
+    """attention3.hip H16: inside an f16 step (half = 1: ops._image_args) the fused attention core runs every product as ONE half MFMA
     product - q, k, v, P rounded to half's 10-bit mantissa (the TF32 operand format), dO and dS times the pass's power-of-two gradient
     scale before their conversion, results handed back divided by it.  Against float64: forward and gradients to TF32-class error
     (2e-3 of their scale; the bf16x3 kernels: 2e-5 / 5e-5, a bf16 core: 1.5e-2 / 3e-2); a gradient-sized dO (1e-6) needs the scale
@@ -1702,7 +1702,7 @@ def test_fused_attention_f16_mode(B, Sq, Skv, nh, packed):
 
 def test_f16_mode_producers_write_half_images():
     """Inside an f16 step the producer kernels (GLU forward / backward, AdaLN-norm forward / backward, the fused attention's context and
-    gradients) write their result's IEEE-half operand image next to the f32 result (muse_operand_images): bit for bit what
+    gradients) write their result's IEEE-half operand image next to the f32 result (half = 1: ops._image_args): bit for bit what
     muse_cast_f32_to_f16 makes of that result - unscaled in a forward pass, times the pass's gradient scale in a backward pass -
     registered under the result tensor so the product that reads it launches no cast; the f32 results are the plain kernels' bits
     (the attention core's, which computes in half itself inside the mode, to that precision).

@@ -425,7 +425,7 @@ def test_f16_mode_training_steps(golden_dir):
 def test_f16_mode_optimizer_guard(golden_dir):
     """the f16 mode with muse.FusedAdamW and NO call in the training loop: the toy model of test_f16_mode_training_steps overflows half's range
     at the default gradient scale (NaN gradients).  The optimizer kernel reads the backward pass's overflow counter on the device and
-    leaves parameters and moments untouched (muse_adamw_skip_flag); the next backward pass reads that step's counters from pinned memory
+    leaves parameters and moments untouched (the `skip` argument of ops.adamw_*); the next backward pass reads that step's counters from pinned memory
     and halves the scale.  Parameters stay finite throughout, three updates are skipped, the scale ends where the explicit recipe puts
     it, and the loss of the steps that were applied falls like the exact-f32 run's."""
     import muse

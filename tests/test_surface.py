@@ -243,6 +243,36 @@ def test_library_exports_every_declared_symbol():
     assert _hip.lib().muse_layernorm_bwd_nblk(16448) == 1028
 
 
+def test_ctypes_signatures_match_the_header():
+    """every prototype of include/muse_hip.h against _hip.SIGNATURES, argument by argument: the same arity and the same kind per
+    position (a ctypes list one entry short shifts every later argument - a pointer arrives as an int), and the same return type"""
+    from muse import _hip
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(ROOT, "include", "muse_hip.h")).read(), flags=re.S)
+    protos = re.findall(r"^\s*(int|int64_t)\s+(muse_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
+    assert len(protos) == len(set(_hip.SIGNATURES)), sorted({p[1] for p in protos} ^ set(_hip.SIGNATURES))
+
+    def c_kind(param):
+        words = param.replace("*", " * ").split()
+        if "*" in words:
+            return "ptr"
+        return {"int32_t": "i32", "int": "i32", "int64_t": "i64", "float": "f32", "uint32_t": "u32", "uint64_t": "u64"}[words[0]]
+
+    def ctypes_kind(t):
+        if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+            return "ptr"
+        return {ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_float: "f32", ctypes.c_uint32: "u32", ctypes.c_uint64: "u64"}[t]
+
+    bad = []
+    for ret, name, params in protos:
+        params = [p.strip() for p in params.split(",")]
+        want = [] if params == ["void"] else [c_kind(p) for p in params]
+        got = [ctypes_kind(t) for t in _hip.SIGNATURES[name]]
+        ret_got = _hip._RESTYPES.get(name, ctypes.c_int32)
+        if want != got or ret_got is not {"int": ctypes.c_int32, "int64_t": ctypes.c_int64}[ret]:
+            bad.append((name, ret, want, got))
+    assert not bad, bad
+
+
 def test_sampling_schedules():
     from muse.sampling import cosine_schedule, get_mask_chedule
     t = torch.tensor([0.0, 0.5, 1.0])
