@@ -304,6 +304,52 @@ int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p
                            int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream);
 int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
                             const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream);
+
+/* ---- gradient clipping by global L2 norm (torch.nn.utils.clip_grad_norm_ with norm_type 2, which the reference reaches through
+ * accelerator.clip_grad_norm_: training/train_muse.py:758-759, training/train_maskgit_imagenet.py:435-436) and the per-parameter norms
+ * of log_grad_norm (training/train_muse.py:1309-1314), all on the device.
+ * Sum of squares: one f64 partial per (parameter, 4096-element chunk counted from the parameter's own start) stored to
+ * slab[chunk_first[t] + c] by a plain store - no floating-point atomics, so the slab is the same bits however the gradient is cut
+ * into calls and in whatever order they run.  chunk_first (device int32, num + 1 entries): exclusive
+ * prefix sum of ceil(n_t / 4096) - muse_adamw_multi's table.
+ * _flat: parameters [offset_t, offset_t + n_t) of a flat f32 gradient buffer whose element 0 is g_flat; `ptab` = {offset, n} x int64
+ *   per parameter, ascending, once in DEVICE memory (the kernel's) and once in HOST memory with chunk_first (`*_host`, read during the
+ *   call).  The call covers the parameters inside [base, base + n); alignment padding between parameters belongs to no norm.  base
+ *   must be a parameter's offset and base + n must not cut one: MUSE_ERR_BAD_ARG otherwise.  Offsets need no alignment.
+ * _multi: muse_adamw_multi's / _multi_groups' pointer table (`ncol` = 6 or 7 int64 per tensor: gradient pointer in column 1, n in
+ *   column 5) - every tensor in one launch. */
+int muse_gradnorm_flat(const float* g_flat, int64_t base, int64_t n, const int64_t* ptab_host, const int32_t* chunk_first_host,
+                       const int64_t* ptab, const int32_t* chunk_first, int32_t num_params, double* slab, void* stream);
+int muse_gradnorm_multi(const int64_t* table, int32_t ncol, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                        double* slab, void* stream);
+/* One small launch: the chunks of each parameter folded in chunk order, the parameters in parameter order (f64).  psum: num_tensors
+ * + 1 doubles of scratch; the last one is the launch's ticket counter and must be ZERO before the first call (every call leaves it zero).  out (device f32, 3 + num_tensors): [0] norm = grad_scale * sqrt(total), rounded once to f32 - grad_scale is
+ * the host factor the AdamW entry points multiply the gradient by (1 / world under a SUM reduction), so this is the norm of the
+ * gradient the update uses; [1] coef = min(1, max_norm / (norm + 1e-6)) in f32 (clip_grad_norm_'s formula; a NaN norm gives a NaN
+ * coefficient, like torch.clamp); [2] scale = grad_scale * coef; [3 + t] = grad_scale * sqrt(sum of parameter t). */
+int muse_gradnorm_finalize(const double* slab, const int32_t* chunk_first, int32_t num_tensors, double* psum, float grad_scale,
+                           float max_norm, float* out, void* stream);
+/* g *= *scale in place (clip_grad_norm_'s `g.mul_(clip_coef_clamped)`, applied also when the coefficient is 1, as torch does):
+ * n elements of a flat buffer / every gradient of a pointer table as for muse_gradnorm_multi. */
+int muse_grad_scale_flat(float* g, int64_t n, const float* scale, void* stream);
+int muse_grad_scale_multi(const int64_t* table, int32_t ncol, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                          const float* scale, void* stream);
+/* The four AdamW entry points with the gradient factor read ON THE DEVICE (`scale_dev`: out + 2 of muse_gradnorm_finalize) in place
+ * of the host's grad_scale: clipping (training/train_muse.py:758-759 followed by optimizer.step(), :761) without a host round trip or
+ * a write pass over the gradient.  Same update arithmetic, same skip guard.  The product g * *scale_dev is rounded once to f32 before
+ * the update (the host-factor entry points feed the unrounded product into `g - m` through an fma, invisible for their power-of-two
+ * factors), so the result is bit-identical to muse_grad_scale_* followed by the host-factor entry point with grad_scale 1. */
+int muse_adamw_flat_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int32_t step, const float* scale_dev, const int32_t* skip, void* stream);
+int muse_adamw_multi_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* scale_dev,
+                         const int32_t* skip, void* stream);
+int muse_adamw_flat_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                               const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
+                               int32_t ngroups, int32_t step, const float* scale_dev, const int32_t* skip, void* stream);
+int muse_adamw_multi_groups_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                                const float* group_hyper, int32_t ngroups, int32_t step, const float* scale_dev, const int32_t* skip,
+                                void* stream);
 /* out[i] (+)= sum over s < nslices of ws[s*stride + i]: reduction of split-K partial results (n, stride % 4 == 0) */
 int muse_sum_slices(const float* ws, float* out, int32_t nslices, int64_t n, int64_t stride, int32_t accumulate, void* stream);
 /* njobs <= 16 reductions in ONE launch, each bit-identical to the single-job kernel it stands for: kind 0 = muse_sum_slices

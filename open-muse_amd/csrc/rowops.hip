@@ -1576,18 +1576,37 @@ extern "C" int muse_soft_ce_bwd(const float* logits, const int64_t* labels, cons
 // =================================================================================================================
 // AdamW over a flat f32 buffer; optional bf16 shadow refresh.  7 x 4 B per parameter of HBM traffic (+2 B shadow).
 // =================================================================================================================
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+// The gradient factor.  DEV = false (the host's grad_scale, a kernel argument): the plain product, which the compiler contracts into the
+// `gr - m` that follows (one fma on the unrounded product; invisible for a power of two, what grad_scale is).  DEV = true (the *_dev entry
+// points: the factor is read from device memory, grad_scale * clip coefficient written by muse_gradnorm_finalize): the product is rounded
+// once and that value goes into the update - "scale inside the kernel" and "scale the buffer, then step" are the same bits.
+template <bool DEV> __device__ __forceinline__ float grad_times(float g, float s) {
+  if constexpr (DEV) {
+#pragma clang fp contract(off)
+    float r = g * s;
+    asm volatile("" : "+v"(r));
+    return r;
+  } else {
+    return g * s;
+  }
+}
+// `skip` is the f16 mode's overflow guard; `sdev` (DEV only) the device-side factor that takes gscale's place
+#define ADAMW_PROLOGUE                    \
+  if (skip && *skip != 0) return;         \
+  if constexpr (DEV) gscale = *sdev;
+template <bool DEV> __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
                                                     float b2, float eps, float decay, float omb1, float omb2,
-                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
+                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip,
+                                                    const float* __restrict__ sdev) {
+  ADAMW_PROLOGUE
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float pp[4], gg[4], mm[4], vv[4];
     V4<float>::load(p + i * 4, pp); V4<float>::load(g + i * 4, gg); V4<float>::load(m + i * 4, mm); V4<float>::load(v + i * 4, vv);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float gr = gg[j] * gscale;
+      const float gr = grad_times<DEV>(gg[j], gscale);
       pp[j] = pp[j] * decay;                           // param.mul_(1 - lr * weight_decay), factor rounded once on the host
       mm[j] = fmaf(omb1, gr - mm[j], mm[j]);           // exp_avg.lerp_(grad, 1 - beta1)
       vv[j] = fmaf(omb2, gr * gr, vv[j] * b2);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
@@ -1600,7 +1619,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   // tail (n % 4)
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long i = (n4 << 2) + threadIdx.x;
-    const float gr = g[i] * gscale;
+    const float gr = grad_times<DEV>(g[i], gscale);
     float pp = p[i] * decay;
     const float mm = fmaf(omb1, gr - m[i], m[i]);
     const float vv = fmaf(omb2, gr * gr, v[i] * b2);
@@ -1609,8 +1628,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     if (pb) pb[i] = f32_to_bf16(pp);
   }
 }
-extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
+                                                    float b2, float eps, float decay, float omb1, float omb2,
+                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
+  adamw_body<false>(p, g, m, v, pb, n, lr, b1, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, gscale, skip, nullptr);
+}
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
+                                                        float b2, float eps, float decay, float omb1, float omb2,
+                                                        float step_size, float bc2_sqrt, const float* __restrict__ sdev,
+                                                        const int* __restrict__ skip) {
+  adamw_body<true>(p, g, m, v, pb, n, lr, b1, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, 0.f, skip, sdev);
+}
+// scale_dev != NULL: the *_dev entry point (the factor is read on the device and takes grad_scale's place)
+static int adamw_flat_launch(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int32_t step, float grad_scale, const float* scale_dev, const int32_t* skip, void* stream) {
   if (n <= 0) return 0;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
@@ -1619,19 +1652,34 @@ extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, voi
   const float bc2_sqrt = (float)sqrt(bc2);
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
   const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                     (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
+  if (scale_dev)
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
+                       (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, scale_dev, skip);
+  else
+    hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
+                       (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
   return (int)hipGetLastError();
+}
+extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, skip, stream);
+}
+extern "C" int muse_adamw_flat_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, int32_t step, const float* scale_dev, const int32_t* skip,
+                                   void* stream) {
+  if (!scale_dev) return MUSE_ERR_BAD_ARG;
+  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, 0.f, scale_dev, skip, stream);
 }
 
 // Multi-tensor form: ONE launch over a device-side table of tensors (models whose parameters are ordinary tensors, not views of
 // a flat buffer: MaskGiTUViT has ~500, and 500 launches of 9 us each were 4 % of its step).  The table is 6 x int64 per tensor:
 // {p, g, m, v, p_bf16 or 0, n}; `chunk_first[t]` = index of tensor t's first 4096-element chunk (exclusive prefix sum, nt + 1
 // entries); block b owns chunk b: binary search -> (tensor, offset).  Same arithmetic, same order, as adamw_kernel.
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+template <bool DEV> __device__ __forceinline__ void adamw_multi_body(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
                                                           float b2, float eps, float decay, float omb1, float omb2,
-                                                          float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;
+                                                          float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip,
+                                                          const float* __restrict__ sdev) {
+  ADAMW_PROLOGUE
   int lo = 0, hi = nt;                    // largest t with chunk_first[t] <= blockIdx.x
   while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
   const long* e = table + (long)lo * 6;
@@ -1646,7 +1694,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict
       V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gr = gg[j] * gscale;
+        const float gr = grad_times<DEV>(gg[j], gscale);
         pp[j] = pp[j] * decay;
         mm[j] = fmaf(omb1, gr - mm[j], mm[j]);
         vv[j] = fmaf(omb2, gr * gr, vv[j] * b2);
@@ -1660,7 +1708,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict
   // scalar: the whole chunk when a pointer is unaligned, else the (n % 4) tail of the tensor's last chunk
   const long s0 = vec ? base + ((end - base) & ~3L) : base;
   for (long i = s0 + threadIdx.x; i < end; i += 256) {
-    const float gr = g[i] * gscale;
+    const float gr = grad_times<DEV>(g[i], gscale);
     float pp = p[i] * decay;
     const float mm = fmaf(omb1, gr - m[i], m[i]);
     const float vv = fmaf(omb2, gr * gr, v[i] * b2);
@@ -1668,6 +1716,16 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict
     p[i] = pp; m[i] = mm; v[i] = vv;
     if (pb) pb[i] = f32_to_bf16(pp);
   }
+}
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+                                                          float b2, float eps, float decay, float omb1, float omb2,
+                                                          float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
+  adamw_multi_body<false>(table, chunk_first, nt, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, gscale, skip, nullptr);
+}
+__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+                                                              float b2, float eps, float decay, float omb1, float omb2, float step_size,
+                                                              float bc2_sqrt, const float* __restrict__ sdev, const int* __restrict__ skip) {
+  adamw_multi_body<true>(table, chunk_first, nt, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, 0.f, skip, sdev);
 }
 // Exponential moving average of the weights (reference muse/modeling_ema.py:118-137, called right behind the optimizer step,
 // training/train_muse.py:779-780): shadow -= (1 - decay) * (shadow - param) over EVERY tracked tensor in one launch - the reference
@@ -1710,8 +1768,9 @@ extern "C" int muse_ema_multi(const int64_t* table, const int32_t* chunk_first, 
   return (int)hipGetLastError();
 }
 
-extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+static int adamw_multi_launch(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const float* scale_dev,
+                              const int32_t* skip, void* stream) {
   if (num_tensors <= 0 || num_chunks <= 0) return 0;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
@@ -1719,9 +1778,24 @@ extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first
   const float bc2_sqrt = (float)sqrt(bc2);
   const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
   const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first, num_tensors,
-                     beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
+  if (scale_dev)
+    hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
+                       num_tensors, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, scale_dev, skip);
+  else
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first, num_tensors,
+                       beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
   return (int)hipGetLastError();
+}
+extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+  return adamw_multi_launch(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, skip,
+                            stream);
+}
+extern "C" int muse_adamw_multi_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* scale_dev,
+                                    const int32_t* skip, void* stream) {
+  if (!scale_dev) return MUSE_ERR_BAD_ARG;
+  return adamw_multi_launch(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, 0.f, scale_dev, skip, stream);
 }
 
 // ---- parameter groups (training/train_muse.py:425-445: no weight decay on bias / LayerNorm / embedding weights) ---------------------
@@ -1758,11 +1832,12 @@ __device__ __forceinline__ void adam_update1(float& pp, float gr, float& mm, flo
 // names its parameter group.  The call covers elements [base, base + n) of the flat buffer (p, g, m, v, pb point at element `base`):
 // any slice, so the in-backward / behind-the-all-reduce range updates share the table.  Block b owns elements [4096 b, 4096 b + 4096)
 // of the slice; its first / last segment are found once per block (uniform binary searches), a lane then only steps inside that range.
-__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+template <bool DEV> __device__ __forceinline__ void adamw_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
                                                            const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
-                                                           AdamGroups G, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
+                                                           const AdamGroups& G, float gscale, const int* __restrict__ skip,
+                                                           const float* __restrict__ sdev) {
+  ADAMW_PROLOGUE
   const long c0 = (long)blockIdx.x * 4096, c1 = c0 + 4096 < n ? c0 + 4096 : n;
   auto seg_of = [&](long pos) {   // smallest s with seg_end[s] > pos (positions beyond the last end: the last segment)
     int lo = 0, hi = nseg - 1;
@@ -1777,14 +1852,14 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
       float pp[4], gg[4], mm[4], vv[4];
       V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) adam_update1(pp[j], gg[j] * gscale, mm[j], vv[j], h);
+      for (int j = 0; j < 4; ++j) adam_update1(pp[j], grad_times<DEV>(gg[j], gscale), mm[j], vv[j], h);
       V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
       if (pb) V4<bf16_t>::store(pb + i, pp);
     }
     const long t0 = c0 + ((c1 - c0) & ~3L);
     for (long k = t0 + threadIdx.x; k < c1; k += 256) {
       float pp = p[k], mm = m[k], vv = v[k];
-      adam_update1(pp, g[k] * gscale, mm, vv, h);
+      adam_update1(pp, grad_times<DEV>(g[k], gscale), mm, vv, h);
       p[k] = pp; m[k] = mm; v[k] = vv;
       if (pb) pb[k] = f32_to_bf16(pp);
     }
@@ -1795,14 +1870,26 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     while (s < s1 && seg_end[s] <= base + k) ++s;
     const AdamHyper h = G.h[seg_group[s] & (MUSE_ADAMW_MAX_GROUPS - 1)];
     float pp = p[k], mm = m[k], vv = v[k];
-    adam_update1(pp, g[k] * gscale, mm, vv, h);
+    adam_update1(pp, grad_times<DEV>(g[k], gscale), mm, vv, h);
     p[k] = pp; m[k] = mm; v[k] = vv;
     if (pb) pb[k] = f32_to_bf16(pp);
   }
 }
-extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
-                                      const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
-                                      int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
+                                                           const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
+                                                           AdamGroups G, float gscale, const int* __restrict__ skip) {
+  adamw_groups_body<false>(p, g, m, v, pb, n, base, seg_end, seg_group, nseg, G, gscale, skip, nullptr);
+}
+__global__ __launch_bounds__(256) void adamw_groups_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
+                                                               const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
+                                                               AdamGroups G, const float* __restrict__ sdev, const int* __restrict__ skip) {
+  adamw_groups_body<true>(p, g, m, v, pb, n, base, seg_end, seg_group, nseg, G, 0.f, skip, sdev);
+}
+static int adamw_flat_groups_launch(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base, const int64_t* seg_end,
+                                    const int32_t* seg_group, int32_t nseg, const float* group_hyper, int32_t ngroups, int32_t step,
+                                    float grad_scale, const float* scale_dev, const int32_t* skip, void* stream) {
   if (n <= 0) return 0;
   if (nseg < 1 || !seg_end || !seg_group) return MUSE_ERR_BAD_ARG;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
@@ -1810,15 +1897,33 @@ extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float*
   AdamGroups G;
   const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
   if (rc) return rc;
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, skip);
+  if (scale_dev)
+    hipLaunchKernelGGL(adamw_groups_dev_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, scale_dev, skip);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, skip);
   return (int)hipGetLastError();
+}
+extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                                      const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
+                                      int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
+  return adamw_flat_groups_launch(p, g, m, v, p_bf16, n, base, seg_end, seg_group, nseg, group_hyper, ngroups, step, grad_scale, nullptr, skip,
+                                  stream);
+}
+extern "C" int muse_adamw_flat_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
+                                          const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
+                                          int32_t ngroups, int32_t step, const float* scale_dev, const int32_t* skip, void* stream) {
+  if (!scale_dev) return MUSE_ERR_BAD_ARG;
+  return adamw_flat_groups_launch(p, g, m, v, p_bf16, n, base, seg_end, seg_group, nseg, group_hyper, ngroups, step, 0.f, scale_dev, skip,
+                                  stream);
 }
 // Multi-tensor form with groups: `table` is 7 x int64 per tensor {p, g, m, v, p_bf16 or 0, n, group | lo_plane_distance << 8}
 // (lo_plane_distance < 0: p_bf16 receives an IEEE-half copy).
-__global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                                 AdamGroups G, float gscale, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;       // (the f16 mode's overflow guard)
+template <bool DEV> __device__ __forceinline__ void adamw_multi_groups_body(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+                                                                 const AdamGroups& G, float gscale, const int* __restrict__ skip,
+                                                                 const float* __restrict__ sdev) {
+  ADAMW_PROLOGUE
   int lo = 0, hi = nt;
   while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
   const long* e = table + (long)lo * 7;
@@ -1839,7 +1944,7 @@ __global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __r
       float pp[4], gg[4], mm[4], vv[4];
       V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) adam_update1(pp[j], gg[j] * gscale, mm[j], vv[j], h);
+      for (int j = 0; j < 4; ++j) adam_update1(pp[j], grad_times<DEV>(gg[j], gscale), mm[j], vv[j], h);
       V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
       if (pb && half_copy) {
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -1858,7 +1963,7 @@ __global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __r
   const long s0 = vec ? base + ((end - base) & ~3L) : base;
   for (long i = s0 + threadIdx.x; i < end; i += 256) {
     float pp = p[i], mm = m[i], vv = v[i];
-    adam_update1(pp, g[i] * gscale, mm, vv, h);
+    adam_update1(pp, grad_times<DEV>(g[i], gscale), mm, vv, h);
     p[i] = pp; m[i] = mm; v[i] = vv;
     if (pb && half_copy) {
       ((_Float16*)pb)[i] = (_Float16)pp;
@@ -1869,16 +1974,40 @@ __global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __r
     }
   }
 }
-extern "C" int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                                       const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip,
-                                       void* stream) {
+__global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+                                                                 AdamGroups G, float gscale, const int* __restrict__ skip) {
+  adamw_multi_groups_body<false>(table, chunk_first, nt, G, gscale, skip, nullptr);
+}
+__global__ __launch_bounds__(256) void adamw_multi_groups_dev_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
+                                                                     AdamGroups G, const float* __restrict__ sdev,
+                                                                     const int* __restrict__ skip) {
+  adamw_multi_groups_body<true>(table, chunk_first, nt, G, 0.f, skip, sdev);
+}
+static int adamw_multi_groups_launch(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                                     const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const float* scale_dev,
+                                     const int32_t* skip, void* stream) {
   if (num_tensors <= 0 || num_chunks <= 0) return 0;
   AdamGroups G;
   const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
   if (rc) return rc;
-  hipLaunchKernelGGL(adamw_multi_groups_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
-                     num_tensors, G, grad_scale, skip);
+  if (scale_dev)
+    hipLaunchKernelGGL(adamw_multi_groups_dev_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
+                       num_tensors, G, scale_dev, skip);
+  else
+    hipLaunchKernelGGL(adamw_multi_groups_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
+                       num_tensors, G, grad_scale, skip);
   return (int)hipGetLastError();
+}
+extern "C" int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                                       const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip,
+                                       void* stream) {
+  return adamw_multi_groups_launch(table, chunk_first, num_tensors, num_chunks, group_hyper, ngroups, step, grad_scale, nullptr, skip, stream);
+}
+extern "C" int muse_adamw_multi_groups_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                                           const float* group_hyper, int32_t ngroups, int32_t step, const float* scale_dev,
+                                           const int32_t* skip, void* stream) {
+  if (!scale_dev) return MUSE_ERR_BAD_ARG;
+  return adamw_multi_groups_launch(table, chunk_first, num_tensors, num_chunks, group_hyper, ngroups, step, 0.f, scale_dev, skip, stream);
 }
 
 // f32 -> the two bf16 planes of the bf16x3 product scheme: hi = bf16(x), lo = bf16(x - hi) (x ~= hi + lo to 2^-16 relative); the

@@ -19,8 +19,8 @@ from .pipeline_muse import PipelineMuse, PipelineMuseInpainting
 from .sampling import get_mask_chedule
 from .unbuilt import MOVQ, PaellaVQModel
 from . import lr_schedulers, training_utils
-from .training import (FusedAdamW, GradReducer, TrainStep, cond_dropout, grouped_parameters, mask_or_random_replace_tokens,
-                       prepare_inputs_and_labels)
+from .training import (FusedAdamW, GradReducer, TrainStep, clip_grad_norm_, cond_dropout, grad_norms, grouped_parameters,
+                       mask_or_random_replace_tokens, prepare_inputs_and_labels)
 
-__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "GradReducer",
+__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "GradReducer", "clip_grad_norm_", "grad_norms",
            "TrainStep", "prepare_inputs_and_labels", "mask_or_random_replace_tokens", "cond_dropout", "grouped_parameters"]

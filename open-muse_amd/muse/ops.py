@@ -1581,17 +1581,28 @@ def soft_ce_bwd(logits, labels, soft, seq1, lse, psum, loss_out, grad_out, out_d
 
 # skip (every adamw_*): None, or the device int32 overflow counter of an "f16" backward pass - the kernel leaves parameters and moments
 # untouched when it is non-zero (training.FusedAdamW's guard)
-def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None):
-    require_gpu(p, g, m, v)
+# scale_dev (every adamw_*): None, or a device f32 (gradnorm_finalize's `scale`) the kernel multiplies the gradient by INSTEAD of
+# grad_scale (the muse_adamw_*_dev entry points: gradient clipping without a host round trip)
+def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None, scale_dev=None):
+    require_gpu(p, g, m, v, scale_dev)
     e0 = _prof_begin()
-    check(lib().muse_adamw_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
-                                beta2, eps, weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_flat")
+    if scale_dev is not None:
+        check(lib().muse_adamw_flat_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
+                                        beta2, eps, weight_decay, step, scale_dev.data_ptr(), ptr(skip), stream()), "muse_adamw_flat_dev")
+    else:
+        check(lib().muse_adamw_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
+                                    beta2, eps, weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_flat")
     _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
 
 
-def adamw_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None):
+def adamw_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None,
+                scale_dev=None):
     """one AdamW launch over a device-side table of tensors (muse_adamw_multi; training.FusedAdamW builds the table)"""
-    require_gpu(table, chunk_first)
+    require_gpu(table, chunk_first, scale_dev)
+    if scale_dev is not None:
+        check(lib().muse_adamw_multi_dev(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
+                                         weight_decay, step, scale_dev.data_ptr(), ptr(skip), stream()), "muse_adamw_multi_dev")
+        return
     check(lib().muse_adamw_multi(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
                                  weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_multi")
 
@@ -1615,13 +1626,20 @@ def _group_hyper(groups):
     return (ctypes.c_float * len(flat))(*flat)
 
 
-def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step, grad_scale=1.0, skip=None):
+def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step, grad_scale=1.0, skip=None, scale_dev=None):
     """AdamW on elements [base, base + p.numel()) of a flat buffer whose segments belong to different parameter groups
     (muse_adamw_flat_groups); p, g, m, v, p_bf16 are the slices starting at `base`; `groups`: torch param_groups-like dicts"""
-    require_gpu(p, g, m, v, seg_end, seg_group)
+    require_gpu(p, g, m, v, seg_end, seg_group, scale_dev)
     import ctypes
     hy = _group_hyper(groups)
     e0 = _prof_begin()
+    if scale_dev is not None:
+        check(lib().muse_adamw_flat_groups_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
+                                               seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()),
+                                               ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), scale_dev.data_ptr(), ptr(skip),
+                                               stream()), "muse_adamw_flat_groups_dev")
+        _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
+        return
     check(lib().muse_adamw_flat_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
                                        seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()),
                                        ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
@@ -1629,14 +1647,63 @@ def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step
     _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
 
 
-def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step, grad_scale=1.0, skip=None):
+def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step, grad_scale=1.0, skip=None, scale_dev=None):
     """muse_adamw_multi with a group column in the table (7 x int64 per tensor)"""
-    require_gpu(table, chunk_first)
+    require_gpu(table, chunk_first, scale_dev)
     import ctypes
     hy = _group_hyper(groups)
+    if scale_dev is not None:
+        check(lib().muse_adamw_multi_groups_dev(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
+                                                ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), scale_dev.data_ptr(), ptr(skip),
+                                                stream()), "muse_adamw_multi_groups_dev")
+        return
     check(lib().muse_adamw_multi_groups(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
                                         ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
           "muse_adamw_multi_groups")
+
+
+# ---- gradient clipping by global L2 norm / per-parameter gradient norms (csrc/gradnorm.hip; training.GradNorm drives these) -------------
+GRADNORM_CHUNK = 4096     # elements per f64 partial, counted from each parameter's own start (GN_CHUNK of csrc/gradnorm.hip, the AdamW chunk)
+
+
+def gradnorm_flat(g_flat, base, n, ptab_host, chunk_first_host, ptab, chunk_first, slab):
+    """sums of squares of the parameters inside [base, base + n) of the flat f32 gradient buffer `g_flat` (the WHOLE buffer) -> their
+    chunks of `slab` (f64).  ptab {offset, n} int64 rows and chunk_first int32, on the device and (`*_host`) on the host.  A range that
+    does not begin at a parameter or cuts one raises (MUSE_ERR_BAD_ARG)."""
+    require_gpu(g_flat, ptab, chunk_first, slab)
+    if ptab_host.is_cuda or chunk_first_host.is_cuda:
+        raise _hip.MuseHipError("gradnorm_flat: ptab_host / chunk_first_host are host tensors")
+    e0 = _prof_begin()
+    check(lib().muse_gradnorm_flat(g_flat.data_ptr(), int(base), int(n), ptab_host.data_ptr(), chunk_first_host.data_ptr(), ptab.data_ptr(),
+                                   chunk_first.data_ptr(), int(ptab_host.shape[0]), slab.data_ptr(), stream()), "muse_gradnorm_flat")
+    _prof_end(e0, "gradnorm", 4.0 * n, "byte")
+
+
+def gradnorm_multi(table, chunk_first, num_tensors, num_chunks, slab):
+    """the same over FusedAdamW's device pointer table ({p, g, m, v, shadow, n[, group]} rows): every tensor in one launch"""
+    require_gpu(table, chunk_first, slab)
+    check(lib().muse_gradnorm_multi(table.data_ptr(), int(table.shape[1]), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
+                                    slab.data_ptr(), stream()), "muse_gradnorm_multi")
+
+
+def gradnorm_finalize(slab, chunk_first, num_tensors, psum, grad_scale, max_norm, out):
+    """slab -> out (f32 [3 + num_tensors]): norm, coef = min(1, max_norm / (norm + 1e-6)), scale = grad_scale * coef, per-parameter norms"""
+    require_gpu(slab, chunk_first, psum, out)
+    check(lib().muse_gradnorm_finalize(slab.data_ptr(), chunk_first.data_ptr(), int(num_tensors), psum.data_ptr(), float(grad_scale),
+                                       float(max_norm), out.data_ptr(), stream()), "muse_gradnorm_finalize")
+
+
+def grad_scale_flat_(g, scale):
+    """g *= scale (a device f32) in place"""
+    require_gpu(g, scale)
+    check(lib().muse_grad_scale_flat(g.data_ptr(), g.numel(), scale.data_ptr(), stream()), "muse_grad_scale_flat")
+
+
+def grad_scale_multi_(table, chunk_first, num_tensors, num_chunks, scale):
+    """every gradient of the pointer table *= scale (a device f32) in place, one launch"""
+    require_gpu(table, chunk_first, scale)
+    check(lib().muse_grad_scale_multi(table.data_ptr(), int(table.shape[1]), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
+                                      scale.data_ptr(), stream()), "muse_grad_scale_multi")
 
 
 def cast_to_bf16(src, dst=None):

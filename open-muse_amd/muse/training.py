@@ -184,15 +184,185 @@ def _owner_of(params):
     return owner
 
 
+def _flat_grad_checked(model, params, who="FusedAdamW"):
+    """the flat gradient buffer, after making sure it really holds this step's gradients: every p.grad must be the
+    parameter's view of it (what backward writes with model.direct_grad); a gradient that lives elsewhere (autograd-
+    returned with direct_grad=False, or assigned by the user) is copied in."""
+    g = model.flat_grads()
+    for p, gv in zip(params, model._grad_views):
+        if not p.requires_grad:
+            raise MuseHipError(f"{who} steps the whole flat buffer: a frozen parameter (requires_grad=False) is not supported")
+        if p.grad.data_ptr() != gv.data_ptr():
+            if p.grad.shape != gv.shape:
+                raise MuseHipError(f"{who}: gradient shape differs from its parameter")
+            gv.copy_(p.grad)
+            p.grad = gv
+    return g
+
+
+class _FlatNormState:
+    """what the gradient-norm kernels need for a model with a flat gradient buffer, built once: the {offset, n} table of its
+    parameters and the chunk prefix sums (on the host for muse_gradnorm_flat's range check, on the device for the kernels) and the
+    slab of f64 partials - one per (parameter, 4096-element chunk), then the finalize kernel's scratch (one per parameter and its
+    zeroed ticket)."""
+
+    def __init__(self, model):
+        flat = model.flat_params()
+        order = model._param_order()
+        sizes = [p.numel() for p in order]
+        first = [0]
+        for n in sizes:
+            first.append(first[-1] + (n + ops.GRADNORM_CHUNK - 1) // ops.GRADNORM_CHUNK)
+        self.key = (flat.device, tuple(model._offsets), tuple(sizes))
+        self.ptab_host = torch.tensor([[o, n] for o, n in zip(model._offsets, sizes)], dtype=torch.int64)
+        self.first_host = torch.tensor(first, dtype=torch.int32)
+        self.ptab, self.first = self.ptab_host.to(flat.device), self.first_host.to(flat.device)
+        self.nt, self.nchunks = len(sizes), first[-1]
+        self.slab = torch.zeros(self.nchunks + self.nt + 1, dtype=torch.float64, device=flat.device)
+
+    @staticmethod
+    def of(model):
+        st = model.__dict__.get("_muse_gradnorm")
+        flat = model.flat_params()
+        if st is None or st.key != (flat.device, tuple(model._offsets), tuple(p.numel() for p in model._param_order())):
+            st = model.__dict__["_muse_gradnorm"] = _FlatNormState(model)
+        return st
+
+    def accumulate(self, g, begin, end):
+        """the parameters inside [begin, end) of the flat gradient buffer g -> their chunks of the slab (current stream)"""
+        ops.gradnorm_flat(g, begin, end - begin, self.ptab_host, self.first_host, self.ptab, self.first, self.slab)
+
+    def finish(self, g, covered, grad_scale, max_norm):
+        """cover what `covered` ([(begin, end), ...], accumulated earlier) left out, then the finalize launch -> out (f32 [3 + nt]:
+        norm, coef, scale, per-parameter norms)"""
+        pos = 0
+        for b, e in sorted(covered):
+            if b > pos:
+                self.accumulate(g, pos, b)
+            pos = max(pos, e)
+        if pos < g.numel():
+            self.accumulate(g, pos, g.numel())
+        out = torch.empty(3 + self.nt, dtype=torch.float32, device=g.device)
+        ops.gradnorm_finalize(self.slab, self.first, self.nt, self.slab[self.nchunks:], grad_scale, max_norm, out)
+        return out
+
+
+def _multi_norm(table, chunk_first, nt, nchunks, slab, grad_scale, max_norm):
+    """the multi-tensor form: sums of squares over a FusedAdamW-style pointer table, then the finalize launch -> out"""
+    if slab is None or slab.numel() != nchunks + nt + 1 or slab.device != table.device:
+        slab = torch.zeros(nchunks + nt + 1, dtype=torch.float64, device=table.device)   # (partials, per-parameter sums, the zeroed ticket)
+    ops.gradnorm_multi(table, chunk_first, nt, nchunks, slab)
+    out = torch.empty(3 + nt, dtype=torch.float32, device=table.device)
+    ops.gradnorm_finalize(slab, chunk_first, nt, slab[nchunks:], grad_scale, max_norm, out)
+    return out, slab
+
+
+def _grad_table(grads):
+    """device pointer table in muse_adamw_multi's layout (only the gradient pointer and n filled) for a list of gradient tensors
+    -> (table, chunk_first, nchunks).  One (pageable) host -> device copy: the optimizer's own path keeps its pinned staging."""
+    rows, first = [], [0]
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise MuseHipError("muse.clip_grad_norm_ / grad_norms: gradients must be contiguous float32 tensors")
+        rows.append((0, g.data_ptr(), 0, 0, 0, g.numel()))
+        first.append(first[-1] + (g.numel() + ops.GRADNORM_CHUNK - 1) // ops.GRADNORM_CHUNK)
+    dev = grads[0].device
+    return torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(first, dtype=torch.int32).to(dev), first[-1]
+
+
+def _norm_target(parameters_or_model):
+    """-> (flat-buffer model or None, the parameters that have a gradient, in the order of the norms)"""
+    if isinstance(parameters_or_model, torch.Tensor):
+        parameters_or_model = [parameters_or_model]
+    model = parameters_or_model if hasattr(parameters_or_model, "parameters") else None
+    params = list(model.parameters() if model is not None else parameters_or_model)
+    owner = _owner_of(params) if params else None
+    if owner is not None:
+        theirs = owner._param_order()
+        if len(params) == len(theirs) and {id(q) for q in params} == {id(q) for q in theirs} and owner._flat_ok() \
+                and all(q.grad is not None for q in theirs):
+            return owner, theirs
+    return None, [q for q in params if q.grad is not None]
+
+
+def _run_norm(parameters_or_model, max_norm, scale_in_place):
+    """-> (out of the finalize launch or None when there is no gradient, the parameters the per-parameter norms belong to)"""
+    owner, params = _norm_target(parameters_or_model)
+    if not params:
+        return None, params
+    if owner is not None:
+        g = _flat_grad_checked(owner, params, "muse.clip_grad_norm_")
+        out = _FlatNormState.of(owner).finish(g, [], 1.0, max_norm)
+        if scale_in_place:
+            ops.grad_scale_flat_(g, out[1:2])
+            ops._touched(g)
+        return out, params
+    grads = [q.grad for q in params]
+    ops.require_gpu(*grads)
+    table, first, nchunks = _grad_table(grads)
+    out, _ = _multi_norm(table, first, len(grads), nchunks, None, 1.0, max_norm)
+    if scale_in_place:
+        ops.grad_scale_multi_(table, first, len(grads), nchunks, out[1:2])
+        for g in grads:
+            ops._touched(g)
+    return out, params
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters_or_model, max_norm, return_coef=False):
+    """Drop-in for `accelerator.clip_grad_norm_(model.parameters(), max_norm)` / `torch.nn.utils.clip_grad_norm_` (norm_type 2;
+    training/train_muse.py:758-759) for loops that keep the reference's statement order or another optimizer: the global L2 norm of
+    the gradients by the HIP norm kernels (f64 sums, deterministic), then `grad *= min(1, max_norm / (norm + 1e-6))` in place by one
+    more launch (applied also when the coefficient is 1, as torch does).  No device-to-host copy.  Takes a model or its parameters:
+    a muse.MaskGitTransformer's flat gradient buffer in one piece, ordinary tensors (muse.MaskGiTUViT) through one pointer table.
+    -> the norm before clipping, a 0-dim device tensor (with `return_coef`: (norm, coefficient)).  With muse.FusedAdamW prefer
+    `FusedAdamW(max_grad_norm=...)`: same result bit for bit, without the write pass over the gradient."""
+    out, params = _run_norm(parameters_or_model, float(max_norm), True)
+    if out is None:
+        z = torch.zeros((), dtype=torch.float32)
+        return (z, torch.ones_like(z)) if return_coef else z
+    return (out[0], out[1]) if return_coef else out[0]
+
+
+@torch.no_grad()
+def grad_norms(model_or_parameters):
+    """L2 norm of every gradient -> f32 device tensor [number of parameters that have a gradient] (order: the model's flat-buffer
+    order for a flat-buffer model with all gradients present - see named_grad_norms -, else the order given): one launch chain, no
+    device-to-host copy."""
+    out, params = _run_norm(model_or_parameters, float("inf"), False)
+    if out is None:
+        return torch.zeros(0, dtype=torch.float32)
+    return out[3:]
+
+
+@torch.no_grad()
+def named_grad_norms(model):
+    """-> ([names], f32 device tensor of their gradients' L2 norms), for the parameters that have a gradient"""
+    out, params = _run_norm(model, float("inf"), False)
+    names = {id(p): n for n, p in model.named_parameters()}
+    if out is None:
+        return [], torch.zeros(0, dtype=torch.float32)
+    return [names[id(p)] for p in params], out[3:]
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW (decoupled weight decay, torch.optim.AdamW numerics) as ONE kernel launch over the model's flat f32
     parameter / gradient buffers; also refreshes the bf16 compute copy of the weights in the same pass.
 
     Drop-in for `optimizer_cls(model.parameters(), lr=..., betas=..., weight_decay=..., eps=...)`.  `state_dict()` /
     `load_state_dict()` use torch.optim.AdamW's layout ({"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups"}),
-    so optimizer checkpoints written by the reference's `adamw` choice load here and vice versa."""
+    so optimizer checkpoints written by the reference's `adamw` choice load here and vice versa.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    `max_grad_norm` (also an attribute; None = off): clip the gradient by its global L2 norm inside the step - the semantics of
+    `accelerator.clip_grad_norm_(model.parameters(), max_grad_norm)` right before `optimizer.step()` (training/train_muse.py:758-761):
+    step() = norm kernels (for whatever begin_norm_in_backward / begin_norm_in_reducer have not already delivered) -> one finalize
+    launch -> ONE AdamW launch that reads `grad_scale * min(1, max_grad_norm / (norm + 1e-6))` from device memory.  No device-to-host
+    copy, no stream synchronisation.  `p.grad` is left UNSCALED (that write pass is what is saved): code that reads the gradients
+    after step() sees the unclipped ones - use muse.clip_grad_norm_ where the clipped gradient itself is needed.  After the step
+    `last_grad_norm` (the norm before clipping, of the gradient times `grad_scale`) and `last_clip_coef` are 0-dim device tensors.
+    It is not a param_groups default and does not enter state_dict(): checkpoints keep torch.optim.AdamW's layout."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         # Parameter groups: `params` may be the list of dicts training/train_muse.py:425-445 builds (weight decay on the matrices,
@@ -217,6 +387,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ranges_done = self._ranges_done_live = None                        # (step, [(begin, end), ...]) applied inside backward
         self._upd_stream, self._upd_used = None, False                           # stream of the per-bucket update (begin_step_in_reducer)
         self.grad_scale = 1.0   # multiplied into the gradient inside the kernel (GradReducer sets 1/world for SUM reductions)
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm = self.last_clip_coef = None
+        self._norm_done = self._norm_live = None     # (step, [(begin, end), ...]) whose sums of squares backward already delivered
+        self._norm_slab = None                       # per-tensor mode: the slab of f64 partials
 
     def _all_params(self):
         """every parameter, in torch.optim's state-dict order (group by group)"""
@@ -240,21 +414,6 @@ class FusedAdamW(torch.optim.Optimizer):
                          torch.tensor(gids, dtype=torch.int32, device=flat.device), tuple(model._offsets))
         return self._seg_dev[0], self._seg_dev[1]
 
-    def _flat_grad_checked(self, model, params):
-        """the flat gradient buffer, after making sure it really holds this step's gradients: every p.grad must be the
-        parameter's view of it (what backward writes with model.direct_grad); a gradient that lives elsewhere (autograd-
-        returned with direct_grad=False, or assigned by the user) is copied in."""
-        g = model.flat_grads()
-        for p, gv in zip(params, model._grad_views):
-            if not p.requires_grad:
-                raise MuseHipError("FusedAdamW steps the whole flat buffer: a frozen parameter (requires_grad=False) is not supported")
-            if p.grad.data_ptr() != gv.data_ptr():
-                if p.grad.shape != gv.shape:
-                    raise MuseHipError("FusedAdamW: gradient shape differs from its parameter")
-                gv.copy_(p.grad)
-                p.grad = gv
-        return g
-
     @torch.no_grad()
     def step(self, closure=None):
         self._check_not_partial()
@@ -273,15 +432,23 @@ class FusedAdamW(torch.optim.Optimizer):
             if all(p.grad is None for p in order):
                 return loss  # nothing to do before the first backward (torch skips None grads)
             raise MuseHipError("FusedAdamW: some parameters have no gradient; the flat step needs all of them")
-        g = self._flat_grad_checked(model, order)
+        g = _flat_grad_checked(model, order)
         self._ensure_flat_state(flat)
         self._step += 1
         shadow = model._flat_c if model._flat_c is not None and model._flat_c.device == flat.device else None
         done = self._ranges_done
         self._ranges_done = None
+        normed, self._norm_done = self._norm_done, None
         guards, skip = self._f16_guard_on(flat.device)     # ("f16" mode: as in _step_per_tensor - the update is skipped on the device on overflow)
         try:
-            if done is not None and done[0] == self._step:
+            if self.max_grad_norm is not None:
+                # clipping: sums of squares of what backward has not delivered, the finalize launch, ONE update that reads the scale
+                # from the device (on an "f16" step that overflowed the norm is simply non-finite and the guard skips the update)
+                covered = normed[1] if normed is not None and normed[0] == self._step else []
+                out = _FlatNormState.of(model).finish(g, covered, float(self.grad_scale), float(self.max_grad_norm))
+                self.last_grad_norm, self.last_clip_coef = out[0], out[1]
+                self._apply(model, 0, flat.numel(), shadow, skip, scale_dev=out[2:3])
+            elif done is not None and done[0] == self._step:
                 # backward already applied this step's update range by range (begin_step_in_backward); cover what it did not report
                 covered = sorted(done[1])
                 pos = 0
@@ -298,11 +465,14 @@ class FusedAdamW(torch.optim.Optimizer):
         model._note_shadow_refreshed(shadow is not None)
         return loss
 
-    def _apply(self, model, b, e, shadow, skip=None):
+    def _apply(self, model, b, e, shadow, skip=None, scale_dev=None):
         flat, g = model.flat_params(), model.flat_grads()
         # (the guard only when there is one: an unguarded update stays the call it always was, so a stand-in for ops.adamw_flat /
-        #  adamw_flat_groups written without the keyword - a host-logic test, a CPU restatement of the kernel - keeps working)
+        #  adamw_flat_groups written without the keyword - a host-logic test, a CPU restatement of the kernel - keeps working; the
+        #  same for the device-side gradient factor of a clipped step)
         guard = {} if skip is None else {"skip": skip}
+        if scale_dev is not None:
+            guard["scale_dev"] = scale_dev
         if len(self.param_groups) > 1:
             seg_end, seg_group = self._segments(model)
             ops.adamw_flat_groups(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], b,
@@ -327,8 +497,8 @@ class FusedAdamW(torch.optim.Optimizer):
         clipping, no gradient accumulation, no all-reduce (muse.TrainStep checks this and arms it).  Never for a model in the "f16"
         compute mode: its update waits for the whole backward pass's overflow guard (step())."""
         self._check_not_partial()
-        if model.__dict__.get("_f32_f16", False):
-            return False
+        if model.__dict__.get("_f32_f16", False) or self.max_grad_norm is not None:
+            return False                      # (clipping: no update before the last gradient exists - begin_norm_in_backward)
         flat = model.flat_params()
         self._ensure_flat_state(flat)
         if any((o * 4) % 16 for o in model._offsets):
@@ -371,7 +541,7 @@ class FusedAdamW(torch.optim.Optimizer):
         bit for bit, but measured much slower at one rank: 69.6 vs 61.5 ms per step, profiles/r02_ab_dp1_updstream_*.json - the
         low-priority update is starved until the end of the step and then serialises).  Same validity conditions as
         begin_step_in_backward; call end_step_in_reducer after reducer.finish()."""
-        if model.__dict__.get("_f32_f16", False):
+        if model.__dict__.get("_f32_f16", False) or self.max_grad_norm is not None:
             return False
         flat = model.flat_params()
         self._ensure_flat_state(flat)
@@ -418,6 +588,62 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ranges_done, self._ranges_done_live = self._ranges_done_live, None
         if failed and self._ranges_done is not None and self._ranges_done[1]:
             self._partial_step = True
+
+    # ---- clipping: the sums of squares overlapped with backward ---------------------------------------------------------------------
+    def begin_norm_in_backward(self, model):
+        """With `max_grad_norm` set the update cannot start before the last gradient exists, but the norm can be accumulated where the
+        update runs otherwise: every time backward reports a finished range of the flat gradient buffer (model.grad_ready_hook, on the
+        weight-gradient stream) the sum-of-squares kernel runs on that range, and step() is left with the ranges that were never
+        reported, the finalize launch and the update.  Ranges are whole parameters, partials go to fixed slots of a slab: the norm is
+        bit-identical to the one step() alone computes.  Arm it around the LAST backward before step() (gradient accumulation: the
+        earlier micro-batches' backward runs unarmed); pair with end_norm_in_backward.  Nothing is applied inside backward, so a
+        backward that raises leaves the step retryable - unlike begin_step_in_backward."""
+        self._check_not_partial()
+        if self.max_grad_norm is None or self._model is None or self._model() is not model or model.__dict__.get("_f32_f16", False):
+            return False                      # ("f16" compute mode: as for the update, everything waits for the whole backward pass)
+        st = _FlatNormState.of(model)
+        self._norm_live = (self._step + 1, [])
+        self._direct_grad_before = model.direct_grad
+
+        def hook(begin, end):
+            live = self._norm_live
+            if live is None or end <= begin:
+                return
+            st.accumulate(model.flat_grads(), begin, end)
+            live[1].append((begin, end))
+        model.direct_grad = True
+        model.grad_ready_hook = hook
+        return True
+
+    def end_norm_in_backward(self, model, failed=False):
+        """`failed`: backward raised - what it had accumulated is dropped, step() takes the whole norm itself"""
+        model.grad_ready_hook = None
+        model.direct_grad = getattr(self, "_direct_grad_before", model.direct_grad)
+        self._norm_done, self._norm_live = (None if failed else self._norm_live), None
+
+    def begin_norm_in_reducer(self, model, reducer):
+        """The data-parallel form: the sum-of-squares kernel runs on each bucket right behind its all-reduce (GradReducer.post_reduce),
+        on the reducer's stream, so the norm is that of the averaged gradient - the same bytes on every rank, hence the same norm and
+        coefficient bit for bit without another collective.  Under reducer.no_sync() no bucket is reduced and nothing is accumulated;
+        the synchronising backward reports the accumulated gradient.  Call end_norm_in_reducer after reducer.finish()."""
+        self._check_not_partial()
+        if self.max_grad_norm is None or self._model is None or self._model() is not model or model.__dict__.get("_f32_f16", False):
+            return False
+        st = _FlatNormState.of(model)
+        self._norm_live = (self._step + 1, [])
+
+        def hook(begin, end):
+            live = self._norm_live
+            if live is None or end <= begin:
+                return
+            st.accumulate(model.flat_grads(), begin, end)
+            live[1].append((begin, end))
+        reducer.post_reduce = hook
+        return True
+
+    def end_norm_in_reducer(self, reducer, failed=False):
+        reducer.post_reduce = None
+        self._norm_done, self._norm_live = (None if failed else self._norm_live), None
 
     def _ensure_flat_state(self, flat):
         if self._m is None:
@@ -500,14 +726,20 @@ class FusedAdamW(torch.optim.Optimizer):
         # (the host does not know about the skip when it happens: self._step advances anyway, so the bias corrections of the following
         #  updates are those of one step later - a factor that tends to 1)
         guards, skip = self._f16_guard_on(dev)
+        clip = {}
+        if self.max_grad_norm is not None:      # the norm over the same pointer table, then the update reads the scale from the device
+            out, self._norm_slab = _multi_norm(self._table, self._chunk_first, len(rows), self._nchunks, self._norm_slab,
+                                               float(self.grad_scale), float(self.max_grad_norm))
+            self.last_grad_norm, self.last_clip_coef = out[0], out[1]
+            clip = {"scale_dev": out[2:3]}
         try:
             if multi:
                 ops.adamw_multi_groups(self._table, self._chunk_first, len(rows), self._nchunks, self.param_groups, self._step,
-                                       grad_scale=float(self.grad_scale), skip=skip)
+                                       grad_scale=float(self.grad_scale), skip=skip, **clip)
             else:
                 grp = self.param_groups[0]
                 ops.adamw_multi(self._table, self._chunk_first, len(rows), self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
-                                grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale), skip=skip)
+                                grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale), skip=skip, **clip)
         finally:
             self._f16_guard_off(guards)
         return loss
@@ -956,11 +1188,21 @@ class TrainStep:
 
     `use_soft_code_target` / `soft_code_temp` / `use_stochastic_code` (config.training, :364-367, :421-424): the tokens and the soft
     targets come from `vq_model.get_soft_code`, and the step is `logits = model(input_ids)`, `soft_target_cross_entropy(logits,
-    labels, soft_targets)`, backward, AdamW (class-conditional MaskGitTransformer only).  The prefetch then carries both."""
+    labels, soft_targets)`, backward, AdamW (class-conditional MaskGitTransformer only).  The prefetch then carries both.
+
+    `max_grad_norm` (config.training.max_grad_norm, training/train_maskgit_imagenet.py:435-436): clip the gradient by its global L2
+    norm before the update (muse.FusedAdamW's `max_grad_norm`, which this sets).  The sums of squares are then accumulated where the
+    update runs otherwise - inside backward, or behind each bucket's all-reduce - and step() finalizes and updates; the update itself
+    cannot overlap backward any more (it needs the last gradient's norm)."""
 
     def __init__(self, vq_model, model, optimizer, reducer: Optional[GradReducer] = None, label_smoothing: float = 0.0,
                  min_masking_rate: float = 0.0, use_soft_code_target: bool = False, soft_code_temp: float = 1.0,
-                 use_stochastic_code: bool = False):
+                 use_stochastic_code: bool = False, max_grad_norm: Optional[float] = None):
+        if max_grad_norm is not None:
+            if not isinstance(optimizer, FusedAdamW):
+                raise MuseHipError("TrainStep(max_grad_norm=...) clips inside muse.FusedAdamW's step; with another optimizer call "
+                                   "muse.clip_grad_norm_ between backward and step in a loop of your own")
+            optimizer.max_grad_norm = float(max_grad_norm)
         self.vq_model, self.model, self.optimizer, self.reducer = vq_model, model, optimizer, reducer
         self.label_smoothing, self.min_masking_rate = label_smoothing, min_masking_rate
         self.use_soft_code_target, self.soft_code_temp = bool(use_soft_code_target), float(soft_code_temp)
@@ -1054,12 +1296,20 @@ class TrainStep:
             loss = soft_target_cross_entropy(logits, labels, soft)
         else:
             _, loss = self.model(input_ids=input_ids, labels=labels, label_smoothing=self.label_smoothing)
+        # clipping (FusedAdamW.max_grad_norm): the sums of squares are accumulated where the update would run - the update waits for step()
+        clip = isinstance(self.optimizer, FusedAdamW) and self.optimizer.max_grad_norm is not None
+        flat_model = hasattr(self.model, "grad_ready_hook") and hasattr(self.model, "flat_grads")
+        normed = (clip and self.optimizer_in_backward and self.reducer is None and flat_model
+                  and self.optimizer.begin_norm_in_backward(self.model))
+        normed_r = (clip and not normed and self.optimizer_in_reducer and self.reducer is not None
+                    and getattr(self.reducer, "_flat_mode", False) and self.reducer.model is self.model
+                    and self.optimizer.begin_norm_in_reducer(self.model, self.reducer))
         # AdamW inside backward (FusedAdamW.begin_step_in_backward): only when nothing sits between the two - no reducer here
-        armed = (self.optimizer_in_backward and self.reducer is None and isinstance(self.optimizer, FusedAdamW)
+        armed = (not clip and self.optimizer_in_backward and self.reducer is None and isinstance(self.optimizer, FusedAdamW)
                  and getattr(self.model, "wgrad_stream", False) and hasattr(self.model, "grad_ready_hook")
                  and self.model._resolve_cd() == torch.bfloat16 and self.optimizer.begin_step_in_backward(self.model))
         # ... and with a reducer: AdamW on each bucket right behind its all-reduce, on the reducer's stream
-        armed_r = (not armed and self.optimizer_in_reducer and self.reducer is not None and getattr(self.reducer, "_flat_mode", False)
+        armed_r = (not clip and not armed and self.optimizer_in_reducer and self.reducer is not None and getattr(self.reducer, "_flat_mode", False)
                    and self.reducer.model is self.model and isinstance(self.optimizer, FusedAdamW) and loss.is_cuda
                    and self.model._resolve_cd() == torch.bfloat16 and self.optimizer.begin_step_in_reducer(self.model, self.reducer))
         failed = True
@@ -1073,6 +1323,10 @@ class TrainStep:
                 self.optimizer.end_step_in_backward(self.model, failed=failed)
             if armed_r:
                 self.optimizer.end_step_in_reducer(self.reducer, failed=failed)
+            if normed:
+                self.optimizer.end_norm_in_backward(self.model, failed=failed)
+            if normed_r:
+                self.optimizer.end_norm_in_reducer(self.reducer, failed=failed)
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
         return loss.detach(), mask_prob

@@ -96,3 +96,19 @@ def token_probability_distributions_per_percent_masked_bucket(logits, input_ids,
         first_masked = probs[b][input_ids[b] == mask_id][0]
         rows += [{"bucket": b, "masked_pixel_prob": p} for p in first_masked.cpu().numpy()]
     return pd.DataFrame(rows)
+
+
+@torch.no_grad()
+def log_grad_norm(model):
+    """training/train_muse.py:1309-1314 (`log_grad_norm`, every `experiment.log_grad_norm_every` steps) without its one norm and one
+    `.item()` per parameter: -> {"grad_norm/" + name: ||grad||_2 / grad.numel()} for every parameter that has a gradient - the
+    reference's formula (:1313) -, all norms from one launch chain of the HIP norm kernels and ONE device-to-host copy.  Hand the
+    dictionary to `accelerator.log(..., step=global_step)`.  Call it where the reference does, between backward and
+    `optimizer.zero_grad()`."""
+    from .training import named_grad_norms
+    names, norms = named_grad_norms(model)
+    if not names:
+        return {}
+    numel = {n: p.numel() for n, p in model.named_parameters()}
+    values = norms.tolist()                       # the one device-to-host copy
+    return {"grad_norm/" + n: v / numel[n] for n, v in zip(names, values)}
