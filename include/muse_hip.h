@@ -489,6 +489,14 @@ int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale, const floa
                                const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
                                int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
                                void* stream);
+/* muse_conv2d_nhwc_gn_split2 + F.avg_pool2d(2, 2) of its output in one kernel (the 2 x 2 average is taken in the convolution's epilogue:
+ * a quarter of the stores, no pooling pass).  out [batch, H/2, W/2, Cout] f32, the same bits as muse_avgpool2x2_nhwc_stats of the
+ * un-pooled output; residual stays [batch, H, W, Cout]; gn_partial (optional): [batch, H * W / 256, gn_groups, 2] f64 sums of the POOLED
+ * values, one chunk per convolution tile - muse_groupnorm_scale_shift with nchunk = H * W / 256, HW = (H / 2) * (W / 2). */
+int muse_conv2d_nhwc_gn_split2_pool(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
+                                    const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
+                                    int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
+                                    void* stream);
 int muse_groupnorm_scale_shift(const double* partial, int32_t nchunk, const float* gamma, const float* beta, float* scale,
                                float* shift, int32_t batch, int32_t HW, int32_t C, int32_t groups, float eps, void* stream);
 /* Encoder.conv_in (muse/modeling_maskgit_vqgan.py:175; taming :380): 3x3, padding 1, Cin <= 4 image channels -> Cout, as a direct
@@ -498,6 +506,10 @@ int muse_groupnorm_scale_shift(const double* partial, int32_t nchunk, const floa
  * the `partial` / nchunk = H a following GroupNorm consumes.  Cout % 4 == 0, Cout / 4 divides 256. */
 int muse_conv_in_direct(const float* x, const float* w4, const float* bias, float* out, double* gn_partial, int32_t gn_groups,
                         int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cpad, int32_t Cout, void* stream);
+/* The same convolution reading the image as it arrives: x [batch, Cin, H, W] f32 contiguous (NCHW), no channel-padded NHWC copy.
+ * Output and gn_partial are the same bits as muse_nchw_to_nhwc + muse_conv_in_direct. */
+int muse_conv_in_direct_nchw(const float* x, const float* w4, const float* bias, float* out, double* gn_partial, int32_t gn_groups,
+                             int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* stream);
 /* Decoder.conv_out behind norm_out + swish (muse/modeling_maskgit_vqgan.py:236-240; hidden_channels -> 3 image channels) as ONE
  * direct exact-f32 convolution: x [B, H, W, C] f32 is normalised with the per-image affine form of the GroupNorm (scale / shift
  * [B, C] f32 from muse_groupnorm_scale_shift), activated (SiLU) and convolved 3x3 / padding 1 (zero padding after the activation)

@@ -332,7 +332,11 @@ __device__ long* g_conv_ts = nullptr;
 // top-of-tap wait of tap s+2 leaves only tap s+1's operations outstanding - with the arithmetic of gn_apply_split8_kernel
 // (vqgan.hip; same bits) spread over that tap's MFMA slots, and written to the slab buffer in the layout the plane DMA produces.
 // Saves the write and the re-read of both planes (8 of the 12 bytes per element the unfused pair moves) and a launch.
-template <bool GN>
+// POOL = true: the epilogue stores the 2 x 2 average of the tile (F.avg_pool2d(2, 2) of the output, DownsamplingBlock with
+// resample_with_conv = False) instead of the tile: out is [B, H/2, W/2, N] and the GroupNorm partials are those of the POOLED values.
+// Every 2 x 2 window lies inside one 16 x 16 patch; the full-resolution values and the order of the three adds are those of the
+// un-pooled epilogue followed by avgpool_stats_kernel (vqgan.hip): same bits, a quarter of the stores and no second pass.
+template <bool GN, bool POOL = false>
 __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   CDMA_TS(0)
@@ -641,7 +645,36 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
   constexpr int NIT = (BM * 32) / NT;   // 16 chunks of 16 bytes per thread: patch row `it`, pixel rbase
   const int col = (threadIdx.x & 31) * 4, n = n0 + col, rbase = threadIdx.x >> 5;
   const long pix0 = ((long)img * H + y0) * W + x0 + rbase;
-  if (n < p.N) {
+  if constexpr (POOL) {
+    // 8 x 8 pooled pixels x 32 channel quads = 4 items per thread: pooled pixel (qy0 + 2k, qx), k = 0..3, i.e. the windows at patch
+    // rows 2 * qy0 + 4k.  The residual is read at full resolution: 16 loads per thread, all in flight before the first store.
+    const int qx = rbase & 7, qy0 = rbase >> 3, Wo = W >> 1;
+    const long pixf = ((long)img * H + y0 + 2 * qy0) * W + x0 + 2 * qx;
+    const long pixo = ((long)img * (H >> 1) + (y0 >> 1) + qy0) * Wo + (x0 >> 1) + qx;
+    if (n < p.N) {
+      f32x4 rv[NIT];
+      if (p.residual) {
+#pragma unroll
+        for (int it = 0; it < NIT; ++it)   // it = 4k + 2dy + dx
+          rv[it] = *(const f32x4*)(p.residual + (pixf + (long)(4 * (it >> 2) + ((it >> 1) & 1)) * W + (it & 1)) * p.N + n);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        f32x4 v[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          v[d] = *(const f32x4*)(smem + ((2 * qy0 + 4 * k + (d >> 1)) * 16 + 2 * qx + (d & 1)) * CST + col * 4);
+          if (p.residual) v[d] += rv[4 * k + d];
+        }
+        const f32x4 w = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;   // avgpool_stats_kernel's order
+        *(f32x4*)(p.out + (pixo + (long)(2 * k) * Wo) * p.N + n) = w;
+        if (p.gn_partial) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
+        }
+      }
+    }
+  } else if (n < p.N) {
     f32x4 rv[NIT];
     if (p.residual) {
 #pragma unroll
@@ -710,7 +743,9 @@ static_assert(P_BBASE + 3 * BSTAGE == P_BUF1 && P_BUF1 + SLAB <= P_LDS_BYTES && 
 // SiLU + hi / lo split are applied on the way into the slab buffer - same slots, same arithmetic, same bits as the launch-per-tile
 // kernel - and the look-ahead across the tile boundary carries the NEXT tile's first chunk through that same register path with the
 // next tile's image's scale / shift (second table, fetched by one 256-byte LDS-DMA per wave early in the tile).
-template <bool GN>
+// POOL = true: the pooled epilogue of conv_slab_kernel<true, true> (2 x 2 average of the tile, GroupNorm partials of the pooled values):
+// each staged half of the tile (eight patch rows) holds whole windows, so a pass stores its four pooled rows.
+template <bool GN, bool POOL = false>
 __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int H = p.H, W = p.W, Cin = p.Cin;
@@ -732,7 +767,9 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
   const unsigned oobB = (bytesB + 15u) & ~15u;
   const int nchunks = Cin >> 5;
   const unsigned bytesO = (unsigned)((long)p.M * p.N * 4);   // < 4 GiB (host check)
-  const rsrc_t rs_out = make_rsrc(p.out, bytesO), rs_res = make_rsrc(p.residual ? (const void*)p.residual : (const void*)p.out, bytesO);
+  const unsigned bytesOut = POOL ? bytesO >> 2 : bytesO;     // POOL: out is [B, H/2, W/2, N]; the residual stays full-resolution
+  const rsrc_t rs_out = make_rsrc(p.out, bytesOut);
+  const rsrc_t rs_res = make_rsrc(p.residual ? (const void*)p.residual : (const void*)p.out, p.residual ? bytesO : bytesOut);
 
   int slab_piece[3];
 #pragma unroll
@@ -1062,7 +1099,28 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
         }
       }
       lds_barrier();
-      if (n < p.N) {
+      if constexpr (POOL) {
+        // 4 x 8 pooled pixels x 32 channel quads per pass = 2 items per thread: pooled pixel (half * 4 + qy0 + 2k, qx), k = 0, 1
+        if (n < p.N) {
+          const int qx = rbase & 7, qy0 = rbase >> 3;
+          const long pixo = ((long)g.img * (H >> 1) + (g.y0 >> 1) + qy0) * (W >> 1) + (g.x0 >> 1) + qx;
+          const unsigned pbase = (unsigned)((pixo * p.N + n) * 4);
+          const unsigned prowstep = (unsigned)((long)(W >> 1) * p.N * 4);
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            f32x4 v[4];
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+              v[d] = *(const f32x4*)(smem + P_STAGING + ((2 * qy0 + 4 * k + (d >> 1)) * 16 + 2 * qx + (d & 1)) * CST + col * 4);
+            const f32x4 w = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;   // avgpool_stats_kernel's order
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), rs_out, (int)pbase, (int)(prowstep * (half * 4 + 2 * k)), 0);
+            if (p.gn_partial) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
+            }
+          }
+        }
+      } else if (n < p.N) {
 #pragma unroll
         for (int it = 0; it < NITH; ++it) {
           const f32x4 w = *(const f32x4*)(smem + P_STAGING + (rbase + 16 * it) * CST + col * 4);
@@ -1175,10 +1233,11 @@ extern "C" int muse_conv2d_nhwc_gn_split2_ok(int32_t batch, int32_t H, int32_t W
   return KS == 3 && (H % 16) == 0 && (W % 16) == 0 && (Cin % 64) == 0 && Cin <= 2048 && (Cout % 4) == 0 && M > 0 &&
          M * Cin * 4 < (1L << 32) - 64 && (long)Cout * 9 * Cin * 2 < (1L << 32) - 64 && M < (1L << 31) - 256;
 }
-extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
-                                          const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
-                                          int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
-                                          void* stream) {
+template <bool POOL>
+static int conv_gn_split2_launch(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
+                                 const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
+                                 int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
+                                 void* stream) {
   const long M = (long)batch * H * W;
   if (M <= 0 || Cout <= 0) return 0;
   if (!muse_conv2d_nhwc_gn_split2_ok(batch, H, W, Cin, Cout, KS)) return MUSE_ERR_UNSUPPORTED;
@@ -1205,22 +1264,41 @@ extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale,
     const int ncu = device_cus();
     if (!ncu) return MUSE_ERR_UNSUPPORTED;
     const int grid = grid_env ? grid_env : ncu;
-    set_max_dynamic_lds((const void*)cslab::conv_slab_persist_kernel<true>, cslab::P_LDS_BYTES_GN);
+    set_max_dynamic_lds((const void*)cslab::conv_slab_persist_kernel<true, POOL>, cslab::P_LDS_BYTES_GN);
     const int nslab = (p.M >> 8) * ntn;
     // MUSE_CONV_PERSIST_TILES=k: workgroups of k tiles each (grid = tiles / k) instead of one workgroup per CU for the whole launch - a CU
     // is handed back to the dispatcher (and to the other streams' kernels) every k tiles
     static const int per_wg = []() { const char* e = getenv("MUSE_CONV_PERSIST_TILES"); return e ? atoi(e) : 0; }();
     if (per_wg > 0) {
       if (nslab >= (min_given ? (min_tiles > 1 ? min_tiles : 1) * per_wg : 2 * per_wg * ncu)) {
-        hipLaunchKernelGGL(cslab::conv_slab_persist_kernel<true>, dim3((nslab + per_wg - 1) / per_wg), dim3(512), cslab::P_LDS_BYTES_GN, (hipStream_t)stream, p);
+        hipLaunchKernelGGL((cslab::conv_slab_persist_kernel<true, POOL>), dim3((nslab + per_wg - 1) / per_wg), dim3(512), cslab::P_LDS_BYTES_GN, (hipStream_t)stream, p);
         return (int)hipGetLastError();
       }
     } else if (nslab >= min_tiles * grid) {
-      hipLaunchKernelGGL(cslab::conv_slab_persist_kernel<true>, dim3(nslab < grid ? nslab : grid), dim3(512), cslab::P_LDS_BYTES_GN, (hipStream_t)stream, p);
+      hipLaunchKernelGGL((cslab::conv_slab_persist_kernel<true, POOL>), dim3(nslab < grid ? nslab : grid), dim3(512), cslab::P_LDS_BYTES_GN, (hipStream_t)stream, p);
       return (int)hipGetLastError();
     }
   }
-  set_max_dynamic_lds((const void*)cslab::conv_slab_kernel<true>, cslab::LDS_BYTES + 2 * 2048 * 4);
-  hipLaunchKernelGGL(cslab::conv_slab_kernel<true>, dim3((p.M >> 8) * ntn), dim3(512), cslab::LDS_BYTES + 2 * Cin * 4, (hipStream_t)stream, p);
+  set_max_dynamic_lds((const void*)cslab::conv_slab_kernel<true, POOL>, cslab::LDS_BYTES + 2 * 2048 * 4);
+  hipLaunchKernelGGL((cslab::conv_slab_kernel<true, POOL>), dim3((p.M >> 8) * ntn), dim3(512), cslab::LDS_BYTES + 2 * Cin * 4, (hipStream_t)stream, p);
   return (int)hipGetLastError();
+}
+extern "C" int muse_conv2d_nhwc_gn_split2(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi, const void* w_lo,
+                                          const float* bias, const float* residual, float* out, double* gn_partial, int32_t gn_groups,
+                                          int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, int32_t persistent,
+                                          void* stream) {
+  return conv_gn_split2_launch<false>(x, gn_scale, gn_shift, w_hi, w_lo, bias, residual, out, gn_partial, gn_groups, batch, H, W, Cin, Cout,
+                                      KS, persistent, stream);
+}
+// muse_conv2d_nhwc_gn_split2 followed by F.avg_pool2d(2, 2) (and, with gn_partial, the GroupNorm statistics of the POOLED tensor) in
+// one kernel: the 2 x 2 average is taken in the convolution's epilogue (every window lies inside one 16 x 16 patch).  out is
+// [batch, H/2, W/2, Cout] f32; residual stays [batch, H, W, Cout]; gn_partial is [batch, H * W / 256, gn_groups, 2] f64 - one chunk per
+// convolution tile, 64 pooled pixels each - for muse_groupnorm_scale_shift with nchunk = H * W / 256 and HW = (H / 2) * (W / 2).
+// Same bits as muse_conv2d_nhwc_gn_split2 + muse_avgpool2x2_nhwc_stats for the tensor; the partials sum the same values in another grouping.
+extern "C" int muse_conv2d_nhwc_gn_split2_pool(const float* x, const float* gn_scale, const float* gn_shift, const void* w_hi,
+                                               const void* w_lo, const float* bias, const float* residual, float* out, double* gn_partial,
+                                               int32_t gn_groups, int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS,
+                                               int32_t persistent, void* stream) {
+  return conv_gn_split2_launch<true>(x, gn_scale, gn_shift, w_hi, w_lo, bias, residual, out, gn_partial, gn_groups, batch, H, W, Cin, Cout,
+                                     KS, persistent, stream);
 }

@@ -399,7 +399,9 @@ extern "C" int muse_groupnorm_silu_nhwc_split(const float* x, void* y_hi, void* 
 // gn_partial (optional): [B, H, groups, 2] f64 sums of the output, one chunk per image row (groups of exactly four channels).
 // =================================================================================================================
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-template <int CIN>
+// NCHW = true: x is the image as it arrives, [B, CIN, H, W] f32 contiguous; the staging loop builds the same {c0, c1, c2, c3 | 0} vectors
+// from CIN row-contiguous plane reads (no padded NHWC copy of the image).  Everything behind the staging loop is shared: same bits.
+template <int CIN, bool NCHW = false>
 __global__ __launch_bounds__(256) void conv_in_direct_kernel(const float* __restrict__ x, const float* __restrict__ w4,
                                                              const float* __restrict__ bias, float* __restrict__ out,
                                                              double* __restrict__ gn_partial, int H, int W, int Cpad, int Cout) {
@@ -426,7 +428,17 @@ __global__ __launch_bounds__(256) void conv_in_direct_kernel(const float* __rest
   for (int i = threadIdx.x; i < 3 * (W + 2); i += 256) {
     const int ky = i / (W + 2), ix = i - ky * (W + 2) - 1;
     const bool ok = (ky == 1 || (ky == 0 ? yy > 0 : yy + 1 < H)) && ix >= 0 && ix < W;
-    xs[i] = ok ? *(const f32x4*)(x + ((long)(row + ky - 1) * W + ix) * Cpad) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (NCHW) {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (ok) {
+        const float* src = x + (((long)(row / H) * CIN) * H + (yy + ky - 1)) * W + ix;
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) v[c] = src[(long)c * H * W];
+      }
+      xs[i] = v;
+    } else {
+      xs[i] = ok ? *(const f32x4*)(x + ((long)(row + ky - 1) * W + ix) * Cpad) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
   __syncthreads();
   double gs = 0.0, gq = 0.0;
@@ -475,6 +487,25 @@ extern "C" int muse_conv_in_direct(const float* x, const float* w4, const float*
   if (lds > 48 * 1024) return MUSE_ERR_UNSUPPORTED;              // (W <= 1022)
 #define CID(N) hipLaunchKernelGGL(conv_in_direct_kernel<N>, dim3((unsigned)(batch * H)), dim3(256), lds, (hipStream_t)stream, x, w4, bias, out, \
                                   gn_partial, H, W, Cpad, Cout)
+  if (Cin == 3) CID(3); else if (Cin == 4) CID(4); else if (Cin == 1) CID(1); else CID(2);
+#undef CID
+  return (int)hipGetLastError();
+}
+
+// muse_conv_in_direct reading the image in its NCHW f32 layout ([batch, Cin, H, W] contiguous) instead of a channel-padded NHWC copy:
+// saves muse_nchw_to_nhwc's pass and launch.  Output and GroupNorm partials are the same bits.
+extern "C" int muse_conv_in_direct_nchw(const float* x, const float* w4, const float* bias, float* out, double* gn_partial,
+                                        int32_t gn_groups, int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* stream) {
+  const int qpp = Cout >> 2;
+  if ((Cout & 3) || qpp > 256 || (256 % qpp) || Cin < 1 || Cin > 4) return MUSE_ERR_UNSUPPORTED;
+  if (gn_partial && gn_groups * 4 != Cout) return MUSE_ERR_UNSUPPORTED;      // groups of exactly four channels
+  if (((((uintptr_t)w4) | ((uintptr_t)bias) | ((uintptr_t)out)) & 15) || (((uintptr_t)x) & 3)) return MUSE_ERR_ALIGN;
+  if ((long)batch * H <= 0) return 0;
+  if ((long)batch * H >= (1L << 31)) return MUSE_ERR_UNSUPPORTED;
+  const size_t lds = (size_t)3 * (W + 2) * 16;
+  if (lds > 48 * 1024) return MUSE_ERR_UNSUPPORTED;              // (W <= 1022)
+#define CID(N) hipLaunchKernelGGL((conv_in_direct_kernel<N, true>), dim3((unsigned)(batch * H)), dim3(256), lds, (hipStream_t)stream, x, w4, bias, \
+                                  out, gn_partial, H, W, 0, Cout)
   if (Cin == 3) CID(3); else if (Cin == 4) CID(4); else if (Cin == 1) CID(1); else CID(2);
 #undef CID
   return (int)hipGetLastError();

@@ -152,8 +152,10 @@ SIGNATURES = {
     "muse_conv2d_nhwc_split2": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_void_p],
     "muse_conv_in_direct": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "muse_conv_in_direct_nchw": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "muse_conv2d_nhwc_gn_split2_ok": [c_int, c_int, c_int, c_int, c_int, c_int],
     "muse_conv2d_nhwc_gn_split2": [c_void_p] * 9 + [c_int] * 8 + [c_void_p],
+    "muse_conv2d_nhwc_gn_split2_pool": [c_void_p] * 9 + [c_int] * 8 + [c_void_p],
     "muse_groupnorm_scale_shift": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "muse_groupnorm_silu_nhwc_split": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                        c_int, c_float, c_int, c_void_p],

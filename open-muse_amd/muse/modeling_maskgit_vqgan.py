@@ -125,6 +125,10 @@ class _ConvEngine:
         self.fuse_gn_stats = True   # convolution / pooling epilogues produce the next GroupNorm's statistics
         self.fuse_gn_apply = os.environ.get("MUSE_GN_FUSE", "1") != "0"   # GroupNorm + SiLU applied inside the consuming patch-slab convolution
         self.direct_conv_in = os.environ.get("MUSE_CONV_IN_DIRECT", "1") != "0"   # bf16x3 mode: conv_in as a direct exact-f32 kernel
+        self.conv_in_nchw = os.environ.get("MUSE_CONV_IN_NCHW", "1") != "0"   # ... reading the NCHW image itself (no padded NHWC copy)
+        # bf16x3 mode, encoder: avg_pool2d(2, 2) (+ the next GroupNorm's statistics) in the epilogue of the convolution that produces the
+        # pooled tensor (the level's last ResBlock.conv2) instead of a pooling pass over its output
+        self.fuse_pool = os.environ.get("MUSE_POOL_FUSE", "1") != "0"
         self.dma_conv = True        # "bf16x3" mode: 3x3 convs after GroupNorm run as the LDS-DMA kernel on pre-split planes
         # bf16x3 mode, decoder: norm_out -> swish -> conv_out (-> 3 image channels) as one direct exact-f32 kernel; the up-sampling
         # convolutions on the LDS-DMA kernel (nearest x2 written as the convolution's operand planes)
@@ -179,23 +183,44 @@ class _ConvEngine:
             self._packed[key] = hit
         return hit
 
+    def _conv_in_image(self, pixel_values, conv, B, H, W, cd):
+        """conv_in of an NCHW f32 image batch -> NHWC features.  bf16x3 mode: the direct kernel stages its rows from the NCHW tensor
+        itself; otherwise the image is first re-laid out as channel-padded NHWC in the activation dtype."""
+        C = pixel_values.shape[1]
+        cout, cin, k, _ = conv.weight.shape
+        cpad = self._cpad(C, cd)
+        x = pixel_values.float()
+        if (cd == "bf16x3" and self.direct_conv_in and self.conv_in_nchw and cin == C and ops.conv_in_direct_ok(cin, cout, k, cpad, W)):
+            w4, bias = self._w_conv_in_direct(conv)
+            return ops.conv_in_direct_nchw(x.contiguous(), w4, B, H, W, cin, cout, bias=bias, gn_groups=32 if self.fuse_gn_stats else 0)
+        return self._conv_in(ops.nchw_to_nhwc(x, self._act_dtype(), cpad), conv, B, H, W, cd, cpad)
+
+    def _w_conv_in_direct(self, conv):
+        cout, cin, k, _ = conv.weight.shape
+        key = (id(conv), "direct")
+        hit = self._packed.get(key)
+        if hit is None:
+            w4 = torch.zeros((cout, 9, 4), dtype=torch.float32, device=conv.weight.device)
+            w4[:, :, :cin] = conv.weight.data.float().permute(0, 2, 3, 1).reshape(cout, 9, cin)
+            hit = (w4.contiguous(), None if conv.bias is None else conv.bias.data.float().contiguous())
+            self._packed[key] = hit
+        return hit
+
     def _conv_in(self, x, conv, B, H, W, cd, cpad):
         """the image-to-features convolution: in the bf16x3 mode a direct exact-f32 kernel (3 input channels are no matrix-core
         problem; ops.conv_in_direct), otherwise the mode's implicit GEMM"""
         cout, cin, k, _ = conv.weight.shape
         if cd == "bf16x3" and self.direct_conv_in and ops.conv_in_direct_ok(cin, cout, k, cpad, W):
-            key = (id(conv), "direct")
-            hit = self._packed.get(key)
-            if hit is None:
-                w4 = torch.zeros((cout, 9, 4), dtype=torch.float32, device=conv.weight.device)
-                w4[:, :, :cin] = conv.weight.data.float().permute(0, 2, 3, 1).reshape(cout, 9, cin)
-                hit = (w4.contiguous(), None if conv.bias is None else conv.bias.data.float().contiguous())
-                self._packed[key] = hit
+            hit = self._w_conv_in_direct(conv)
             return ops.conv_in_direct(x, hit[0], B, H, W, cin, cpad, cout, bias=hit[1], gn_groups=32 if self.fuse_gn_stats else 0)
         return self._conv(x, conv, B, H, W, cd, gn_next=True)
 
-    def _conv(self, x, conv, B, H, W, cd, residual=None, upsample=False, gn_next=False):
+    def _conv(self, x, conv, B, H, W, cd, residual=None, upsample=False, gn_next=False, pool=False):
+        """pool=True (only with _pool_ok): the convolution's epilogue stores the 2 x 2 average of its output, [B, H/2, W/2, Cout]"""
         wp, cp, cout, k, bias = self._w(conv, cd)
+        if pool:
+            return ops.conv2d_nhwc_gn_split2_pool(x.x, x.scale, x.shift, wp[0], wp[1], B, H, W, cp, cout, bias=bias, residual=residual,
+                                                  gn_groups=32 if (gn_next and self.fuse_gn_stats) else 0)
         if isinstance(x, _GNInput):   # GroupNorm + SiLU + split inside the convolution (_gn_for)
             return ops.conv2d_nhwc_gn_split2(x.x, x.scale, x.shift, wp[0], wp[1], B, H, W, cp, cout, bias=bias, residual=residual,
                                              gn_groups=32 if (gn_next and self.fuse_gn_stats) else 0)
@@ -214,6 +239,12 @@ class _ConvEngine:
             return ops.conv2d_nhwc_split(x, wp[0], wp[1], B, H, W, cp, cout, k, bias=bias, residual=residual, upsample=upsample,
                                          gn_groups=32 if (gn_next and self.fuse_gn_stats) else 0)
         return ops.conv2d_nhwc(x, wp, B, H, W, cp, cout, k, bias=bias, residual=residual, upsample=upsample)
+
+    def _pool_ok(self, x, conv: _Conv, B, H, W, cd):
+        """may `conv` (input `x` as _gn_for returned it) take the average pooling that follows it into its epilogue?"""
+        cout, cin, k, _ = conv.weight.shape
+        return (cd == "bf16x3" and self.fuse_pool and isinstance(x, _GNInput) and cin == cout
+                and ops.conv_gn_split2_pool_ok(B, H, W, cin, cout, k, 32 if self.fuse_gn_stats else 0))
 
     def _upsample_conv(self, h, conv: _Conv, B, H, W, cd):
         """UpsamplingBlock (:141-149): nearest x2 then 3x3 convolution; H, W = the OUTPUT size.  bf16x3 mode: the up-sampled tensor is
@@ -304,13 +335,20 @@ class MaskGitVQGAN(_ConvEngine, ModelMixin, ConfigMixin):
         self.quantize = _Quantizer(num_embeddings, quantized_embed_dim)
         self._init_engine()
 
-    def _res(self, x, blk: _Res, B, H, W, cd):
+    def _res(self, x, blk: _Res, B, H, W, cd, pool=False):
+        """pool=True: the block is followed by avg_pool2d(2, 2); when its last convolution qualifies (_pool_ok) the POOLED tensor is
+        returned, marked `_pooled` (its `_gn_stats` are the pooled tensor's); otherwise the block's output as usual"""
         cin = blk.conv1.weight.shape[1]
         cout = blk.conv1.weight.shape[0]
         # gn_next: the convolution's epilogue also leaves the GroupNorm statistics of its output for the next norm layer
         h = self._conv(self._gn_for(x, blk.norm1, blk.conv1, B, H, W, cd), blk.conv1, B, H, W, cd, gn_next=True)
         if cin == cout:
-            return self._conv(self._gn_for(h, blk.norm2, blk.conv2, B, H, W, cd), blk.conv2, B, H, W, cd, residual=x, gn_next=True)
+            g = self._gn_for(h, blk.norm2, blk.conv2, B, H, W, cd)
+            if pool and self._pool_ok(g, blk.conv2, B, H, W, cd):
+                out = self._conv(g, blk.conv2, B, H, W, cd, residual=x, gn_next=True, pool=True)
+                out._pooled = True
+                return out
+            return self._conv(g, blk.conv2, B, H, W, cd, residual=x, gn_next=True)
         h = self._conv(self._gn_for(h, blk.norm2, blk.conv2, B, H, W, cd), blk.conv2, B, H, W, cd)
         # reference quirk (:82-85): the "shortcut" is a 1x1 conv of the conv2 output, out = h + nin(h)
         return self._conv(h, blk.nin_shortcut, B, H, W, cd, residual=h, gn_next=True)
@@ -323,14 +361,14 @@ class MaskGitVQGAN(_ConvEngine, ModelMixin, ConfigMixin):
         cd = self.compute_dtype
         enc = self.encoder
         B, C, H, W = pixel_values.shape
-        x = ops.nchw_to_nhwc(pixel_values.float(), self._act_dtype(), self._cpad(C, cd))
-        h = self._conv_in(x, enc.conv_in, B, H, W, cd, self._cpad(C, cd))
+        h = self._conv_in_image(pixel_values, enc.conv_in, B, H, W, cd)
         nres = self.config.num_resolutions
         for lvl, down in enumerate(enc.down):
-            for blk in down.block:
-                h = self._res(h, blk, B, H, W, cd)
+            for i, blk in enumerate(down.block):
+                h = self._res(h, blk, B, H, W, cd, pool=lvl != nres - 1 and i == len(down.block) - 1)
             if lvl != nres - 1:
-                h = ops.avgpool2x2_nhwc(h, B, H, W, h.shape[-1], gn_groups=32 if (cd == "bf16x3" and self.fuse_gn_stats) else 0)
+                if not getattr(h, "_pooled", False):   # (the level's last convolution did not take the pooling into its epilogue)
+                    h = ops.avgpool2x2_nhwc(h, B, H, W, h.shape[-1], gn_groups=32 if (cd == "bf16x3" and self.fuse_gn_stats) else 0)
                 H, W = H // 2, W // 2
         for blk in enc.mid:
             h = self._res(h, blk, B, H, W, cd)

@@ -1898,6 +1898,25 @@ def conv_in_direct(x, w4, B, H, W, Cin, Cpad, Cout, bias=None, gn_groups=0):
     return out
 
 
+def conv_in_direct_nchw(x, w4, B, H, W, Cin, Cout, bias=None, gn_groups=0):
+    """conv_in_direct reading the image as it arrives (muse_conv_in_direct_nchw): x [B, Cin, H, W] f32 contiguous; no padded NHWC copy.
+    Same bits as nchw_to_nhwc + conv_in_direct."""
+    require_gpu(x, w4)
+    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (B, Cin, H, W):
+        raise ValueError("conv_in_direct_nchw: x must be a contiguous f32 [B, Cin, H, W] tensor")
+    out = torch.empty((B, H, W, Cout), dtype=torch.float32, device=x.device)
+    part = None
+    if gn_groups and gn_groups * 4 == Cout:
+        part = torch.empty(B * H * gn_groups * 2, dtype=torch.float64, device=x.device)
+    e0 = _prof_begin()
+    check(lib().muse_conv_in_direct_nchw(x.data_ptr(), w4.data_ptr(), ptr(bias), out.data_ptr(), ptr(part), gn_groups if part is not None else 0,
+                                         B, H, W, Cin, Cout, stream()), "muse_conv_in_direct_nchw")
+    _prof_end(e0, "conv_in_direct", _nbytes(x, out), "byte")
+    if part is not None:
+        out._gn_stats = (part, H)
+    return out
+
+
 def conv_out_direct_ok(H, W, Cin, Cout, KS):
     """shapes muse_conv_out_direct takes: the features-to-image 3x3 convolution of a decoder"""
     return KS == 3 and Cout <= 4 and Cin % 32 == 0 and Cin >= 32 and H % 16 == 0 and W % 16 == 0
@@ -1986,6 +2005,34 @@ def conv2d_nhwc_gn_split2(x, scale, shift, w_hi, w_lo, B, H, W, Cin, Cout, bias=
     check(lib().muse_conv2d_nhwc_gn_split2(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr(), ptr(bias),
                                            ptr(residual), out.data_ptr(), ptr(part), gn_groups if part is not None else 0,
                                            B, H, W, Cin, Cout, 3, int(_CONV_PERSISTENT[0]), stream()), "muse_conv2d_nhwc_gn_split2")
+    _prof_end(e0, "conv_bf16x3_dma", 2.0 * B * H * W * Cout * 9 * Cin)
+    if e0 is not None:
+        PROF_BYTES["conv_bf16x3_dma"] = PROF_BYTES.get("conv_bf16x3_dma", 0.0) + _nbytes(x, w_hi, w_lo, residual, out)
+    if part is not None:
+        out._gn_stats = (part, nchunk)
+    return out
+
+
+def conv_gn_split2_pool_ok(B, H, W, Cin, Cout, KS, gn_groups=0):
+    """layers muse_conv2d_nhwc_gn_split2_pool takes: the shapes of conv2d_nhwc_gn_split2 (H, W multiples of 16: every 2 x 2 window lies
+    inside one convolution tile) and, when the pooled tensor's GroupNorm statistics are wanted, the epilogue's channel condition"""
+    return conv_gn_split2_ok(B, H, W, Cin, Cout, KS) and (not gn_groups or conv_gn_stats_ok(H, W, Cout, gn_groups))
+
+
+def conv2d_nhwc_gn_split2_pool(x, scale, shift, w_hi, w_lo, B, H, W, Cin, Cout, bias=None, residual=None, gn_groups=0):
+    """avg_pool2d(conv3x3(silu(GroupNorm(x))) + residual, 2, 2) in one kernel (muse_conv2d_nhwc_gn_split2_pool): the 2 x 2 average is taken
+    in the convolution's epilogue -> [B, H/2, W/2, Cout] f32, the bits of conv2d_nhwc_gn_split2 + avgpool2x2_nhwc.  gn_groups > 0: the
+    GroupNorm statistics of the POOLED tensor ride on it (`out._gn_stats = (partial, H * W / 256)`: one chunk per convolution tile)."""
+    require_gpu(x, scale, shift, w_hi, w_lo)
+    out = torch.empty((B, H // 2, W // 2, Cout), dtype=torch.float32, device=x.device)
+    part, nchunk = None, 0
+    if gn_groups and conv_gn_stats_ok(H, W, Cout, gn_groups):
+        nchunk = (H * W) // 256
+        part = torch.empty(B * nchunk * gn_groups * 2, dtype=torch.float64, device=out.device)
+    e0 = _prof_begin()
+    check(lib().muse_conv2d_nhwc_gn_split2_pool(x.data_ptr(), scale.data_ptr(), shift.data_ptr(), w_hi.data_ptr(), w_lo.data_ptr(), ptr(bias),
+                                                ptr(residual), out.data_ptr(), ptr(part), gn_groups if part is not None else 0,
+                                                B, H, W, Cin, Cout, 3, int(_CONV_PERSISTENT[0]), stream()), "muse_conv2d_nhwc_gn_split2_pool")
     _prof_end(e0, "conv_bf16x3_dma", 2.0 * B * H * W * Cout * 9 * Cin)
     if e0 is not None:
         PROF_BYTES["conv_bf16x3_dma"] = PROF_BYTES.get("conv_bf16x3_dma", 0.0) + _nbytes(x, w_hi, w_lo, residual, out)
