@@ -624,6 +624,30 @@ int muse_grn_bwd(const float* dy, const float* x, const float* gamma, const floa
 int muse_scale_rows(float* x, const float* w, const float* num, const float* den, int64_t rows, int32_t cols, int64_t ld,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * CLIP text tower (transformers CLIPTextModel / CLIPTextModelWithProjection, the `type: "clip"` text encoder of the reference's
+ * configs: training/train_muse.py:331-338, called every step at :647-649).  Forward only.  (csrc/clip_text.hip)
+ * muse_causal_attention_fwd: fused CAUSAL self-attention, bf16 q / k / v / o addressed as for muse_attention_fwd_ex (row strides
+ *   free: slices of one packed q | k | v projection; all strides multiples of 8, pointers 16-byte aligned), f32 softmax and
+ *   accumulation, MFMA products.  Key j takes part in query i iff j <= i.  seq_q == seq_kv in 1..128 (the sequence is one tile: one
+ *   workgroup per (image, head), no S x S matrix in memory), head_dim 32 or 64; anything else MUSE_ERR_UNSUPPORTED.  Rows >= seq of an
+ *   image are never read.  Replaces CLIPAttention.forward with the causal mask (transformers models/clip/modeling_clip.py).
+ * muse_causal_softmax_fwd: the same mask on materialised scores, [mats][seq][ld] (f32 or bf16): row i of each matrix = softmax over
+ *   its columns 0..i, every other column of [0, ld) written as 0; in place capable.  (The exact-f32 mode: between two muse_gemm products.)
+ * muse_bias_quick_gelu: y = v * sigmoid(1.702 v), v = x + bias[col], on [rows, cols] f32 or bf16, in place capable
+ *   (QuickGELUActivation behind CLIPMLP.fc1, `hidden_act: "quick_gelu"`).
+ * muse_layernorm_bias_fwd: y = LayerNorm(x) * w + b in one pass, x f32 [rows, cols], y f32 or bf16 (nn.LayerNorm with its bias:
+ *   layer_norm1 / layer_norm2 / final_layer_norm).
+ * muse_eos_index: idx[b] = the pooled position of ids[b, :] (int64 [batch, seq]): the first position equal to eos_token_id, or - when
+ *   eos_token_id == 2, the legacy rule the openai checkpoints carry - the first position of the row maximum; 0 when nothing matches.
+ *   flat_idx (may be NULL) receives b * seq + idx[b], the row muse_gather_rows picks from the [batch * seq, hidden] states. */
+int muse_causal_attention_fwd(const muse_attn_desc* d, void* stream);
+int muse_causal_softmax_fwd(const void* x, void* y, int32_t dtype, int64_t mats, int32_t seq, int64_t ld, void* stream);
+int muse_bias_quick_gelu(const void* x, const float* bias, void* y, int32_t dtype, int64_t rows, int32_t cols, void* stream);
+int muse_layernorm_bias_fwd(const float* x, const float* w, const float* b, void* y, int32_t y_dtype, int64_t rows, int32_t cols,
+                            float eps, void* stream);
+int muse_eos_index(const int64_t* ids, int64_t* idx, int64_t* flat_idx, int32_t batch, int32_t seq, int64_t eos_token_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

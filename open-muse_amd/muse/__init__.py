@@ -2,7 +2,8 @@
 
 Same import surface as the reference package for the classes on the path (reference muse/__init__.py:18-25):
 MaskGitTransformer, MaskGiTUViT, MaskGitVQGAN, VQGANModel (the taming tokenizer of the text-to-image configs),
-PipelineMuse, PipelineMuseInpainting, EMAModel (the weight average train_muse.py advances behind every optimizer step), get_mask_chedule; everything computes
+PipelineMuse, PipelineMuseInpainting, EMAModel (the weight average train_muse.py advances behind every optimizer step), get_mask_chedule; plus
+CLIPTextEncoder, the CLIP text tower of the text-to-image configs on the same kernels (opt-in; T5 stays a `transformers` model); everything computes
 through libmuse_hip.so (hand-written HIP kernels for gfx950).
 The MoVQ / Paella VQ models are not part of this build: their names import (the training scripts import them unconditionally) and
 refuse to construct.  `muse.lr_schedulers` / `muse.training_utils` carry the host-side helpers those scripts import.
@@ -10,6 +11,7 @@ refuse to construct.  `muse.lr_schedulers` / `muse.training_utils` carry the hos
 __version__ = "0.0.1"
 
 from .ema import EMAModel
+from .modeling_clip_text import CLIPTextEncoder
 from .modeling_maskgit_vqgan import MaskGitVQGAN
 from .modeling_taming_vqgan import VQGANModel
 from .modeling_transformer import MaskGitTransformer
@@ -22,5 +24,5 @@ from . import lr_schedulers, training_utils
 from .training import (FusedAdamW, GradReducer, TrainStep, clip_grad_norm_, cond_dropout, grad_norms, grouped_parameters,
                        mask_or_random_replace_tokens, prepare_inputs_and_labels)
 
-__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "GradReducer", "clip_grad_norm_", "grad_norms",
+__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "CLIPTextEncoder", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "GradReducer", "clip_grad_norm_", "grad_norms",
            "TrainStep", "prepare_inputs_and_labels", "mask_or_random_replace_tokens", "cond_dropout", "grouped_parameters"]

@@ -194,6 +194,11 @@ SIGNATURES = {
     "muse_grn_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_scale_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p],
     "muse_probe_tr16": [c_void_p, c_void_p, c_void_p],
+    "muse_causal_attention_fwd": [C.POINTER(AttnDesc), c_void_p],
+    "muse_causal_softmax_fwd": [c_void_p, c_void_p, c_int, c_i64, c_int, c_i64, c_void_p],
+    "muse_bias_quick_gelu": [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
+    "muse_layernorm_bias_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_float, c_void_p],
+    "muse_eos_index": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p],
 }
 _RESTYPES = {"muse_embed_bwd_scratch_floats": c_i64, "muse_embed_bwd2_scratch_bytes": c_i64}
 

@@ -2414,3 +2414,62 @@ def probe_tr16(addr):
     out = torch.empty(256, dtype=torch.int32, device=addr.device)
     check(lib().muse_probe_tr16(addr.data_ptr(), out.data_ptr(), stream()), "muse_probe_tr16")
     return out
+
+
+# ---- CLIP text tower (csrc/clip_text.hip; muse.CLIPTextEncoder): forward only ------------------------------------------------------
+def causal_attention_fwd(q, k, v, B, S, nh, hd, alpha, out=None):
+    """fused causal softmax(alpha q k^T) v for q / k / v [B*S, H] bf16 views (row strides free: slices of one packed q | k | v
+    projection; rows >= S of an image are never read) -> ctx [B*S, H] bf16.  No score matrix in memory."""
+    require_gpu(q, k, v)
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise _hip.MuseHipError("the fused causal attention kernel takes bf16 operands")
+    ctx = out if out is not None else torch.empty((B * S, nh * hd), dtype=torch.bfloat16, device=q.device)
+    d = _attn_desc(q, k, v, ctx, B, S, S, nh, hd, alpha)
+    e0 = _prof_begin()
+    check(lib().muse_causal_attention_fwd(C.byref(d), stream()), "muse_causal_attention_fwd")
+    _prof_end(e0, "attn_causal_fwd_bf16", 4.0 * B * nh * S * S * hd)
+    return _touched(ctx)
+
+
+def causal_softmax_(x, mats, seq, ld):
+    """in place on [mats, seq, ld] score matrices: row i = softmax over its columns 0..i, every other column of [0, ld) = 0"""
+    require_gpu(x)
+    e0 = _prof_begin()
+    check(lib().muse_causal_softmax_fwd(x.data_ptr(), x.data_ptr(), dt(x), mats, seq, ld, stream()), "muse_causal_softmax_fwd")
+    _prof_end(e0, "causal_softmax_fwd", 2.0 * _nbytes(x), "byte")
+    return _touched(x)
+
+
+def bias_quick_gelu_(x, bias):
+    """in place on x [rows, cols] (f32 / bf16): v = x + bias[col]; x = v * sigmoid(1.702 v)"""
+    require_gpu(x, bias)
+    rows, cols = x.shape
+    if not x.is_contiguous() or bias.dtype != torch.float32 or bias.numel() != cols:
+        raise _hip.MuseHipError("bias_quick_gelu_: x contiguous [rows, cols], bias f32 [cols]")
+    check(lib().muse_bias_quick_gelu(x.data_ptr(), bias.data_ptr(), x.data_ptr(), dt(x), rows, cols, stream()), "muse_bias_quick_gelu")
+    return _touched(x)
+
+
+def layernorm_bias_fwd(x, w, b, eps, out_dtype):
+    """LayerNorm(x) * w + b in one pass: x f32 [rows, cols] -> f32 or bf16"""
+    require_gpu(x, w, b)
+    rows, cols = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _hip.MuseHipError("layernorm_bias_fwd: x is a contiguous f32 [rows, cols] tensor")
+    y = torch.empty((rows, cols), dtype=out_dtype, device=x.device)
+    check(lib().muse_layernorm_bias_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), dt(y), rows, cols, eps, stream()),
+          "muse_layernorm_bias_fwd")
+    return y
+
+
+def eos_index(ids, eos_token_id):
+    """ids int64 [B, S] -> (idx [B], flat [B] = b * S + idx[b]) int64: the pooled position of every row (first eos_token_id; with
+    eos_token_id == 2 the first position of the row maximum; 0 when nothing matches) - no host read of the ids"""
+    require_gpu(ids)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_contiguous():
+        raise _hip.MuseHipError("eos_index: ids is a contiguous int64 [batch, seq] tensor")
+    B, S = ids.shape
+    idx = torch.empty(B, dtype=torch.int64, device=ids.device)
+    flat = torch.empty(B, dtype=torch.int64, device=ids.device)
+    check(lib().muse_eos_index(ids.data_ptr(), idx.data_ptr(), flat.data_ptr(), B, S, int(eos_token_id), stream()), "muse_eos_index")
+    return idx, flat

@@ -2,7 +2,7 @@
 
 Thin: `generate2` on the transformer, then `vae.decode_code`; both run on the HIP kernels (the inpainting pipeline first tokenises the
 picture with `vae.encode`).  The text encoder is the reference's own third-party dependency (a `transformers` CLIP / T5 model and its
-tokenizer, handed to the constructor): when one is given, `text=` is encoded by calling it exactly as the reference does; without one the
+tokenizer, handed to the constructor) or, for CLIP, `muse.CLIPTextEncoder` (the same tower on the HIP kernels): when one is given, `text=` is encoded by calling it exactly as the reference does; without one the
 pipelines take PRE-COMPUTED text states (`prompt_embeds`, ...).  Constructor / `to` / `from_pretrained` / `save_pretrained` signatures kept.
 """
 from __future__ import annotations
@@ -186,8 +186,9 @@ class PipelineMuse:
     @classmethod
     def from_pretrained(cls, model_name_or_path: str = None, text_encoder_path: Optional[str] = None,
                         vae_path: Optional[str] = None, transformer_path: Optional[str] = None, vae=None, text_encoder=None,
-                        transformer=None, is_class_conditioned: bool = False, **kwargs):
-        """reference :254-355, same arguments.  The text encoder and tokenizer of a text-conditioned pipeline are the reference's own
+                        transformer=None, is_class_conditioned: bool = False, native_text_encoder: bool = False, **kwargs):
+        """reference :254-355, same arguments, plus `native_text_encoder` (this build's addition, default False): True loads the text
+        tower from the same folder as `muse.CLIPTextEncoder` (the CLIP text model on the HIP kernels) instead.  The text encoder and tokenizer of a text-conditioned pipeline are the reference's own
         `transformers` classes, loaded the way the reference loads them (`CLIPTextModelWithProjection`, `AutoTokenizer`) - from
         `<model>/text_encoder` or `text_encoder_path`; a LOCAL checkpoint directory without a `text_encoder/` folder gives a pipeline
         that takes pre-computed text states instead (this build's addition)."""
@@ -214,7 +215,10 @@ class PipelineMuse:
             local_without = os.path.isdir(str(te_path)) and not os.path.isdir(os.path.join(str(te_path), sub.get("subfolder", "")))
             if not local_without:
                 from transformers import AutoTokenizer, CLIPTextModelWithProjection
-                if text_encoder is None:
+                if text_encoder is None and native_text_encoder:
+                    from .modeling_clip_text import CLIPTextEncoder
+                    text_encoder = CLIPTextEncoder.from_pretrained(te_path, **sub)
+                elif text_encoder is None:
                     text_encoder = CLIPTextModelWithProjection.from_pretrained(te_path, **sub)
                 tokenizer = AutoTokenizer.from_pretrained(te_path, **sub)
         if model_name_or_path is not None:
