@@ -91,6 +91,47 @@ template <> struct Elem<bf16_t> {
   static __device__ __forceinline__ void store(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 };
 
+// ---- 4-element vector access helpers ---------------------------------------------------------------------------
+template <typename T> struct V4;
+template <> struct V4<float> {
+  typedef f32x4 raw;
+  static __device__ __forceinline__ raw load_raw(const float* p) { return *(const f32x4*)p; }
+  static __device__ __forceinline__ void unpack(const raw& t, float (&v)[4]) { v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
+    const f32x4 t = *(const f32x4*)p; v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  }
+  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]}; }
+};
+template <> struct V4<bf16_t> {
+  typedef u32x2 raw;
+  static __device__ __forceinline__ raw load_raw(const bf16_t* p) { return *(const u32x2*)p; }
+  static __device__ __forceinline__ void unpack(const raw& t, float (&v)[4]) {
+    v[0] = __uint_as_float(t[0] << 16); v[1] = __uint_as_float(t[0] & 0xffff0000u);
+    v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
+    const u32x2 t = *(const u32x2*)p;
+    v[0] = __uint_as_float(t[0] << 16); v[1] = __uint_as_float(t[0] & 0xffff0000u);
+    v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
+    u32x2 t;
+    t[0] = pack2_bf16(v[0], v[1]);
+    t[1] = pack2_bf16(v[2], v[3]);
+    *(u32x2*)p = t;
+  }
+};
+
+// grid of a grid-stride element-wise kernel over n items (256 per block, at most 4096 blocks)
+static inline int ew_grid(long n) { long g = (n + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }
+
+// chunked multi-tensor kernels (optim.hip, gradnorm.hip): chunk_first is the exclusive prefix sum of the tensors' chunk counts, block ->
+// chunk id -> the largest t in [lo, hi) with chunk_first[t] <= id
+__device__ __forceinline__ int tensor_of_chunk(const int* __restrict__ chunk_first, int lo, int hi, int id) {
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= id) lo = mid; else hi = mid; }
+  return lo;
+}
+
 // ---- wave64 reductions -------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -4,14 +4,14 @@
 //   1. sum of squares per (parameter, 4096-element chunk counted from the parameter's own start) -> a slab of f64 partials, one plain
 //      store per chunk: no floating-point atomics, so the slab does not depend on how the gradient is cut into calls or on their order;
 //   2. finalize (one launch): the chunks of a parameter folded in chunk order, the parameters in parameter order, norm / coefficient /
-//      scale / per-parameter norms written to device memory - the AdamW kernels read the scale from there (rowops.hip, *_dev);
+//      scale / per-parameter norms written to device memory - the AdamW kernels read the scale from there (optim.hip, *_dev);
 //   3. in-place scale of the gradients by a device-side factor, for loops that clip and then step in the reference's order.
 // Squares and sums are f64: an f32 square is exact in f64 and the kernel streams 4 bytes per element, far from the f64 FMA rate.
 #include "common.h"
 #include "../../include/muse_hip.h"
 #include <math.h>
 
-#define GN_CHUNK 4096   // the chunk of adamw_multi_kernel: FusedAdamW's chunk_first table serves both
+#define GN_CHUNK 4096   // the chunk of adamw_multi_kernel (OPT_CHUNK of optim.hip): FusedAdamW's chunk_first table serves both
 
 // Sum of squares of g[0, cnt), cnt <= GN_CHUNK, by one workgroup of 256 -> *out.  Element i belongs to lane (i / 4) % 256, slot i % 4,
 // whether it is read by a 16-byte load or (unaligned start, ragged end) alone: the partial is a function of the values only.
@@ -41,12 +41,6 @@ __device__ __forceinline__ void chunk_sumsq(const float* __restrict__ g, long cn
   if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) *out = (w[0] + w[1]) + (w[2] + w[3]);
-}
-
-// largest t in [lo, hi) with chunk_first[t] <= id
-__device__ __forceinline__ int tensor_of_chunk(const int* __restrict__ chunk_first, int lo, int hi, int id) {
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= id) lo = mid; else hi = mid; }
-  return lo;
 }
 
 // Flat form: g is element 0 of the model's flat gradient buffer, ptab {offset, n} per parameter (absolute element offsets; the alignment

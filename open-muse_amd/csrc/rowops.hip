@@ -1,39 +1,8 @@
 // Row / element kernels of the MaskGitTransformer path: LayerNorm, softmax, GLU, GELU, cross-entropy, embedding,
-// AdamW, casts, mask sampling.  All HBM-bound: 8/16-byte vector accesses, wave64 shuffle reductions, one wave per
+// casts, mask sampling (the optimizer step is optim.hip).  All HBM-bound: 8/16-byte vector accesses, wave64 shuffle reductions, one wave per
 // row where a row fits a wave's registers.
 #include "common.h"
 #include "../../include/muse_hip.h"
-
-// ---- 4-element vector access helpers ---------------------------------------------------------------------------
-template <typename T> struct V4;
-template <> struct V4<float> {
-  typedef f32x4 raw;
-  static __device__ __forceinline__ raw load_raw(const float* p) { return *(const f32x4*)p; }
-  static __device__ __forceinline__ void unpack(const raw& t, float (&v)[4]) { v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const f32x4 t = *(const f32x4*)p; v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]}; }
-};
-template <> struct V4<bf16_t> {
-  typedef u32x2 raw;
-  static __device__ __forceinline__ raw load_raw(const bf16_t* p) { return *(const u32x2*)p; }
-  static __device__ __forceinline__ void unpack(const raw& t, float (&v)[4]) {
-    v[0] = __uint_as_float(t[0] << 16); v[1] = __uint_as_float(t[0] & 0xffff0000u);
-    v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
-    const u32x2 t = *(const u32x2*)p;
-    v[0] = __uint_as_float(t[0] << 16); v[1] = __uint_as_float(t[0] & 0xffff0000u);
-    v[2] = __uint_as_float(t[1] << 16); v[3] = __uint_as_float(t[1] & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-    u32x2 t;
-    t[0] = pack2_bf16(v[0], v[1]);
-    t[1] = pack2_bf16(v[2], v[3]);
-    *(u32x2*)p = t;
-  }
-};
 
 // =================================================================================================================
 // LayerNorm (weight only).  One wave per row, 4 rows per 256-thread block.
@@ -975,7 +944,6 @@ __global__ void glu_bwd_kernel(const T* __restrict__ ab, const T* __restrict__ d
     V4<T>::store(dab + r * 2 * inter + inter + c, db);
   }
 }
-static inline int ew_grid(long n) { long g = (n + 255) / 256; return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g)); }
 // f32 GLU of the "bf16x3" compute mode: the same expressions as glu_*_kernel<float> (the same f32 bits), and the result ALSO as the
 // (hi, lo) bf16 operand planes of the product that reads it (muse_gemm_x3: h feeds the FFN's output projection, d(ab) the dX and dW
 // products of its input projection) - the separate split pass (read 4 + write 4 bytes per element) becomes 4 written bytes here.
@@ -1567,447 +1535,6 @@ extern "C" int muse_soft_ce_bwd(const float* logits, const int64_t* labels, cons
 #undef SCB_T
 #undef SCB
   return (int)hipGetLastError();
-}
-
-// Overflow guard of the "f16" compute mode (the `skip` argument of every AdamW entry point): when non-NULL, every AdamW kernel (flat, flat
-// groups, multi-tensor) reads *skip first and leaves every tensor untouched if it is non-zero - the gradients of a backward pass whose operand
-// images overflowed half's range are NaN, and the update is skipped ON THE DEVICE (torch.cuda.amp.GradScaler's found_inf, without a host
-// round trip).  NULL = no guard.
-// =================================================================================================================
-// AdamW over a flat f32 buffer; optional bf16 shadow refresh.  7 x 4 B per parameter of HBM traffic (+2 B shadow).
-// =================================================================================================================
-// The gradient factor.  DEV = false (the host's grad_scale, a kernel argument): the plain product, which the compiler contracts into the
-// `gr - m` that follows (one fma on the unrounded product; invisible for a power of two, what grad_scale is).  DEV = true (the *_dev entry
-// points: the factor is read from device memory, grad_scale * clip coefficient written by muse_gradnorm_finalize): the product is rounded
-// once and that value goes into the update - "scale inside the kernel" and "scale the buffer, then step" are the same bits.
-template <bool DEV> __device__ __forceinline__ float grad_times(float g, float s) {
-  if constexpr (DEV) {
-#pragma clang fp contract(off)
-    float r = g * s;
-    asm volatile("" : "+v"(r));
-    return r;
-  } else {
-    return g * s;
-  }
-}
-// `skip` is the f16 mode's overflow guard; `sdev` (DEV only) the device-side factor that takes gscale's place
-#define ADAMW_PROLOGUE                    \
-  if (skip && *skip != 0) return;         \
-  if constexpr (DEV) gscale = *sdev;
-template <bool DEV> __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
-                                                    float b2, float eps, float decay, float omb1, float omb2,
-                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip,
-                                                    const float* __restrict__ sdev) {
-  ADAMW_PROLOGUE
-  const long n4 = n >> 2;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    float pp[4], gg[4], mm[4], vv[4];
-    V4<float>::load(p + i * 4, pp); V4<float>::load(g + i * 4, gg); V4<float>::load(m + i * 4, mm); V4<float>::load(v + i * 4, vv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = grad_times<DEV>(gg[j], gscale);
-      pp[j] = pp[j] * decay;                           // param.mul_(1 - lr * weight_decay), factor rounded once on the host
-      mm[j] = fmaf(omb1, gr - mm[j], mm[j]);           // exp_avg.lerp_(grad, 1 - beta1)
-      vv[j] = fmaf(omb2, gr * gr, vv[j] * b2);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-      const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-      pp[j] = pp[j] - step_size * (mm[j] / denom);     // param.addcdiv_(exp_avg, denom, value=-step_size)
-    }
-    V4<float>::store(p + i * 4, pp); V4<float>::store(m + i * 4, mm); V4<float>::store(v + i * 4, vv);
-    if (pb) V4<bf16_t>::store(pb + i * 4, pp);
-  }
-  // tail (n % 4)
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long i = (n4 << 2) + threadIdx.x;
-    const float gr = grad_times<DEV>(g[i], gscale);
-    float pp = p[i] * decay;
-    const float mm = fmaf(omb1, gr - m[i], m[i]);
-    const float vv = fmaf(omb2, gr * gr, v[i] * b2);
-    pp = pp - step_size * (mm / (sqrtf(vv) / bc2_sqrt + eps));
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (pb) pb[i] = f32_to_bf16(pp);
-  }
-}
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
-                                                    float b2, float eps, float decay, float omb1, float omb2,
-                                                    float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
-  adamw_body<false>(p, g, m, v, pb, n, lr, b1, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, gscale, skip, nullptr);
-}
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, bf16_t* __restrict__ pb, long n, float lr, float b1,
-                                                        float b2, float eps, float decay, float omb1, float omb2,
-                                                        float step_size, float bc2_sqrt, const float* __restrict__ sdev,
-                                                        const int* __restrict__ skip) {
-  adamw_body<true>(p, g, m, v, pb, n, lr, b1, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, 0.f, skip, sdev);
-}
-// scale_dev != NULL: the *_dev entry point (the factor is read on the device and takes grad_scale's place)
-static int adamw_flat_launch(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int32_t step, float grad_scale, const float* scale_dev, const int32_t* skip, void* stream) {
-  if (n <= 0) return 0;
-  if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
-  if (scale_dev)
-    hipLaunchKernelGGL(adamw_dev_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                       (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, scale_dev, skip);
-  else
-    hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16,
-                       (long)n, lr, beta1, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
-  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, skip, stream);
-}
-extern "C" int muse_adamw_flat_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                                   float beta2, float eps, float weight_decay, int32_t step, const float* scale_dev, const int32_t* skip,
-                                   void* stream) {
-  if (!scale_dev) return MUSE_ERR_BAD_ARG;
-  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, 0.f, scale_dev, skip, stream);
-}
-
-// Multi-tensor form: ONE launch over a device-side table of tensors (models whose parameters are ordinary tensors, not views of
-// a flat buffer: MaskGiTUViT has ~500, and 500 launches of 9 us each were 4 % of its step).  The table is 6 x int64 per tensor:
-// {p, g, m, v, p_bf16 or 0, n}; `chunk_first[t]` = index of tensor t's first 4096-element chunk (exclusive prefix sum, nt + 1
-// entries); block b owns chunk b: binary search -> (tensor, offset).  Same arithmetic, same order, as adamw_kernel.
-template <bool DEV> __device__ __forceinline__ void adamw_multi_body(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                          float b2, float eps, float decay, float omb1, float omb2,
-                                                          float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip,
-                                                          const float* __restrict__ sdev) {
-  ADAMW_PROLOGUE
-  int lo = 0, hi = nt;                    // largest t with chunk_first[t] <= blockIdx.x
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
-  const long* e = table + (long)lo * 6;
-  float* p = (float*)e[0]; const float* g = (const float*)e[1]; float* m = (float*)e[2]; float* v = (float*)e[3];
-  bf16_t* pb = (bf16_t*)e[4];
-  const long n = e[5], base = (long)((int)blockIdx.x - chunk_first[lo]) * 4096;
-  const long end = base + 4096 < n ? base + 4096 : n;
-  const bool vec = !((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) && !(((uintptr_t)pb) & 7);
-  if (vec) {
-    for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) {
-      float pp[4], gg[4], mm[4], vv[4];
-      V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gr = grad_times<DEV>(gg[j], gscale);
-        pp[j] = pp[j] * decay;
-        mm[j] = fmaf(omb1, gr - mm[j], mm[j]);
-        vv[j] = fmaf(omb2, gr * gr, vv[j] * b2);
-        const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-        pp[j] = pp[j] - step_size * (mm[j] / denom);
-      }
-      V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
-      if (pb) V4<bf16_t>::store(pb + i, pp);
-    }
-  }
-  // scalar: the whole chunk when a pointer is unaligned, else the (n % 4) tail of the tensor's last chunk
-  const long s0 = vec ? base + ((end - base) & ~3L) : base;
-  for (long i = s0 + threadIdx.x; i < end; i += 256) {
-    const float gr = grad_times<DEV>(g[i], gscale);
-    float pp = p[i] * decay;
-    const float mm = fmaf(omb1, gr - m[i], m[i]);
-    const float vv = fmaf(omb2, gr * gr, v[i] * b2);
-    pp = pp - step_size * (mm / (sqrtf(vv) / bc2_sqrt + eps));
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (pb) pb[i] = f32_to_bf16(pp);
-  }
-}
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                          float b2, float eps, float decay, float omb1, float omb2,
-                                                          float step_size, float bc2_sqrt, float gscale, const int* __restrict__ skip) {
-  adamw_multi_body<false>(table, chunk_first, nt, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, gscale, skip, nullptr);
-}
-__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                              float b2, float eps, float decay, float omb1, float omb2, float step_size,
-                                                              float bc2_sqrt, const float* __restrict__ sdev, const int* __restrict__ skip) {
-  adamw_multi_body<true>(table, chunk_first, nt, b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, 0.f, skip, sdev);
-}
-// Exponential moving average of the weights (reference muse/modeling_ema.py:118-137, called right behind the optimizer step,
-// training/train_muse.py:779-780): shadow -= (1 - decay) * (shadow - param) over EVERY tracked tensor in one launch - the reference
-// issues three elementwise kernels per tensor.  Table: 4 x int64 per tensor {shadow, param, n, mode}; mode 0 = the update, mode 1 =
-// plain copy (a parameter with requires_grad == False, :134-135).  chunk_first as in adamw_multi_kernel.  The three roundings of the
-// reference's expression (subtract, multiply, subtract - each an f32 tensor op there) are kept: no contraction into an fma.
-__device__ __forceinline__ float ema_update1(float s, float p, float omd) {
-#pragma clang fp contract(off)
-  const float t = s - p;
-  const float u = omd * t;
-  return s - u;
-}
-__global__ __launch_bounds__(256) void ema_multi_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt, float omd) {
-  int lo = 0, hi = nt;
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
-  const long* e = table + (long)lo * 4;
-  float* s = (float*)e[0]; const float* p = (const float*)e[1];
-  const long n = e[2], base = (long)((int)blockIdx.x - chunk_first[lo]) * 4096;
-  const bool copy = e[3] != 0;
-  const long end = base + 4096 < n ? base + 4096 : n;
-  const bool vec = !((((uintptr_t)s) | ((uintptr_t)p)) & 15);
-  if (vec) {
-    for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) {
-      float ss[4], pp[4];
-      V4<float>::load(s + i, ss); V4<float>::load(p + i, pp);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ss[j] = copy ? pp[j] : ema_update1(ss[j], pp[j], omd);
-      V4<float>::store(s + i, ss);
-    }
-  }
-  const long s0 = vec ? base + ((end - base) & ~3L) : base;
-  for (long i = s0 + threadIdx.x; i < end; i += 256) s[i] = copy ? p[i] : ema_update1(s[i], p[i], omd);
-}
-extern "C" int muse_ema_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                              float one_minus_decay, void* stream) {
-  if (num_tensors <= 0 || num_chunks <= 0) return 0;
-  if (!table || !chunk_first) return MUSE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(ema_multi_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first, num_tensors,
-                     one_minus_decay);
-  return (int)hipGetLastError();
-}
-
-static int adamw_multi_launch(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const float* scale_dev,
-                              const int32_t* skip, void* stream) {
-  if (num_tensors <= 0 || num_chunks <= 0) return 0;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-  const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
-  if (scale_dev)
-    hipLaunchKernelGGL(adamw_multi_dev_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
-                       num_tensors, beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, scale_dev, skip);
-  else
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first, num_tensors,
-                       beta2, eps, decay, omb1, omb2, step_size, bc2_sqrt, grad_scale, skip);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_adamw_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
-                                float beta1, float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
-  return adamw_multi_launch(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, skip,
-                            stream);
-}
-extern "C" int muse_adamw_multi_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, float lr,
-                                    float beta1, float beta2, float eps, float weight_decay, int32_t step, const float* scale_dev,
-                                    const int32_t* skip, void* stream) {
-  if (!scale_dev) return MUSE_ERR_BAD_ARG;
-  return adamw_multi_launch(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, 0.f, scale_dev, skip, stream);
-}
-
-// ---- parameter groups (training/train_muse.py:425-445: no weight decay on bias / LayerNorm / embedding weights) ---------------------
-// torch.optim semantics: every group carries its own lr / betas / eps / weight_decay.  The per-group constants are computed on the
-// host exactly like muse_adamw_flat computes its single set and travel BY VALUE in the kernel arguments (they change every step with
-// the lr schedule: no host -> device copy).  Same arithmetic, same order as adamw_kernel: a one-group call is bit-identical to it.
-#define MUSE_ADAMW_MAX_GROUPS 8
-struct AdamHyper { float b2, eps, decay, omb1, omb2, step_size, bc2_sqrt, pad; };
-struct AdamGroups { AdamHyper h[MUSE_ADAMW_MAX_GROUPS]; };
-static inline int adam_fill_groups(AdamGroups& G, const float* hyper, int ngroups, int step) {
-  if (ngroups < 1 || ngroups > MUSE_ADAMW_MAX_GROUPS || !hyper) return MUSE_ERR_BAD_ARG;
-  for (int k = 0; k < ngroups; ++k) {
-    const float lr = hyper[k * 5 + 0], beta1 = hyper[k * 5 + 1], beta2 = hyper[k * 5 + 2], eps = hyper[k * 5 + 3], wd = hyper[k * 5 + 4];
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    AdamHyper& h = G.h[k];
-    h.step_size = (float)((double)lr / bc1);
-    h.bc2_sqrt = (float)sqrt(bc2);
-    h.decay = (float)(1.0 - (double)lr * (double)wd);
-    h.omb1 = (float)(1.0 - (double)beta1); h.omb2 = (float)(1.0 - (double)beta2);
-    h.b2 = beta2; h.eps = eps; h.pad = 0.f;
-  }
-  for (int k = ngroups; k < MUSE_ADAMW_MAX_GROUPS; ++k) G.h[k] = G.h[0];
-  return 0;
-}
-__device__ __forceinline__ void adam_update1(float& pp, float gr, float& mm, float& vv, const AdamHyper& h) {
-  pp = pp * h.decay;
-  mm = fmaf(h.omb1, gr - mm, mm);
-  vv = fmaf(h.omb2, gr * gr, vv * h.b2);
-  const float denom = sqrtf(vv) / h.bc2_sqrt + h.eps;
-  pp = pp - h.step_size * (mm / denom);
-}
-// Flat buffer cut into segments: seg_end[s] (ascending, ABSOLUTE element offsets in the flat buffer) closes segment s, seg_group[s]
-// names its parameter group.  The call covers elements [base, base + n) of the flat buffer (p, g, m, v, pb point at element `base`):
-// any slice, so the in-backward / behind-the-all-reduce range updates share the table.  Block b owns elements [4096 b, 4096 b + 4096)
-// of the slice; its first / last segment are found once per block (uniform binary searches), a lane then only steps inside that range.
-template <bool DEV> __device__ __forceinline__ void adamw_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
-                                                           const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
-                                                           const AdamGroups& G, float gscale, const int* __restrict__ skip,
-                                                           const float* __restrict__ sdev) {
-  ADAMW_PROLOGUE
-  const long c0 = (long)blockIdx.x * 4096, c1 = c0 + 4096 < n ? c0 + 4096 : n;
-  auto seg_of = [&](long pos) {   // smallest s with seg_end[s] > pos (positions beyond the last end: the last segment)
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (seg_end[mid] > pos) hi = mid; else lo = mid + 1; }
-    return lo;
-  };
-  const int s0 = seg_of(base + c0), s1 = seg_of(base + c1 - 1);
-  if (s0 == s1) {                 // the common case: one group for the whole chunk
-    const AdamHyper h = G.h[seg_group[s0] & (MUSE_ADAMW_MAX_GROUPS - 1)];
-    long i = c0 + threadIdx.x * 4;
-    for (; i + 3 < c1; i += 1024) {
-      float pp[4], gg[4], mm[4], vv[4];
-      V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) adam_update1(pp[j], grad_times<DEV>(gg[j], gscale), mm[j], vv[j], h);
-      V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
-      if (pb) V4<bf16_t>::store(pb + i, pp);
-    }
-    const long t0 = c0 + ((c1 - c0) & ~3L);
-    for (long k = t0 + threadIdx.x; k < c1; k += 256) {
-      float pp = p[k], mm = m[k], vv = v[k];
-      adam_update1(pp, grad_times<DEV>(g[k], gscale), mm, vv, h);
-      p[k] = pp; m[k] = mm; v[k] = vv;
-      if (pb) pb[k] = f32_to_bf16(pp);
-    }
-    return;
-  }
-  for (long k = c0 + threadIdx.x; k < c1; k += 256) {   // a chunk with a segment boundary inside: element-wise, group per element
-    int s = s0;
-    while (s < s1 && seg_end[s] <= base + k) ++s;
-    const AdamHyper h = G.h[seg_group[s] & (MUSE_ADAMW_MAX_GROUPS - 1)];
-    float pp = p[k], mm = m[k], vv = v[k];
-    adam_update1(pp, grad_times<DEV>(g[k], gscale), mm, vv, h);
-    p[k] = pp; m[k] = mm; v[k] = vv;
-    if (pb) pb[k] = f32_to_bf16(pp);
-  }
-}
-__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
-                                                           const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
-                                                           AdamGroups G, float gscale, const int* __restrict__ skip) {
-  adamw_groups_body<false>(p, g, m, v, pb, n, base, seg_end, seg_group, nseg, G, gscale, skip, nullptr);
-}
-__global__ __launch_bounds__(256) void adamw_groups_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, bf16_t* __restrict__ pb, long n, long base,
-                                                               const long* __restrict__ seg_end, const int* __restrict__ seg_group, int nseg,
-                                                               AdamGroups G, const float* __restrict__ sdev, const int* __restrict__ skip) {
-  adamw_groups_body<true>(p, g, m, v, pb, n, base, seg_end, seg_group, nseg, G, 0.f, skip, sdev);
-}
-static int adamw_flat_groups_launch(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base, const int64_t* seg_end,
-                                    const int32_t* seg_group, int32_t nseg, const float* group_hyper, int32_t ngroups, int32_t step,
-                                    float grad_scale, const float* scale_dev, const int32_t* skip, void* stream) {
-  if (n <= 0) return 0;
-  if (nseg < 1 || !seg_end || !seg_group) return MUSE_ERR_BAD_ARG;
-  if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
-  if (p_bf16 && (((uintptr_t)p_bf16) & 7)) return MUSE_ERR_ALIGN;
-  AdamGroups G;
-  const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
-  if (rc) return rc;
-  if (scale_dev)
-    hipLaunchKernelGGL(adamw_groups_dev_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, scale_dev, skip);
-  else
-    hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (bf16_t*)p_bf16, (long)n, (long)base, (const long*)seg_end, seg_group, nseg, G, grad_scale, skip);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_adamw_flat_groups(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
-                                      const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
-                                      int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip, void* stream) {
-  return adamw_flat_groups_launch(p, g, m, v, p_bf16, n, base, seg_end, seg_group, nseg, group_hyper, ngroups, step, grad_scale, nullptr, skip,
-                                  stream);
-}
-extern "C" int muse_adamw_flat_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, int64_t base,
-                                          const int64_t* seg_end, const int32_t* seg_group, int32_t nseg, const float* group_hyper,
-                                          int32_t ngroups, int32_t step, const float* scale_dev, const int32_t* skip, void* stream) {
-  if (!scale_dev) return MUSE_ERR_BAD_ARG;
-  return adamw_flat_groups_launch(p, g, m, v, p_bf16, n, base, seg_end, seg_group, nseg, group_hyper, ngroups, step, 0.f, scale_dev, skip,
-                                  stream);
-}
-// Multi-tensor form with groups: `table` is 7 x int64 per tensor {p, g, m, v, p_bf16 or 0, n, group | lo_plane_distance << 8}
-// (lo_plane_distance < 0: p_bf16 receives an IEEE-half copy).
-template <bool DEV> __device__ __forceinline__ void adamw_multi_groups_body(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                                 const AdamGroups& G, float gscale, const int* __restrict__ skip,
-                                                                 const float* __restrict__ sdev) {
-  ADAMW_PROLOGUE
-  int lo = 0, hi = nt;
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (chunk_first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
-  const long* e = table + (long)lo * 7;
-  float* p = (float*)e[0]; const float* g = (const float*)e[1]; float* m = (float*)e[2]; float* v = (float*)e[3];
-  bf16_t* pb = (bf16_t*)e[4];
-  const AdamHyper h = G.h[(int)e[6] & (MUSE_ADAMW_MAX_GROUPS - 1)];
-  // column 6 above bit 8: p_bf16 is the HI plane of the parameter's bf16x3 operand planes and the lo plane sits that many elements behind
-  // it (hi = bf16(p), lo = bf16(p - hi): split_f2bb_kernel's arithmetic) - the planes the next step's weight GEMMs read; 0 = a plain bf16 copy
-  // ... and a NEGATIVE value there: p_bf16 is an IEEE-half copy instead (the weight's operand image of the "f16" compute mode)
-  const long plo_raw = e[6] >> 8;
-  const bool half_copy = plo_raw < 0;
-  const long plo = half_copy ? 0 : plo_raw;
-  const long n = e[5], base = (long)((int)blockIdx.x - chunk_first[lo]) * 4096;
-  const long end = base + 4096 < n ? base + 4096 : n;
-  const bool vec = !((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) && !(((uintptr_t)pb) & 7) && !(plo & 3);
-  if (vec) {
-    for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) {
-      float pp[4], gg[4], mm[4], vv[4];
-      V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) adam_update1(pp[j], grad_times<DEV>(gg[j], gscale), mm[j], vv[j], h);
-      V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
-      if (pb && half_copy) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        *(h4*)(pb + i) = h4{(_Float16)pp[0], (_Float16)pp[1], (_Float16)pp[2], (_Float16)pp[3]};
-      } else if (pb) {
-        V4<bf16_t>::store(pb + i, pp);
-        if (plo) {
-          float rr[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) rr[j] = pp[j] - bf16_to_f32(f32_to_bf16(pp[j]));
-          V4<bf16_t>::store(pb + plo + i, rr);
-        }
-      }
-    }
-  }
-  const long s0 = vec ? base + ((end - base) & ~3L) : base;
-  for (long i = s0 + threadIdx.x; i < end; i += 256) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    adam_update1(pp, grad_times<DEV>(g[i], gscale), mm, vv, h);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (pb && half_copy) {
-      ((_Float16*)pb)[i] = (_Float16)pp;
-    } else if (pb) {
-      const bf16_t hi = f32_to_bf16(pp);
-      pb[i] = hi;
-      if (plo) pb[plo + i] = f32_to_bf16(pp - bf16_to_f32(hi));
-    }
-  }
-}
-__global__ __launch_bounds__(256) void adamw_multi_groups_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                                 AdamGroups G, float gscale, const int* __restrict__ skip) {
-  adamw_multi_groups_body<false>(table, chunk_first, nt, G, gscale, skip, nullptr);
-}
-__global__ __launch_bounds__(256) void adamw_multi_groups_dev_kernel(const long* __restrict__ table, const int* __restrict__ chunk_first, int nt,
-                                                                     AdamGroups G, const float* __restrict__ sdev,
-                                                                     const int* __restrict__ skip) {
-  adamw_multi_groups_body<true>(table, chunk_first, nt, G, 0.f, skip, sdev);
-}
-static int adamw_multi_groups_launch(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                                     const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const float* scale_dev,
-                                     const int32_t* skip, void* stream) {
-  if (num_tensors <= 0 || num_chunks <= 0) return 0;
-  AdamGroups G;
-  const int rc = adam_fill_groups(G, group_hyper, ngroups, step);
-  if (rc) return rc;
-  if (scale_dev)
-    hipLaunchKernelGGL(adamw_multi_groups_dev_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
-                       num_tensors, G, scale_dev, skip);
-  else
-    hipLaunchKernelGGL(adamw_multi_groups_kernel, dim3(num_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, chunk_first,
-                       num_tensors, G, grad_scale, skip);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_adamw_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                                       const float* group_hyper, int32_t ngroups, int32_t step, float grad_scale, const int32_t* skip,
-                                       void* stream) {
-  return adamw_multi_groups_launch(table, chunk_first, num_tensors, num_chunks, group_hyper, ngroups, step, grad_scale, nullptr, skip, stream);
-}
-extern "C" int muse_adamw_multi_groups_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
-                                           const float* group_hyper, int32_t ngroups, int32_t step, const float* scale_dev,
-                                           const int32_t* skip, void* stream) {
-  if (!scale_dev) return MUSE_ERR_BAD_ARG;
-  return adamw_multi_groups_launch(table, chunk_first, num_tensors, num_chunks, group_hyper, ngroups, step, 0.f, scale_dev, skip, stream);
 }
 
 // f32 -> the two bf16 planes of the bf16x3 product scheme: hi = bf16(x), lo = bf16(x - hi) (x ~= hi + lo to 2^-16 relative); the

@@ -58,7 +58,7 @@ class EMAModel:
         key = tuple((s.data_ptr(), p.data_ptr(), p.numel(), p.requires_grad) for s, p in zip(self.shadow_params, params))
         if self._pairs is not None and self._pairs["key"] == key:
             return self._pairs
-        entries, first = [], [0]
+        entries, sizes = [], []
         for s, p in zip(self.shadow_params, params):
             if not (s.is_cuda and p.is_cuda):
                 raise MuseHipError("EMAModel.step (MI355X build) has no CPU path: move the model and the EMA (`ema.to(device)`) to the GPU")
@@ -66,9 +66,10 @@ class EMAModel:
                 raise MuseHipError("EMAModel.step: shadow and parameter must be contiguous f32 tensors of one shape")
             if p.numel():
                 entries += [s.data_ptr(), p.data_ptr(), p.numel(), 0 if p.requires_grad else 1]      # mode 1: frozen parameter, plain copy (:134-135)
-                first.append(first[-1] + (p.numel() + 4095) // 4096)
+                sizes.append(p.numel())
+        first, chunks = ops.chunk_first(sizes)
         dev = self.shadow_params[0].device
-        self._pairs = dict(key=key, n=len(first) - 1, chunks=first[-1],
+        self._pairs = dict(key=key, n=len(sizes), chunks=chunks,
                            table=torch.tensor(entries, dtype=torch.int64, device=dev) if entries else None,
                            first=torch.tensor(first, dtype=torch.int32, device=dev))
         return self._pairs

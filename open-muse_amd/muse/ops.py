@@ -1583,28 +1583,27 @@ def soft_ce_bwd(logits, labels, soft, seq1, lse, psum, loss_out, grad_out, out_d
 # untouched when it is non-zero (training.FusedAdamW's guard)
 # scale_dev (every adamw_*): None, or a device f32 (gradnorm_finalize's `scale`) the kernel multiplies the gradient by INSTEAD of
 # grad_scale (the muse_adamw_*_dev entry points: gradient clipping without a host round trip)
+def _adamw_call(name, args, grad_scale, skip, scale_dev, prof=None):
+    """muse_<name> (the host's grad_scale) or muse_<name>_dev (scale_dev); prof: the parameter tensor and its bf16 copy, to report to the profiler"""
+    name = "muse_" + name + ("_dev" if scale_dev is not None else "")
+    e0 = _prof_begin() if prof else None
+    check(getattr(lib(), name)(*args, float(grad_scale) if scale_dev is None else scale_dev.data_ptr(), ptr(skip), stream()), name)
+    if prof:
+        _prof_end(e0, "adamw", 28.0 * prof[0].numel() + (2.0 * prof[0].numel() if prof[1] is not None else 0.0), "byte")
+
+
 def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None, scale_dev=None):
     require_gpu(p, g, m, v, scale_dev)
-    e0 = _prof_begin()
-    if scale_dev is not None:
-        check(lib().muse_adamw_flat_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
-                                        beta2, eps, weight_decay, step, scale_dev.data_ptr(), ptr(skip), stream()), "muse_adamw_flat_dev")
-    else:
-        check(lib().muse_adamw_flat(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1,
-                                    beta2, eps, weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_flat")
-    _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
+    _adamw_call("adamw_flat", (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), lr, beta1, beta2, eps,
+                               weight_decay, step), grad_scale, skip, scale_dev, prof=(p, p_bf16))
 
 
 def adamw_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None,
                 scale_dev=None):
     """one AdamW launch over a device-side table of tensors (muse_adamw_multi; training.FusedAdamW builds the table)"""
     require_gpu(table, chunk_first, scale_dev)
-    if scale_dev is not None:
-        check(lib().muse_adamw_multi_dev(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
-                                         weight_decay, step, scale_dev.data_ptr(), ptr(skip), stream()), "muse_adamw_multi_dev")
-        return
-    check(lib().muse_adamw_multi(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
-                                 weight_decay, step, grad_scale, ptr(skip), stream()), "muse_adamw_multi")
+    _adamw_call("adamw_multi", (table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), lr, beta1, beta2, eps,
+                                weight_decay, step), grad_scale, skip, scale_dev)
 
 
 def ema_multi(table, chunk_first, num_tensors, num_chunks, one_minus_decay):
@@ -1632,19 +1631,9 @@ def adamw_flat_groups(p, g, m, v, p_bf16, base, seg_end, seg_group, groups, step
     require_gpu(p, g, m, v, seg_end, seg_group, scale_dev)
     import ctypes
     hy = _group_hyper(groups)
-    e0 = _prof_begin()
-    if scale_dev is not None:
-        check(lib().muse_adamw_flat_groups_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
-                                               seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()),
-                                               ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), scale_dev.data_ptr(), ptr(skip),
-                                               stream()), "muse_adamw_flat_groups_dev")
-        _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
-        return
-    check(lib().muse_adamw_flat_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
-                                       seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()),
-                                       ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
-          "muse_adamw_flat_groups")
-    _prof_end(e0, "adamw", 28.0 * p.numel() + (2.0 * p.numel() if p_bf16 is not None else 0.0), "byte")
+    _adamw_call("adamw_flat_groups", (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), p.numel(), int(base),
+                                      seg_end.data_ptr(), seg_group.data_ptr(), int(seg_end.numel()), ctypes.cast(hy, ctypes.c_void_p),
+                                      len(groups), int(step)), grad_scale, skip, scale_dev, prof=(p, p_bf16))
 
 
 def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step, grad_scale=1.0, skip=None, scale_dev=None):
@@ -1652,18 +1641,21 @@ def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step
     require_gpu(table, chunk_first, scale_dev)
     import ctypes
     hy = _group_hyper(groups)
-    if scale_dev is not None:
-        check(lib().muse_adamw_multi_groups_dev(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
-                                                ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), scale_dev.data_ptr(), ptr(skip),
-                                                stream()), "muse_adamw_multi_groups_dev")
-        return
-    check(lib().muse_adamw_multi_groups(table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
-                                        ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step), float(grad_scale), ptr(skip), stream()),
-          "muse_adamw_multi_groups")
+    _adamw_call("adamw_multi_groups", (table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
+                                       ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step)), grad_scale, skip, scale_dev)
 
 
 # ---- gradient clipping by global L2 norm / per-parameter gradient norms (csrc/gradnorm.hip; training.GradNorm drives these) -------------
 GRADNORM_CHUNK = 4096     # elements per f64 partial, counted from each parameter's own start (GN_CHUNK of csrc/gradnorm.hip, the AdamW chunk)
+
+
+def chunk_first(sizes):
+    """the chunk tables of the chunked multi-tensor kernels (AdamW, EMA, gradient norm): exclusive prefix sum of ceil(n / GRADNORM_CHUNK)
+    over the tensors' element counts -> (list of len(sizes) + 1 entries, total number of chunks)"""
+    first = [0]
+    for n in sizes:
+        first.append(first[-1] + (n + GRADNORM_CHUNK - 1) // GRADNORM_CHUNK)
+    return first, first[-1]
 
 
 def gradnorm_flat(g_flat, base, n, ptab_host, chunk_first_host, ptab, chunk_first, slab):

@@ -210,14 +210,12 @@ class _FlatNormState:
         flat = model.flat_params()
         order = model._param_order()
         sizes = [p.numel() for p in order]
-        first = [0]
-        for n in sizes:
-            first.append(first[-1] + (n + ops.GRADNORM_CHUNK - 1) // ops.GRADNORM_CHUNK)
+        first, self.nchunks = ops.chunk_first(sizes)
         self.key = (flat.device, tuple(model._offsets), tuple(sizes))
         self.ptab_host = torch.tensor([[o, n] for o, n in zip(model._offsets, sizes)], dtype=torch.int64)
         self.first_host = torch.tensor(first, dtype=torch.int32)
         self.ptab, self.first = self.ptab_host.to(flat.device), self.first_host.to(flat.device)
-        self.nt, self.nchunks = len(sizes), first[-1]
+        self.nt = len(sizes)
         self.slab = torch.zeros(self.nchunks + self.nt + 1, dtype=torch.float64, device=flat.device)
 
     @staticmethod
@@ -260,14 +258,14 @@ def _multi_norm(table, chunk_first, nt, nchunks, slab, grad_scale, max_norm):
 def _grad_table(grads):
     """device pointer table in muse_adamw_multi's layout (only the gradient pointer and n filled) for a list of gradient tensors
     -> (table, chunk_first, nchunks).  One (pageable) host -> device copy: the optimizer's own path keeps its pinned staging."""
-    rows, first = [], [0]
+    rows = []
     for g in grads:
         if g.dtype != torch.float32 or not g.is_contiguous():
             raise MuseHipError("muse.clip_grad_norm_ / grad_norms: gradients must be contiguous float32 tensors")
         rows.append((0, g.data_ptr(), 0, 0, 0, g.numel()))
-        first.append(first[-1] + (g.numel() + ops.GRADNORM_CHUNK - 1) // ops.GRADNORM_CHUNK)
+    first, nchunks = ops.chunk_first(g.numel() for g in grads)
     dev = grads[0].device
-    return torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(first, dtype=torch.int32).to(dev), first[-1]
+    return torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(first, dtype=torch.int32).to(dev), nchunks
 
 
 def _norm_target(parameters_or_model):
@@ -708,12 +706,7 @@ class FusedAdamW(torch.optim.Optimizer):
             ht, hf, ev = self._stage[self._stage_i]
             self._stage_i ^= 1
             ev.synchronize()      # the copy issued from this staging buffer two rebuilds ago has run
-            nchunks = 0
-            first = [0] * (nt + 1)
-            for i, r in enumerate(rows):
-                first[i] = nchunks
-                nchunks += (r[5] + 4095) // 4096
-            first[nt] = nchunks
+            first, nchunks = ops.chunk_first(r[5] for r in rows)
             ht[:nt].copy_(torch.tensor(rows, dtype=torch.int64))
             hf[:nt + 1].copy_(torch.tensor(first, dtype=torch.int32))
             self._table[:nt].copy_(ht[:nt], non_blocking=True)
