@@ -648,6 +648,40 @@ int muse_layernorm_bias_fwd(const float* x, const float* w, const float* b, void
                             float eps, void* stream);
 int muse_eos_index(const int64_t* ids, int64_t* idx, int64_t* flat_idx, int32_t batch, int32_t seq, int64_t eos_token_id, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Paella VQ tokenizer (muse/modeling_paella_vq.py, `vq_model.type: "paella_vq"`).  Forward only, f32, channels-last rows
+ * [batch*H*W, C] with C % 4 == 0.  Every element offset inside these kernels is 64-bit; int32 arguments are sides and channel counts.
+ * (csrc/paella.hip)
+ * muse_paella_mix_fwd: the first half of ResBlock.forward (:141-142) over x [batch*H*W, C], C <= 1024:
+ *     y = x + g2 * (dwconv3x3_replicate(LN(x) * (1 + g0) + g1) + bias)
+ *   LN = LayerNorm over the C channels of a pixel, no affine, eps 1e-6, biased variance; the depthwise 3x3 reads its neighbours with
+ *   edge replication (ReplicationPad2d(1): an out-of-range coordinate clamps to the border, H == 1 / W == 1 included).  w9 [9][C]
+ *   (tap-major: depthwise.1.weight [C, 1, 3, 3] permuted once), bias [C], gammas = DEVICE pointer to the block's six floats (g0, g1, g2
+ *   are read by the kernel: no host read).  stats: [batch*H*W, 2] f32 workspace (mean, rstd of every pixel, written by a first pass; the
+ *   normalised tensor itself is never written).  y must not alias x.
+ * muse_patch_rows_nhwc: y[(b, oy, ox)][(ky, kx, c)] = x[b, oy*stride - pad_top + ky, ox*stride - pad_left + kx, c], zero outside the
+ *   image; KS 2 | 4; y [batch*Hout*Wout, KS*KS*C].  Conv2d(4, 2, 1) (:163) = this with (4, 2, 1, 1) + one product with K = 16 Cin;
+ *   ConvTranspose2d(4, 2, 1) (:185-187) = four output phases (a, b), each this with KS 2, stride 1, pad (1 - a, 1 - b), Hout = H,
+ *   Wout = W + one product with the taps (3 - a - 2 ky, 3 - b - 2 kx), interleaved by muse_space_to_depth2_nhwc(inverse).
+ * muse_vq_nearest_small: idx[r] = argmin_j sum_k (z[r, k] - codebook[j, k])^2 for D <= 8 (VectorQuantizer.get_code :103-109 at
+ *   c_latent 4), the sum taken directly with fma in ascending k; the lowest index wins among exactly equal distances.  z [N, D] f32 with
+ *   row stride ldz, codebook [Kc, D] f32 contiguous, idx int64 [N], dist (may be NULL) f32 [N] = the winning squared distance.  No
+ *   [N, Kc] distance matrix exists.
+ * muse_paella_in_block: in_block (:159) = PixelUnshuffle(2) + 1x1 convolution 12 -> C of img [batch, 3, H, W] f32 NCHW (H, W even)
+ *   -> y [batch*(H/2)*(W/2), C]; w12 [12][C] (in_block.1.weight transposed; unshuffled channel k = c*4 + dy*2 + dx), bias [C].
+ * muse_paella_out_block: out_block (:190-193) = 1x1 convolution C -> 12 + PixelShuffle(2): x [batch*(H/2)*(W/2), C] -> img [batch, 3,
+ *   H, W] f32 NCHW; w12 [12][C] (out_block.0.weight as it is), bias [12].  H, W are the IMAGE sides in both. */
+int muse_paella_mix_fwd(const float* x, const float* w9, const float* bias, const float* gammas, float* stats, float* y, int32_t batch,
+                        int32_t H, int32_t W, int32_t C, void* stream);
+int muse_patch_rows_nhwc(const float* x, float* y, int32_t batch, int32_t H, int32_t W, int32_t C, int32_t KS, int32_t stride,
+                         int32_t pad_top, int32_t pad_left, int32_t Hout, int32_t Wout, void* stream);
+int muse_vq_nearest_small(const float* z, int64_t ldz, const float* codebook, int64_t* idx, float* dist, int64_t N, int32_t D, int32_t Kc,
+                          void* stream);
+int muse_paella_in_block(const float* img, const float* w12, const float* bias, float* y, int32_t batch, int32_t H, int32_t W, int32_t C,
+                         void* stream);
+int muse_paella_out_block(const float* x, const float* w12, const float* bias, float* img, int32_t batch, int32_t H, int32_t W, int32_t C,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2465,3 +2465,94 @@ def eos_index(ids, eos_token_id):
     flat = torch.empty(B, dtype=torch.int64, device=ids.device)
     check(lib().muse_eos_index(ids.data_ptr(), idx.data_ptr(), flat.data_ptr(), B, S, int(eos_token_id), stream()), "muse_eos_index")
     return idx, flat
+
+
+# ---- Paella VQ tokenizer (csrc/paella.hip) : f32 forward ops on channels-last rows ---------------------------------------------
+def _f32_operand(what, t, shape):
+    """the kernels read their weights through raw pointers: a transposed, strided or non-f32 operand would be read in the wrong order"""
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _hip.MuseHipError(f"{what} must be a contiguous f32 tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)} "
+                                f"(contiguous: {t.is_contiguous()})")
+
+
+def paella_mix_fwd(x, w9, bias, gammas, B, H, W):
+    """y = x + g2 * (dwconv3x3_replicate(LN(x) * (1 + g0) + g1) + bias): x [B*H*W, C] f32, w9 [9, C] (tap-major), gammas = the block's
+    six floats ON THE DEVICE (read by the kernel)"""
+    require_gpu(x, w9, bias, gammas)
+    rows, C_ = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or rows != B * H * W or gammas.numel() < 3:
+        raise _hip.MuseHipError("paella_mix_fwd: x is a contiguous f32 [B*H*W, C] tensor, gammas holds g0, g1, g2")
+    _f32_operand("paella_mix_fwd: w9", w9, (9, C_))
+    _f32_operand("paella_mix_fwd: bias", bias, (C_,))
+    if gammas.dtype != torch.float32 or not gammas.is_contiguous():
+        raise _hip.MuseHipError("paella_mix_fwd: gammas is a contiguous f32 tensor")
+    y = torch.empty_like(x)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+    e0 = _prof_begin()
+    check(lib().muse_paella_mix_fwd(x.data_ptr(), w9.data_ptr(), bias.data_ptr(), gammas.data_ptr(), stats.data_ptr(), y.data_ptr(), B, H, W,
+                                    C_, stream()), "muse_paella_mix_fwd")
+    _prof_end(e0, "paella_mix", _nbytes(x, x, y, stats, stats), "byte")
+    return y
+
+
+def patch_rows(x, B, H, W, C_, KS, stride, pad_top, pad_left, Hout, Wout):
+    """zero-padded KS x KS patches of x [B*H*W, C] f32 -> [B*Hout*Wout, KS*KS*C], patch element order (ky, kx, c)"""
+    require_gpu(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != B * H * W * C_:
+        raise _hip.MuseHipError("patch_rows: x is a contiguous f32 [B*H*W, C] tensor")
+    y = torch.empty((B * Hout * Wout, KS * KS * C_), dtype=torch.float32, device=x.device)
+    e0 = _prof_begin()
+    check(lib().muse_patch_rows_nhwc(x.data_ptr(), y.data_ptr(), B, H, W, C_, KS, stride, pad_top, pad_left, Hout, Wout, stream()),
+          "muse_patch_rows_nhwc")
+    _prof_end(e0, "patch_rows", _nbytes(x, y), "byte")
+    return y
+
+
+def vq_nearest_small(z_flat, codebook, return_dist=False):
+    """argmin_j sum_k (z_k - e_jk)^2 for codebook width D <= 8, distance and argmin in one kernel (no [N, Kc] matrix).
+    z_flat [N, D] f32 (row stride free), codebook [Kc, D] f32 -> int64 [N] (with return_dist also the winning squared distances)"""
+    require_gpu(z_flat, codebook)
+    N, D = z_flat.shape
+    if z_flat.dtype != torch.float32 or codebook.dtype != torch.float32 or codebook.shape[1] != D or z_flat.stride(1) != 1:
+        raise _hip.MuseHipError("vq_nearest_small: z [N, D] and codebook [Kc, D] are f32 with unit column stride")
+    _f32_operand("vq_nearest_small: codebook", codebook, (codebook.shape[0], D))
+    idx = torch.empty(N, dtype=torch.int64, device=z_flat.device)
+    dist = torch.empty(N, dtype=torch.float32, device=z_flat.device) if return_dist else None
+    e0 = _prof_begin()
+    check(lib().muse_vq_nearest_small(z_flat.data_ptr(), z_flat.stride(0), codebook.data_ptr(), idx.data_ptr(), ptr(dist), N, D,
+                                      codebook.shape[0], stream()), "muse_vq_nearest_small")
+    _prof_end(e0, "vq_nearest_small", _nbytes(z_flat, codebook, idx), "byte")
+    return (idx, dist) if return_dist else idx
+
+
+def paella_in_block(pixel_values, w12, bias):
+    """PixelUnshuffle(2) + 1x1 convolution 12 -> C of an NCHW f32 image batch [B, 3, H, W] -> rows [B*(H/2)*(W/2), C]; w12 [12, C]"""
+    require_gpu(pixel_values, w12, bias)
+    B, Ci, H, W = pixel_values.shape
+    if Ci != 3 or pixel_values.dtype != torch.float32 or not pixel_values.is_contiguous():
+        raise _hip.MuseHipError("paella_in_block: pixel_values is a contiguous f32 [B, 3, H, W] tensor")
+    C_ = w12.shape[-1]
+    _f32_operand("paella_in_block: w12", w12, (12, C_))
+    _f32_operand("paella_in_block: bias", bias, (C_,))
+    y = torch.empty((B * (H // 2) * (W // 2), C_), dtype=torch.float32, device=pixel_values.device)
+    e0 = _prof_begin()
+    check(lib().muse_paella_in_block(pixel_values.data_ptr(), w12.data_ptr(), bias.data_ptr(), y.data_ptr(), B, H, W, C_, stream()),
+          "muse_paella_in_block")
+    _prof_end(e0, "paella_in_block", _nbytes(pixel_values, y), "byte")
+    return y
+
+
+def paella_out_block(x, w12, bias, B, H, W):
+    """1x1 convolution C -> 12 + PixelShuffle(2): rows x [B*(H/2)*(W/2), C] f32 -> NCHW f32 image [B, 3, H, W]; w12 [12, C]"""
+    require_gpu(x, w12, bias)
+    rows, C_ = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or rows != B * (H // 2) * (W // 2):
+        raise _hip.MuseHipError("paella_out_block: x is a contiguous f32 [B*(H/2)*(W/2), C] tensor")
+    _f32_operand("paella_out_block: w12", w12, (12, C_))
+    _f32_operand("paella_out_block: bias", bias, (12,))
+    img = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+    e0 = _prof_begin()
+    check(lib().muse_paella_out_block(x.data_ptr(), w12.data_ptr(), bias.data_ptr(), img.data_ptr(), B, H, W, C_, stream()),
+          "muse_paella_out_block")
+    _prof_end(e0, "paella_out_block", _nbytes(x, img), "byte")
+    return img

@@ -198,12 +198,14 @@ class PipelineMuse:
             klass = MaskGiTUViT_v2 if str(cfg.get("_class_name", "")).startswith("MaskGiTUViT") else MaskGitTransformer
             return klass.from_pretrained(path, **kw)
 
-        def load_vae(path, **kw):           # likewise for the tokenizer (reference :320-329; MoVQ / Paella are not part of this build)
+        def load_vae(path, **kw):           # likewise for the tokenizer (reference :320-329; MoVQ is not part of this build)
+            from .modeling_paella_vq import PaellaVQModel
             from .modeling_taming_vqgan import VQGANModel
+            classes = {"MaskGitVQGAN": MaskGitVQGAN, "VQGANModel": VQGANModel, "PaellaVQModel": PaellaVQModel}
             name = str(MaskGitVQGAN.load_config(path, **kw).get("_class_name", "MaskGitVQGAN"))
-            if name not in ("MaskGitVQGAN", "VQGANModel"):
+            if name not in classes:
                 raise ValueError(f"Unknown VAE class: {name}")
-            return (VQGANModel if name == "VQGANModel" else MaskGitVQGAN).from_pretrained(path, **kw)
+            return classes[name].from_pretrained(path, **kw)
 
         if model_name_or_path is None and (vae_path is None or transformer_path is None or
                                            (text_encoder_path is None and not is_class_conditioned and text_encoder is None)):

@@ -1,8 +1,9 @@
-"""Names the reference's training scripts import from `muse` but whose models are outside this build's hot path (SURVEY.md section 2:
-"OUT OF SCOPE - not named in north_star"): the MoVQ and Paella tokenizers (muse/modeling_movq.py, muse/modeling_paella_vq.py).  The
-scripts import them unconditionally (training/train_muse.py:51-60, training/train_maskgit_imagenet.py:38) and pick one by the config's
-`model.vq_model.type`; the two built tokenizers are `maskgit_vqgan` (muse.MaskGitVQGAN) and `vqgan` (muse.VQGANModel).  Importing the
-names works; building one of these models says what is missing instead of computing something else."""
+"""Names the reference's training scripts import from `muse` that this module answers with refusing stubs: the MoVQ tokenizer
+(muse/modeling_movq.py; SURVEY.md section 2: "OUT OF SCOPE - not named in north_star") and the top-level name of the Paella tokenizer.
+The scripts import both unconditionally (training/train_muse.py:51-60, training/train_maskgit_imagenet.py:38) and pick one by the config's
+`model.vq_model.type`; the built tokenizers are `maskgit_vqgan` (muse.MaskGitVQGAN), `vqgan` (muse.VQGANModel) and `paella_vq`, which is
+built as muse.modeling_paella_vq.PaellaVQModel (bind it from there) while the name here stays the stub.  Importing the
+names works; building one of these stubs says what is missing instead of computing something else."""
 from __future__ import annotations
 
 from ._hip import MuseHipError
