@@ -682,6 +682,25 @@ int muse_paella_in_block(const float* img, const float* w12, const float* bias, 
 int muse_paella_out_block(const float* x, const float* w12, const float* bias, float* img, int32_t batch, int32_t H, int32_t W, int32_t C,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * MoVQ tokenizer (muse/modeling_movq.py, `vq_model.type: "movq"`): SpatialNorm (:21-49) over NHWC in one apply pass (csrc/movq.hip)
+ *     out = GroupNorm(x) * conv_y(nearest(zq)) + conv_b(nearest(zq)), then SiLU when apply_silu
+ * x [batch, H, W, C] f32; zq [batch, zh, zw, Z] f32 (the quantised latent, 1 <= Z <= 8; H % zh == 0 and W % zw == 0: output pixel
+ * (oy, ox) reads source pixel (oy / (H / zh), ox / (W / zw)), F.interpolate(mode="nearest") for integer factors; the two factors are
+ * independent); gamma / beta [C] the GroupNorm affine; wy [C][Z], by [C] = conv_y, wb [C][Z], bb [C] = conv_b (1x1 convolutions).
+ * Per element, all f32: n = fma(x, rstd * gamma, beta - rstd * gamma * mean); m = by + sum_k wy[k] zq[k] and a = bb + sum_k wb[k] zq[k]
+ * (fma, k ascending); out = fma(n, m, a).  mean / rstd come from f64 partial sums folded as muse_groupnorm_silu_nhwc_split folds them.
+ * Exactly one output form: y (f32 tensor; SiLU with the correctly rounded division) or y_hi AND y_lo (the bf16 operand planes of
+ * muse_conv2d_nhwc_split2: hi = bf16(out), lo = bf16(out - hi); SiLU with the hardware reciprocal, as the GroupNorm plane route) -
+ * both or neither: MUSE_ERR_BAD_ARG.  partial / stats_nchunk as for muse_groupnorm_silu_nhwc_split (0: the statistics pass runs here
+ * and `partial` needs batch * muse_groupnorm_nchunk(H * W) * groups * 2 doubles; > 0: `partial` holds a producer's [batch,
+ * stats_nchunk, groups, 2] sums and x is read once).  groups 32 or 64, C % groups == 0, C % 4 == 0, C <= 2048 and C / 4 a divisor of
+ * 256 or larger than it, else MUSE_ERR_UNSUPPORTED; x / y / zq (Z % 4 == 0) 16-byte aligned.  Every element offset is 64-bit. */
+int muse_spatial_norm_nhwc(const float* x, float* y, void* y_hi, void* y_lo, const float* gamma, const float* beta, const float* zq,
+                           const float* wy, const float* by, const float* wb, const float* bb, double* partial, int32_t stats_nchunk,
+                           int32_t batch, int32_t H, int32_t W, int32_t C, int32_t zh, int32_t zw, int32_t Z, int32_t groups, float eps,
+                           int32_t apply_silu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

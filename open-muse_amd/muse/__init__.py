@@ -5,9 +5,10 @@ MaskGitTransformer, MaskGiTUViT, MaskGitVQGAN, VQGANModel (the taming tokenizer 
 PipelineMuse, PipelineMuseInpainting, EMAModel (the weight average train_muse.py advances behind every optimizer step), get_mask_chedule; plus
 CLIPTextEncoder, the CLIP text tower of the text-to-image configs on the same kernels (opt-in; T5 stays a `transformers` model); everything computes
 through libmuse_hip.so (hand-written HIP kernels for gfx950).
-The Paella VQ tokenizer is built on the same kernels as `muse.modeling_paella_vq.PaellaVQModel` (the reference's module path); the top-level
-names `muse.MOVQ` / `muse.PaellaVQModel` are still the stubs of muse/unbuilt.py: they import (the training scripts import them
-unconditionally) and refuse to construct.  MoVQ is not part of this build.  `muse.lr_schedulers` / `muse.training_utils` carry the host-side helpers those scripts import.
+The Paella and MoVQ tokenizers are built on the same kernels under the reference's module paths, `muse.modeling_paella_vq.PaellaVQModel` and
+`muse.modeling_movq.MOVQ` (bind them from there); the top-level names `muse.MOVQ` / `muse.PaellaVQModel` are still the stubs of
+muse/unbuilt.py: they import (the training scripts import them unconditionally) and refuse to construct, saying where the built class lives.
+`muse.lr_schedulers` / `muse.training_utils` carry the host-side helpers those scripts import.
 """
 __version__ = "0.0.1"
 

@@ -2556,3 +2556,40 @@ def paella_out_block(x, w12, bias, B, H, W):
           "muse_paella_out_block")
     _prof_end(e0, "paella_out_block", _nbytes(x, img), "byte")
     return img
+
+
+# ---- MoVQ tokenizer (csrc/movq.hip) ----------------------------------------------------------------------------------------------
+def spatial_norm(x, zq, gamma, beta, wy, by, wb, bb, B, H, W, C, zh, zw, groups=32, eps=1e-6, silu=True, stats=None, split=False):
+    """SpatialNorm (+ SiLU) of an f32 NHWC tensor in one apply pass (muse_spatial_norm_nhwc):
+    GroupNorm(x) * conv_y(nearest(zq)) + conv_b(nearest(zq)), x [B, H, W, C], zq [B, zh, zw, Z] (Z <= 8; H % zh == W % zw == 0),
+    wy / wb [C, Z] and by / bb [C] the two 1x1 convolutions.  -> y f32 like x, or with split=True the (hi, lo) bf16 operand planes of
+    conv2d_nhwc_split2.  stats = (partial, nchunk) from the producing kernel's epilogue skips the statistics pass."""
+    require_gpu(x, zq, gamma, beta, wy, by, wb, bb)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != B * H * W * C:
+        raise _hip.MuseHipError(f"spatial_norm: x is a contiguous f32 [B, H, W, C] tensor, got {x.dtype} {tuple(x.shape)}")
+    if zq.dim() != 4:
+        raise _hip.MuseHipError("spatial_norm: zq is a contiguous f32 [B, zh, zw, Z] tensor")
+    Z = zq.shape[-1]
+    _f32_operand("spatial_norm: zq", zq, (B, zh, zw, Z))
+    for what, t, shape in (("gamma", gamma, (C,)), ("beta", beta, (C,)), ("wy", wy, (C, Z)), ("by", by, (C,)), ("wb", wb, (C, Z)),
+                           ("bb", bb, (C,))):
+        _f32_operand("spatial_norm: " + what, t, shape)
+    if stats is not None:
+        part, snc = stats
+        require_gpu(part)
+        if part.dtype != torch.float64 or not part.is_contiguous() or snc <= 0 or part.numel() != B * snc * groups * 2:
+            raise _hip.MuseHipError("spatial_norm: stats = (partial f64 [B, nchunk, groups, 2], nchunk)")
+    else:
+        part, snc = torch.empty(B * lib().muse_groupnorm_nchunk(H * W) * groups * 2, dtype=torch.float64, device=x.device), 0
+    if split:
+        out = (torch.empty(x.shape, dtype=torch.bfloat16, device=x.device), torch.empty(x.shape, dtype=torch.bfloat16, device=x.device))
+        y_ptr, hi_ptr, lo_ptr = None, out[0].data_ptr(), out[1].data_ptr()
+    else:
+        out = torch.empty_like(x)
+        y_ptr, hi_ptr, lo_ptr = out.data_ptr(), None, None
+    e0 = _prof_begin()
+    check(lib().muse_spatial_norm_nhwc(x.data_ptr(), y_ptr, hi_ptr, lo_ptr, gamma.data_ptr(), beta.data_ptr(), zq.data_ptr(), wy.data_ptr(),
+                                       by.data_ptr(), wb.data_ptr(), bb.data_ptr(), part.data_ptr(), snc, B, H, W, C, zh, zw, Z, groups, eps,
+                                       1 if silu else 0, stream()), "muse_spatial_norm_nhwc")
+    _prof_end(e0, "spatial_norm", _nbytes(x, zq, gamma, beta, wy, by, wb, bb, *(out if split else (out,))), "byte")
+    return out

@@ -198,7 +198,7 @@ class PipelineMuse:
             klass = MaskGiTUViT_v2 if str(cfg.get("_class_name", "")).startswith("MaskGiTUViT") else MaskGitTransformer
             return klass.from_pretrained(path, **kw)
 
-        def load_vae(path, **kw):           # likewise for the tokenizer (reference :320-329; MoVQ is not part of this build)
+        def load_vae(path, **kw):           # likewise for the tokenizer (reference :320-329; a MoVQ tokenizer, muse.modeling_movq.MOVQ, comes in through `vae=`)
             from .modeling_paella_vq import PaellaVQModel
             from .modeling_taming_vqgan import VQGANModel
             classes = {"MaskGitVQGAN": MaskGitVQGAN, "VQGANModel": VQGANModel, "PaellaVQModel": PaellaVQModel}
