@@ -404,8 +404,12 @@ int muse_mask_sample(const int64_t* tokens, const int64_t* class_ids, const floa
  *   for known tokens);  mask_len = max(1, min(#unknown - 1, sched_mask_len));  next_ids = mask_id where confidence < the
  *   mask_len-th smallest confidence of the image (0-based), else the sampled id.
  * noise_exp [batch*seq, vocab] / noise_u [batch, seq]: the caller's random draws (parity tests replay the reference's CPU
- * generator); NULL: Philox4x32-10 keyed by (seed, step).  raw_sampled (may be NULL) receives the samples before known tokens
- * are restored (the reference's `intermediate` list).  conf_scratch: f32 [batch*seq].  2 <= seq <= 4096. */
+ * generator) and are used verbatim; NULL: Philox4x32-10 with counter (row, row >> 32, j, 2 * step) for token j of row = b * seq + s
+ * (2 * step + 1 and j = 0 for the row's Gumbel draw) and key (seed, seed >> 32); the first output word r gives
+ * u = ((r >> 8) + 1) * 2^-24 in (0, 1] and q = -log(u), except that u == 1 (2^-24 of the draws) gives q = 2^-25 instead of 0: q stays
+ * strictly positive, as torch's exponential_ is, so that no token wins or loses a row by p / 0 whatever its probability.  raw_sampled (may be
+ * NULL) receives the samples before known tokens are restored (the reference's `intermediate` list).  conf_scratch: f32 [batch*seq].
+ * 2 <= seq <= 4096. */
 int muse_sample_step(const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride, int64_t ld,
                      int32_t vocab,
                      const int64_t* input_ids, int64_t mask_id, const float* noise_exp, const float* noise_u, uint64_t seed,

@@ -158,8 +158,11 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 }
 
 // erf(x / sqrt(2)) for the kernels whose STORAGE type is bf16 (FAST = true): Abramowitz & Stegun 7.1.26 - branch-free, one reciprocal,
-// one exponential (exp(-x^2 / 2), the very factor the GELU derivative's density needs), five fmas; |error| <= 1.5e-7 (+ ~2 ulp of f32
-// evaluation), four orders below the bf16 rounding of the values these kernels store.  The bf16 GLU / ffn_mid kernels are vector-ALU
+// one exponential (exp(-x^2 / 2), the very factor the GELU derivative's density needs), five fmas.  The formula's own error is 1.5e-7;
+// evaluated in float32 over every finite bf16 input it errs by 5.4e-7 in erf, i.e. up to 3.0e-7 |x| in gelu(x) and 2.8e-7 in gelu'(x)
+// (numpy float32 on the CPU; the subtraction 1 - q t e costs the rest), still three orders below the bf16 rounding of the values these
+// kernels store.  tests/test_gpu_row_edges.py holds the kernels to 0.5e-6 |x| resp. 1e-6 (1 + |x|) beyond one bf16 rounding over all
+// 65280 finite bf16 inputs (room for v_rcp_f32 and the hardware exponential).  The bf16 GLU / ffn_mid kernels are vector-ALU
 // bound (~80 instructions per element with the library erff, whose two branches both execute in a divergent wave: ffn_mid_bwd 103 us
 // of VALU issue for 92 us of memory time); f32 storage keeps the library erff.  Forward and backward of a pair use the same
 // function, so the backward's recomputed gelu(a) * b is still the forward's tensor bit for bit.

@@ -62,7 +62,11 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
     if (noise_exp) q = noise_exp[row * V + j];
     else {
       const u4 r = philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), (uint32_t)j, step * 2u, (uint32_t)seed, (uint32_t)(seed >> 32));
-      q = -logf(u01_open_low(r.x));
+      // u == 1 (the top 24 bits all ones, 2^-24 of the draws) has no positive q: -logf(1.0f) is -0.0f and p / q = -inf, so that token
+      // could not be sampled whatever its probability (and with +0 it would always win).  torch's exponential_ never returns 0 either;
+      // 2^-25 lies below the next smallest draw, -log(1 - 2^-24)
+      const float uq = u01_open_low(r.x);
+      q = uq < 1.0f ? -logf(uq) : 0x1p-25f;
     }
     const float v = p / q;
     if (v > best) { best = v; besti = j; }
