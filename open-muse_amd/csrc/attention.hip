@@ -336,7 +336,11 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
       qf = nfull > wave ? qn : frag_global<HD>(rq, ldq_b, q_begin + qs * 16, lane);
       fwd_reset<HD>(A);
       const int kvalid = P.skv - 4 * g;
-      for (int s = wave; s < MAXT / 2; s += NW) fwd_substep<HD, 2, 0>(Kimg, Vimg, 2 * s, qf, c, kvalid, A, lane);
+      // Only pairs that hold a real key.  The every-tile-masked 16-tile form (97 <= S_kv <= 224) has pairs past the sequence end, and a
+      // wave whose first pair is all mask starts from m = -1e30 with every score -1e30: fmaf(s, c, -m c) is then the rounding error of
+      // m c (+-1e21, its sign set by alpha), i.e. P = exp2(+1e21) = inf at head_dim 16 / 48 / 64 and O = inf * 0 = NaN in the shared tile's
+      // rows.  A wave without a real pair keeps the reset state, which the merge below weighs with exp2(-huge) = 0.
+      for (int s = wave; s < MAXT / 2 && 32 * s < P.skv; s += NW) fwd_substep<HD, 2, 0>(Kimg, Vimg, 2 * s, qf, c, kvalid, A, lane);
       __syncthreads();                                   // every wave is done with the K / V images
       constexpr int PW = HD + 2;                         // floats per (wave, row): O | m | l
       float* part = (float*)smem;
