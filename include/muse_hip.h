@@ -653,6 +653,32 @@ int muse_layernorm_bias_fwd(const float* x, const float* w, const float* b, void
 int muse_eos_index(const int64_t* ids, int64_t* idx, int64_t* flat_idx, int32_t batch, int32_t seq, int64_t eos_token_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * T5 text encoder (transformers T5EncoderModel, the `type: "t5"` text encoder of the reference's configs:
+ * training/train_muse.py:341-343, called every step at :651 as `text_encoder(ids)[0]`).  Forward only.  (csrc/t5_text.hip)
+ * muse_bias_attention_fwd: fused BIDIRECTIONAL self-attention with an additive relative-position bias, bf16 q / k / v / o addressed
+ *   as for muse_causal_attention_fwd (all strides multiples of 8, pointers 16-byte aligned), f32 softmax and accumulation, MFMA
+ *   products.  score(query i, key j) = q_i . k_j + rel[head][j - i + seq - 1] - no scale (d->alpha is not read), no mask: every query
+ *   sees every key < seq.  rel: f32 [heads, 2 seq - 1].  seq_q == seq_kv in 1..128 (one tile: one workgroup per (image, head), no
+ *   S x S matrix in memory), head_dim 32 or 64; anything else MUSE_ERR_UNSUPPORTED.  Rows >= seq of an image are never read.
+ *   Replaces T5Attention.forward of the encoder (transformers models/t5/modeling_t5.py).
+ * muse_bias_softmax_fwd: the same bias on materialised f32 scores, [mats][seq][ld]: row i of matrix z = softmax over j < seq of
+ *   x[i][j] + rel[z % heads][j - i + seq - 1], columns [seq, ld) written as 0.  y (f32, may be x: in place) and / or y_bf16 (the same
+ *   values rounded to bf16, same ld) receive the result; one of them may be NULL.  (Between two muse_gemm products: the exact-f32
+ *   mode, and both modes for seq > 128.)
+ * muse_gated_gelu_tanh: y[r][c] = gelu_new(ab[r][c]) * ab[r][cols + c] for ab [rows, 2 cols], y [rows, cols], both f32 or both bf16;
+ *   gelu_new(x) = 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (NewGELUActivation behind T5DenseGatedActDense.wi_0, times wi_1).
+ * muse_rmsnorm_bf16_fwd: y = bf16(x * rsqrt(mean(x^2) + eps) * w), x f32 [rows, cols] (T5LayerNorm as the bf16 operand of the next
+ *   product; the f32 result is muse_norm_res_fwd mode 0).
+ * muse_rel_bias_gather: rel[h][t] = table[bucket[t]][h] for t < n: table = relative_attention_bias.weight f32 [buckets, heads],
+ *   bucket int64 [n] = the bucket of every signed distance -(seq - 1) .. seq - 1 (computed on the host), rel f32 [heads, n]. */
+int muse_bias_attention_fwd(const muse_attn_desc* d, const float* rel, void* stream);
+int muse_bias_softmax_fwd(const float* x, float* y, void* y_bf16, const float* rel, int64_t mats, int32_t heads, int32_t seq, int64_t ld,
+                          void* stream);
+int muse_gated_gelu_tanh(const void* ab, void* y, int32_t dtype, int64_t rows, int32_t cols, void* stream);
+int muse_rmsnorm_bf16_fwd(const float* x, const float* w, void* y, int64_t rows, int32_t cols, float eps, void* stream);
+int muse_rel_bias_gather(const float* table, const int64_t* bucket, float* rel, int32_t heads, int32_t n, int32_t buckets, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Paella VQ tokenizer (muse/modeling_paella_vq.py, `vq_model.type: "paella_vq"`).  Forward only, f32, channels-last rows
  * [batch*H*W, C] with C % 4 == 0.  Every element offset inside these kernels is 64-bit; int32 arguments are sides and channel counts.
  * (csrc/paella.hip)

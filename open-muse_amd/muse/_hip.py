@@ -199,6 +199,11 @@ SIGNATURES = {
     "muse_bias_quick_gelu": [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_layernorm_bias_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_float, c_void_p],
     "muse_eos_index": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p],
+    "muse_bias_attention_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p],
+    "muse_bias_softmax_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_void_p],
+    "muse_gated_gelu_tanh": [c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
+    "muse_rmsnorm_bf16_fwd": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_void_p],
+    "muse_rel_bias_gather": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     "muse_paella_mix_fwd": [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p],
     "muse_patch_rows_nhwc": [c_void_p, c_void_p] + [c_int] * 10 + [c_void_p],
     "muse_vq_nearest_small": [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p],

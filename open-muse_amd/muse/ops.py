@@ -2467,6 +2467,79 @@ def eos_index(ids, eos_token_id):
     return idx, flat
 
 
+# ---- T5 text encoder (csrc/t5_text.hip; muse.T5TextEncoder): forward only -------------------------------------------------------------
+def _rel_check(what, rel, nh, S):
+    if rel.dtype != torch.float32 or not rel.is_contiguous() or tuple(rel.shape) != (nh, 2 * S - 1):
+        raise _hip.MuseHipError(f"{what}: rel is a contiguous f32 [heads, 2 S - 1] = {(nh, 2 * S - 1)} tensor, got {rel.dtype} {tuple(rel.shape)}")
+
+
+def bias_attention_fwd(q, k, v, rel, B, S, nh, hd, out=None):
+    """fused bidirectional softmax(q k^T + bias) v, bias(query i, key j) = rel[head][j - i + S - 1], no score scale: q / k / v [B*S, H]
+    bf16 views (row strides free: slices of one packed q | k | v projection; rows >= S of an image are never read), rel f32
+    [heads, 2 S - 1] -> ctx [B*S, H] bf16.  No score matrix in memory."""
+    require_gpu(q, k, v, rel)
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise _hip.MuseHipError("the fused bias attention kernel takes bf16 operands")
+    _rel_check("bias_attention_fwd", rel, nh, S)
+    ctx = out if out is not None else torch.empty((B * S, nh * hd), dtype=torch.bfloat16, device=q.device)
+    d = _attn_desc(q, k, v, ctx, B, S, S, nh, hd, 1.0)
+    e0 = _prof_begin()
+    check(lib().muse_bias_attention_fwd(C.byref(d), rel.data_ptr(), stream()), "muse_bias_attention_fwd")
+    _prof_end(e0, "attn_bias_fwd_bf16", 4.0 * B * nh * S * S * hd)
+    return _touched(ctx)
+
+
+def bias_softmax_(x, rel, mats, nh, seq, ld, bf16_copy=False):
+    """[mats, seq, ld] f32 score matrices: row i of matrix z = softmax over j < seq of x[i][j] + rel[z % nh][j - i + seq - 1], every
+    column of [seq, ld) = 0.  In place -> x; bf16_copy: x is left as it is and the result comes back as a bf16 tensor of the same shape"""
+    require_gpu(x, rel)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != mats * seq * ld:
+        raise _hip.MuseHipError("bias_softmax_: x is a contiguous f32 [mats, seq, ld] tensor")
+    _rel_check("bias_softmax_", rel, nh, seq)
+    yb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if bf16_copy else None
+    e0 = _prof_begin()
+    check(lib().muse_bias_softmax_fwd(x.data_ptr(), None if bf16_copy else x.data_ptr(), ptr(yb), rel.data_ptr(), mats, nh, seq, ld, stream()),
+          "muse_bias_softmax_fwd")
+    _prof_end(e0, "bias_softmax_fwd", _nbytes(x) + _nbytes(yb if bf16_copy else x), "byte")
+    return yb if bf16_copy else _touched(x)
+
+
+def gated_gelu_tanh(ab):
+    """ab [rows, 2 F] (f32 / bf16, the packed wi_0 | wi_1 product) -> gelu_new(ab[:, :F]) * ab[:, F:] in the same dtype"""
+    require_gpu(ab)
+    rows, two_f = ab.shape
+    if not ab.is_contiguous() or two_f % 2:
+        raise _hip.MuseHipError("gated_gelu_tanh: ab is a contiguous [rows, 2 F] tensor")
+    y = torch.empty((rows, two_f // 2), dtype=ab.dtype, device=ab.device)
+    check(lib().muse_gated_gelu_tanh(ab.data_ptr(), y.data_ptr(), dt(ab), rows, two_f // 2, stream()), "muse_gated_gelu_tanh")
+    return y
+
+
+def rmsnorm_fwd(x, w, eps, out_dtype):
+    """x * rsqrt(mean(x^2) + eps) * w (T5LayerNorm: no mean subtraction, no bias): x f32 [rows, cols] -> f32 (muse_norm_res_fwd mode 0,
+    cols % 4 == 0) or bf16"""
+    require_gpu(x, w)
+    rows, cols = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous() or w.dtype != torch.float32 or w.numel() != cols:
+        raise _hip.MuseHipError("rmsnorm_fwd: x is a contiguous f32 [rows, cols] tensor, w f32 [cols]")
+    if out_dtype == torch.float32:
+        return norm_res_fwd(x, w, eps, 0)[0]
+    y = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
+    check(lib().muse_rmsnorm_bf16_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rows, cols, eps, stream()), "muse_rmsnorm_bf16_fwd")
+    return y
+
+
+def rel_bias_gather(table, bucket):
+    """table f32 [buckets, heads] (relative_attention_bias.weight), bucket int64 [n] -> rel f32 [heads, n], rel[h][t] = table[bucket[t]][h]"""
+    require_gpu(table, bucket)
+    if table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or bucket.dtype != torch.int64 or not bucket.is_contiguous():
+        raise _hip.MuseHipError("rel_bias_gather: table is a contiguous f32 [buckets, heads] tensor, bucket a contiguous int64 vector")
+    nb, nh = table.shape
+    rel = torch.empty((nh, bucket.numel()), dtype=torch.float32, device=table.device)
+    check(lib().muse_rel_bias_gather(table.data_ptr(), bucket.data_ptr(), rel.data_ptr(), nh, bucket.numel(), nb, stream()), "muse_rel_bias_gather")
+    return rel
+
+
 # ---- Paella VQ tokenizer (csrc/paella.hip) : f32 forward ops on channels-last rows ---------------------------------------------
 def _f32_operand(what, t, shape):
     """the kernels read their weights through raw pointers: a transposed, strided or non-f32 operand would be read in the wrong order"""

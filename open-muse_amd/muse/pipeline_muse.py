@@ -2,11 +2,12 @@
 
 Thin: `generate2` on the transformer, then `vae.decode_code`; both run on the HIP kernels (the inpainting pipeline first tokenises the
 picture with `vae.encode`).  The text encoder is the reference's own third-party dependency (a `transformers` CLIP / T5 model and its
-tokenizer, handed to the constructor) or, for CLIP, `muse.CLIPTextEncoder` (the same tower on the HIP kernels): when one is given, `text=` is encoded by calling it exactly as the reference does; without one the
+tokenizer, handed to the constructor) or `muse.CLIPTextEncoder` / `muse.T5TextEncoder` (the same models on the HIP kernels): when one is given, `text=` is encoded by calling it exactly as the reference does; without one the
 pipelines take PRE-COMPUTED text states (`prompt_embeds`, ...).  Constructor / `to` / `from_pretrained` / `save_pretrained` signatures kept.
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import List, Optional, Union
 
@@ -188,7 +189,8 @@ class PipelineMuse:
                         vae_path: Optional[str] = None, transformer_path: Optional[str] = None, vae=None, text_encoder=None,
                         transformer=None, is_class_conditioned: bool = False, native_text_encoder: bool = False, **kwargs):
         """reference :254-355, same arguments, plus `native_text_encoder` (this build's addition, default False): True loads the text
-        tower from the same folder as `muse.CLIPTextEncoder` (the CLIP text model on the HIP kernels) instead.  The text encoder and tokenizer of a text-conditioned pipeline are the reference's own
+        encoder from the same folder on the HIP kernels instead - `muse.T5TextEncoder` when its config.json says `model_type: "t5"`,
+        `muse.CLIPTextEncoder` otherwise.  The text encoder and tokenizer of a text-conditioned pipeline are the reference's own
         `transformers` classes, loaded the way the reference loads them (`CLIPTextModelWithProjection`, `AutoTokenizer`) - from
         `<model>/text_encoder` or `text_encoder_path`; a LOCAL checkpoint directory without a `text_encoder/` folder gives a pipeline
         that takes pre-computed text states instead (this build's addition)."""
@@ -219,7 +221,13 @@ class PipelineMuse:
                 from transformers import AutoTokenizer, CLIPTextModelWithProjection
                 if text_encoder is None and native_text_encoder:
                     from .modeling_clip_text import CLIPTextEncoder
-                    text_encoder = CLIPTextEncoder.from_pretrained(te_path, **sub)
+                    from .modeling_t5_text import T5TextEncoder
+                    cfg_file = os.path.join(str(te_path), sub.get("subfolder", ""), "config.json")
+                    is_t5 = False
+                    if os.path.isfile(cfg_file):        # (a missing file is the chosen class's own loud error)
+                        with open(cfg_file, "r", encoding="utf-8") as f:
+                            is_t5 = json.load(f).get("model_type") == "t5"
+                    text_encoder = (T5TextEncoder if is_t5 else CLIPTextEncoder).from_pretrained(te_path, **sub)
                 elif text_encoder is None:
                     text_encoder = CLIPTextModelWithProjection.from_pretrained(te_path, **sub)
                 tokenizer = AutoTokenizer.from_pretrained(te_path, **sub)
