@@ -449,6 +449,9 @@ int muse_cond_dropout(const float* x, const float* empty, const float* uniforms,
  *   3x3 convolution over it zero-padded by one row / column at the bottom / right (taming-VQGAN Downsample,
  *   muse/modeling_taming_vqgan.py:53-59: F.pad(0,1,0,1) + Conv2d(3, stride 2, padding 0)).  Same meaning in
  *   muse_conv2d_nhwc_split.
+ *   Span limit (both entries; the loaders address with 32-bit byte offsets): the input tensor - [batch, H, W, Cin] for upsample 0,
+ *   [batch, H/2, W/2, Cin] for 1, [batch, 2H, 2W, Cin] for 2 - and the weight image [Cout][KS][KS][Cin] must each stay below
+ *   4 GiB - 64 bytes, and batch * H * W below 2^31 - 256; anything larger returns MUSE_ERR_UNSUPPORTED before a launch (split the batch).
  */
 int muse_conv2d_nhwc(const void* in, const void* weight, const float* bias, const void* residual, void* out,
                      int32_t dtype, int32_t batch, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS,

@@ -179,6 +179,7 @@ extern "C" int muse_conv2d_nhwc_split(const float* in, const void* w_hi, const v
   if (KS != 1 && KS != 3) return MUSE_ERR_UNSUPPORTED;
   if (upsample < 0 || upsample > 2 || (upsample == 2 && KS != 3)) return MUSE_ERR_BAD_ARG;
   if (upsample == 1 && ((H | W) & 1)) return MUSE_ERR_BAD_ARG;
+  if (!conv_span_ok(batch, H, W, Cin, Cout, KS, upsample, 4)) return MUSE_ERR_UNSUPPORTED;
   SplitParams sp;
   sp.gn_partial = nullptr; sp.gn_groups = 0; sp.gn_cpg = 0;
   if (gn_partial) {   // output statistics for the next GroupNorm, [batch, H*W/128, gn_groups, 2] doubles

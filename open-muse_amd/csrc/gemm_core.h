@@ -200,6 +200,23 @@ struct ConvLoader {
   }
 };
 
+// What ConvLoader's 32-bit arithmetic can address, checked on the host in `long` before anything is narrowed (muse_conv2d_nhwc,
+// muse_conv2d_nhwc_split): the input tensor - its real extent for the upsample mode, esz bytes per element - and the weight image each
+// below 4 GiB (buffer ranges and `center` are 32-bit byte offsets; the - 64 margin of muse_conv2d_nhwc_split2 keeps the rounded-up
+// out-of-range offset representable), and batch * H * W output pixels inside the kernels' signed 31-bit M with room for the tile round-up.
+inline bool conv_span_ok(long batch, long H, long W, long Cin, long Cout, long KS, int upsample, long esz) {
+  const long lim = (1L << 32) - 64, mlim = (1L << 31) - 256;
+  // every factor is bounded before it is multiplied, so no product below can leave 63 bits whatever the arguments are
+  if (batch <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return true;    // nothing to address: the entries return 0 for an empty product
+  if (Cin * esz >= lim) return false;
+  if (H >= mlim || W >= mlim || H * W >= mlim || batch >= mlim || batch * (H * W) >= mlim) return false;   // M < 2^31 - 256
+  const long ih = upsample == 1 ? H / 2 : upsample == 2 ? 2 * H : H, iw = upsample == 1 ? W / 2 : upsample == 2 ? 2 * W : W;
+  const long pixels = batch * ih * iw, row = Cin * esz;                        // pixels <= 4 M < 2^33, row < 2^32
+  if (pixels >= (lim + row - 1) / row) return false;                           // pixels * row >= lim
+  const long taps = KS * KS;                                                    // KS is 1 or 3 here
+  return Cout < (lim + taps * row - 1) / (taps * row);                         // Cout * taps * row < lim
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // LDS -> MFMA fragment readers.  A fragment is (16 rows) x (one MFMA K-group); lane l supplies row (l & 15).
 // ---------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ extern "C" int muse_conv2d_nhwc(const void* in, const void* weight, const float*
   if (KS != 1 && KS != 3) return MUSE_ERR_UNSUPPORTED;
   if (upsample < 0 || upsample > 2 || (upsample == 2 && KS != 3)) return MUSE_ERR_BAD_ARG;
   if (upsample == 1 && ((H | W) & 1)) return MUSE_ERR_BAD_ARG;
+  if (!conv_span_ok(batch, H, W, Cin, Cout, KS, upsample, esz)) return MUSE_ERR_UNSUPPORTED;
   GemmParams p;
   p.A = in; p.B = weight; p.C = out;
   p.bias = bias; p.rowvec = nullptr; p.residual = residual;

@@ -2036,7 +2036,8 @@ def conv2d_nhwc_gn_split2_pool(x, scale, shift, w_hi, w_lo, B, H, W, Cin, Cout, 
 def conv_split2_ok(B, H, W, Cin, Cout, KS):
     """shapes muse_conv2d_nhwc_split2 takes (the rest stay on muse_conv2d_nhwc_split)"""
     M = B * H * W
-    return KS == 3 and Cin % 32 == 0 and Cout % 4 == 0 and M * Cin * 2 < (1 << 32) - 64 and M < (1 << 31) - 256
+    return (KS == 3 and Cin % 32 == 0 and Cout % 4 == 0 and M * Cin * 2 < (1 << 32) - 64 and Cout * 9 * Cin * 2 < (1 << 32) - 64
+            and M < (1 << 31) - 256)
 
 
 def conv_slab_ok(H, W, Cin):
