@@ -91,7 +91,9 @@ int muse_gemm_group_ok(const muse_gemm_desc* d, int32_t n, int32_t split_k);
 int muse_gemm_group(const muse_gemm_desc* d, int32_t n, int32_t split_k, void* stream);
 
 /* 2-D transpose out[c, r] = in[r, c] (strided-batched); used only by the fallback that feeds k-major operands to
- * the k-contiguous GEMM path (MUSE_GEMM_TR=0). */
+ * the k-contiguous GEMM path (MUSE_GEMM_TR=0).  More than 65535 row tiles of 32, or more than 65535 matrices: MUSE_ERR_UNSUPPORTED
+ * before a launch.  65535 is this library's own limit for gridDim.y / .z (the portable one), not a figure asked of the runtime, which
+ * may accept more. */
 int muse_transpose(const void* in, void* out, int32_t dtype, int32_t rows, int32_t cols, int64_t ld_in, int64_t ld_out,
                    int32_t batch, int64_t stride_in, int64_t stride_out, void* stream);
 
@@ -545,7 +547,9 @@ int muse_nchw_to_nhwc(const float* in, void* out, int32_t out_dtype, int32_t bat
                       void* stream);
 int muse_nhwc_to_nchw(const void* in, int32_t in_dtype, float* out, int32_t batch, int32_t C, int32_t HW, int32_t Cpad,
                       void* stream);
-/* argmin over codes of dist [rows, ncodes] f32 (first index wins ties, like torch.argmin), :279/:346 */
+/* argmin over codes of dist [rows, ncodes] f32, :279/:346.  idx[r] is always in [0, ncodes): the lowest index of the smallest non-NaN
+ * value (-0.0 == +0.0; a row of +inf gives 0 like torch.argmin); a NaN never wins - a row of nothing but NaN gives 0, where torch.argmin
+ * returns the first NaN's index.  ncodes <= 0: MUSE_ERR_BAD_ARG. */
 int muse_argmin_rows(const float* dist, int64_t* idx, int64_t rows, int32_t ncodes, int64_t ld, void* stream);
 /* sum of squares per row, f32 in / f32 out (VectorQuantizer.compute_distances :308-309) */
 int muse_row_sumsq(const float* x, float* out, int64_t rows, int32_t cols, int64_t ld, void* stream);
@@ -589,7 +593,7 @@ int muse_sinusoidal_encode(const float* f, float* out, int64_t n, int32_t dim, f
 int muse_weighted_mean(const float* v, const float* w, float* out, int64_t n, void* stream);
 /* backward of the above (f32).  v = the forward's pre-norm sum x (+ res); dv = dx = dres; dw_partial [nblk, cols] is folded
  * with muse_colsum (nblk from _nblk; cols <= 4096).  muse_adaln_bwd: dx and dss [B, 2C] = (sum_r dy x | sum_r dy).
- * muse_dwconv3x3_bwd: dx and dw_partial [nchunk, C*9] (muse_colsum -> dw [C][3][3]).  muse_grn_bwd: `stats` = the forward's
+ * muse_dwconv3x3_bwd: dx and dw_partial [nchunk, C*9] (muse_colsum -> dw [C][3][3]; nchunk > 65535, the library's own limit for gridDim.y whatever the runtime accepts: MUSE_ERR_UNSUPPORTED before a launch).  muse_grn_bwd: `stats` = the forward's
  * scratch [G | N]; work 4*B*C floats, on return work[0:B*C] = per-image dbeta terms, work[B*C:2*B*C] = per-image dgamma terms
  * (muse_colsum over the B rows).  muse_scale_rows: x[r, :cols] *= w[r] * num[0] / den[0] (weighted-loss gradient). */
 int muse_norm_res_bwd_nblk(int64_t rows);

@@ -353,15 +353,16 @@ extern "C" int muse_grn_fwd_ex(const float* x, const float* gamma, const float* 
   if (!y && !y_bf16) return MUSE_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* nx = scratch + (long)batch * C;   // scratch = [G | N], both kept for the backward
+  const bool v4 = (C & 3) == 0 && S * (long)(C >> 2) < (1L << 31) && batch <= 65535 && !((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)y_bf16)) & 15);
+  if (y_bf16 && !v4) return MUSE_ERR_UNSUPPORTED;   // only grn_apply4_kernel writes bf16: refused before the statistics are launched
   hipLaunchKernelGGL(grn_colnorm_kernel, dim3((C + 63) / 64, batch), dim3(256), 0, s, x, scratch, (long)S, C);
   hipLaunchKernelGGL(grn_scale_kernel, dim3(batch), dim3(256), 0, s, (const float*)scratch, nx, C);
-  if ((C & 3) == 0 && S * (long)(C >> 2) < (1L << 31) && batch <= 65535 && !((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)y_bf16)) & 15)) {
+  if (v4) {
     long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(grn_apply4_kernel, dim3((unsigned)gx, batch), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (bf16_t*)y_bf16,
                        (int)S, C);
     return (int)hipGetLastError();
   }
-  if (y_bf16) return MUSE_ERR_UNSUPPORTED;
   long g = (n + 255) / 256; if (g > 65535) g = 65535;
   hipLaunchKernelGGL(grn_apply_kernel, dim3((unsigned)g), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (long)S, C, n);
   return (int)hipGetLastError();
@@ -961,13 +962,13 @@ __global__ __launch_bounds__(256) void dwconv3x3_bwd_dx_kernel(const float* __re
     float acc = 0.f;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
-      const int oy = yy - (ky - 1);            // output pixel that read this input through tap (ky, kx)
-      if (oy < 0 || oy >= H) continue;
+      const int oy = yy + ky - 1;              // output pixel (oy, ox) read this input through tap (2 - ky, 2 - kx); walked top-left to
+      if (oy < 0 || oy >= H) continue;         // bottom-right like dwconv3x3_v4_kernel<true>: the same fma chain, the same bits
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        const int ox = xx - (kx - 1);
+        const int ox = xx + kx - 1;
         if (ox < 0 || ox >= W) continue;
-        acc = fmaf(dy[((b * H + oy) * W + ox) * C + c], w[c * 9 + ky * 3 + kx], acc);
+        acc = fmaf(dy[((b * H + oy) * W + ox) * C + c], w[c * 9 + 8 - (ky * 3 + kx)], acc);
       }
     }
     dx[i] = acc;
@@ -1060,6 +1061,9 @@ extern "C" int muse_dwconv3x3_bwd(const float* dy, const float* x, const float* 
                                   int32_t H, int32_t W, int32_t C, void* stream) {
   const long pixels = (long)batch * H * W, n = pixels * C;
   if (n <= 0) return 0;
+  // the dw kernels take one 64-pixel chunk per blockIdx.y: refuse before the dx launch what the second launch could not be given.
+  // 65535 is the library's own limit (the portable gridDim.y), not the runtime's, which may accept more
+  if ((pixels + DW_PIX - 1) / DW_PIX > 65535) return MUSE_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (!launch_dwconv_v4<true>(dy, w, dx, batch, H, W, C, s)) {
     long g = (n + 255) / 256; if (g > 65535) g = 65535;

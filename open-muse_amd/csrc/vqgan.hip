@@ -812,16 +812,21 @@ __global__ __launch_bounds__(256) void argmin_rows_kernel(const float* __restric
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* r = d + row * ld;
-  float best = INFINITY; int bi = 0x7fffffff;
-  for (int c = lane; c < n; c += 64) { const float v = r[c]; if (v < best) { best = v; bi = c; } }
+  // NONE marks a lane that has seen no comparable value yet (no column, or NaN only): its first +inf is taken, so a row of +inf
+  // returns 0 like torch.argmin; a NaN never compares and a row of nothing but NaN returns 0 (the rule of paella.hip vq_small_kernel)
+  constexpr int NONE = 0x7fffffff;
+  float best = INFINITY; int bi = NONE;
+  for (int c = lane; c < n; c += 64) { const float v = r[c]; if (v < best || (bi == NONE && v == best)) { best = v; bi = c; } }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
     if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
   }
-  if (lane == 0) idx[row] = (int64_t)bi;
+  if (lane == 0) idx[row] = (int64_t)(bi == NONE ? 0 : bi);
 }
+// idx[row] in [0, ncodes): the lowest index of the smallest non-NaN value of the row (-0.0 == +0.0), 0 for a row of NaN
 extern "C" int muse_argmin_rows(const float* dist, int64_t* idx, int64_t rows, int32_t ncodes, int64_t ld, void* stream) {
+  if (ncodes <= 0) return MUSE_ERR_BAD_ARG;
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(argmin_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dist, idx, (long)rows, ncodes, (long)ld);
   return (int)hipGetLastError();
@@ -880,6 +885,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ in
 extern "C" int muse_transpose(const void* in, void* out, int32_t dtype, int32_t rows, int32_t cols, int64_t ld_in,
                               int64_t ld_out, int32_t batch, int64_t stride_in, int64_t stride_out, void* stream) {
   if (rows <= 0 || cols <= 0 || batch <= 0) return 0;
+  if (((long)rows + 31) / 32 > 65535 || batch > 65535) return MUSE_ERR_UNSUPPORTED;   // gridDim.y / .z: the library's own limit, refused here before a launch
   dim3 grid((cols + 31) / 32, (rows + 31) / 32, batch);
   if (dtype == MUSE_F32) hipLaunchKernelGGL(transpose_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)in, (float*)out, rows, cols, (long)ld_in, (long)ld_out, (long)stride_in, (long)stride_out);
   else hipLaunchKernelGGL(transpose_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (bf16_t*)out, rows, cols, (long)ld_in, (long)ld_out, (long)stride_in, (long)stride_out);
