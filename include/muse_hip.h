@@ -738,6 +738,29 @@ int muse_spatial_norm_nhwc(const float* x, float* y, void* y_hi, void* y_lo, con
                            int32_t batch, int32_t H, int32_t W, int32_t C, int32_t zh, int32_t zw, int32_t Z, int32_t groups, float eps,
                            int32_t apply_silu, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Pre-encode image stage (muse/pre_encode.py resize_center_crop; csrc/resize.hip): what scripts/pre_encode.py:449-489 does per image in
+ * front of get_code - uint8 HWC -> CHW f32 / 255 -> TF.resize(BILINEAR, antialias=True) -> crop (-> flip) -> stack - for a ragged
+ * batch in ONE launch.
+ * Value.  Image b is `H x W x 3` uint8; its resized size (oh, ow) and its window origin (top, left) come from the table (the host
+ * computes them: torchvision's _compute_resized_output_size / center_crop, or a random crop).  Per axis (in = source length, out =
+ * resized length, i = resized index), every step ONE rounded f32 operation, none contracted into a multiply-add:
+ *     scale = f32(in) / f32(out);  support = scale >= 1 ? scale : 1;  inv = scale >= 1 ? 1 / scale : 1;  center = scale * (i + 0.5)
+ *     lo = max(trunc((center - support) + 0.5), 0);  hi = min(trunc((center + support) + 0.5), in)
+ *     w_s = max(0, 1 - |((f32(s) - center) + 0.5) * inv|) for s = lo .. hi - 1;  w_s /= (w_lo + w_lo+1 + ..., in this order)
+ *   i.e. ATen's antialias bilinear weights of F.interpolate(mode="bilinear", antialias=True, align_corners=False) bit for bit.
+ *     src = f32(u8) / 255 (correctly rounded);  tmp[y][x] = sum_s src[y][s] * wx_s;  res[i][x] = sum_s tmp[s][x] * wy_s
+ *   both sums from the lowest tap upwards with fma, tmp rounded to f32 (horizontal pass first, as ATen's separable kernel).
+ *     out[b][c][y][x] = res[top + y][left + (flip ? R - 1 - x : x)]  for 0 <= y, x < R: a flip AFTER the crop.
+ *   Tap counts are not capped (source rows are streamed), sizes are not bounded by LDS.
+ * What is read and written.  packed: device bytes; image b occupies [offset, offset + 3 H W) as HWC, at ANY byte offset, gaps between
+ * images allowed; no byte outside the listed images is read.  table: device int64 [B][8] = (offset, H, W, oh, ow, top, left, flip),
+ * 8-byte aligned; the rows are NOT validated here (they live on the device): the caller guarantees H, W >= 1, oh, ow >= R,
+ * 0 <= top <= oh - R, 0 <= left <= ow - R and that the image lies inside `packed` (muse.ops.resize_crop_u8 checks every row on the
+ * host).  out: f32 [B][3][R][R] contiguous, 4-byte aligned; nothing else is written.
+ * B < 1, R < 1 or a NULL pointer: MUSE_ERR_BAD_ARG, nothing is launched.  B > 65535 or R > 16 * 65535: MUSE_ERR_UNSUPPORTED. */
+int muse_resize_crop_u8(const void* packed, const void* table, void* out, int32_t B, int32_t R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

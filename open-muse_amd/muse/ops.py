@@ -2667,3 +2667,37 @@ def spatial_norm(x, zq, gamma, beta, wy, by, wb, bb, B, H, W, C, zh, zw, groups=
                                        1 if silu else 0, stream()), "muse_spatial_norm_nhwc")
     _prof_end(e0, "spatial_norm", _nbytes(x, zq, gamma, beta, wy, by, wb, bb, *(out if split else (out,))), "byte")
     return out
+
+
+# ---- pre-encode image stage (csrc/resize.hip) ------------------------------------------------------------------------------------
+def resize_crop_u8(packed, table, B, R, out=None, host_table=None):
+    """Antialiased bilinear resize + crop (+ flip) of B packed uint8 HWC images into [B, 3, R, R] f32 NCHW in one launch
+    (muse_resize_crop_u8; the value is spelled out in include/muse_hip.h).  packed: uint8 device bytes; table: int64 device [B, 8] =
+    (offset, H, W, oh, ow, top, left, flip) per image.  The kernel trusts the table, so every row is checked here on the host:
+    against `host_table` (the CPU tensor the device table was copied from) when the caller still has it, else against a read-back."""
+    require_gpu(packed, table, out)
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise _hip.MuseHipError(f"resize_crop_u8: packed is a contiguous 1-D uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    if table.dtype != torch.int64 or tuple(table.shape) != (B, 8) or not table.is_contiguous():
+        raise _hip.MuseHipError(f"resize_crop_u8: table is a contiguous int64 [B, 8] tensor, got {table.dtype} {tuple(table.shape)}")
+    if B < 1 or R < 1:
+        raise _hip.MuseHipError(f"resize_crop_u8: B and R are at least 1, got B {B}, R {R}")
+    rows = (table if host_table is None else host_table).cpu()
+    if rows.dtype != torch.int64 or tuple(rows.shape) != (B, 8):
+        raise _hip.MuseHipError("resize_crop_u8: host_table is the int64 [B, 8] CPU copy of table")
+    for b, (off, H, W, oh, ow, top, left, flip) in enumerate(rows.tolist()):
+        if H < 1 or W < 1 or off < 0 or off + 3 * H * W > packed.numel():
+            raise _hip.MuseHipError(f"resize_crop_u8: image {b} ({H} x {W} at byte {off}) does not lie inside packed ({packed.numel()} bytes)")
+        if oh < R or ow < R or not (0 <= top <= oh - R) or not (0 <= left <= ow - R) or flip not in (0, 1):
+            raise _hip.MuseHipError(f"resize_crop_u8: image {b}: window ({top}, {left}) + {R} outside the resized image {oh} x {ow}, or "
+                                    f"flip {flip} not 0 / 1")
+        if max(H, W, oh, ow) >= 1 << 24 or 3 * H * W >= 1 << 31:
+            raise _hip.MuseHipError(f"resize_crop_u8: image {b}: sides are below 2^24 (exact in f32) and an image below 2 GiB")
+    if out is None:
+        out = torch.empty((B, 3, R, R), dtype=torch.float32, device=packed.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, R, R) or not out.is_contiguous():
+        raise _hip.MuseHipError(f"resize_crop_u8: out is a contiguous f32 [B, 3, R, R] tensor, got {out.dtype} {tuple(out.shape)}")
+    e0 = _prof_begin()
+    check(lib().muse_resize_crop_u8(packed.data_ptr(), table.data_ptr(), out.data_ptr(), B, R, stream()), "muse_resize_crop_u8")
+    _prof_end(e0, "resize_crop_u8", _nbytes(packed, out), "byte")
+    return out
