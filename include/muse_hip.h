@@ -761,6 +761,40 @@ int muse_spatial_norm_nhwc(const float* x, float* y, void* y_hi, void* y_lo, con
  * B < 1, R < 1 or a NULL pointer: MUSE_ERR_BAD_ARG, nothing is launched.  B > 65535 or R > 16 * 65535: MUSE_ERR_UNSUPPORTED. */
 int muse_resize_crop_u8(const void* packed, const void* table, void* out, int32_t B, int32_t R, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * CLIP image tower (muse/modeling_clip_vision.py: transformers CLIPVisionModelWithProjection, and the image / text similarity of
+ * CLIPModel - the scorer of scripts/gen_sdxl_synthetic_dataset.py:34-36,98-105 and benchmark/model_quality.py:32-111).  Forward only,
+ * f32 in.  The encoder layers run on muse_gemm, muse_attention_fwd_ex, muse_layernorm_bias_fwd and muse_bias_quick_gelu.
+ * (csrc/clip_vision.hip)
+ * muse_resize_bicubic_norm_f32: x f32 [B, 3, R, R] -> out f32 [B, 3, I, I] = (resize(x) - mean[c]) / std[c], both contiguous, 4-byte
+ *   aligned.  resize is the separable antialiased bicubic of F.interpolate(x, (I, I), mode="bicubic", antialias=True,
+ *   align_corners=False): per axis, every step one rounded f32 operation,
+ *     scale = f32(R) / f32(I);  support = 2 max(scale, 1);  inv = scale >= 1 ? 1 / scale : 1;  center = scale * (i + 0.5)
+ *     lo = max(trunc((center - support) + 0.5), 0);  hi = min(trunc((center + support) + 0.5), R, lo + 2 ceil(support) + 1)
+ *     w_s = k(((f32(s) - center) + 0.5) * inv) for s = lo .. hi - 1, k = Keys' cubic with a = -0.5;  w_s /= (w_lo + w_lo+1 + ...)
+ *   horizontal pass first, both sums from the lowest tap upwards with fma, the intermediate rounded to f32 and NOT clamped (the cubic's
+ *   overshoot below 0 / above 1 is kept), no intermediate image in memory.  R > I, R < I and R == I all run; for R == I the weights are
+ *   exactly (.., 0, 1, 0, ..) and the output is (x - mean[c]) / std[c] with the correctly rounded f32 quotient.  mean3 / std3 are HOST
+ *   pointers to three floats each.  B > 65535, I > 16 * 65535 or a side >= 2^24: MUSE_ERR_UNSUPPORTED.
+ * muse_clip_patch_rows: x f32 [B, 3, I, I] -> y [B * G * G, Kp] (f32 or bf16, round to nearest even), G = I / P, Kp = 3 P P rounded up
+ *   to a multiple of 8 (any other Kp, or I % P != 0: MUSE_ERR_BAD_ARG): y[(b, gy, gx)][(c, ky, kx)] = x[b][c][gy P + ky][gx P + kx],
+ *   columns >= 3 P P written as 0 - the (c, ky, kx) flattening of Conv2d(3, H, P, stride=P).weight, so the patch embedding is one
+ *   muse_gemm against the weight padded to [H, Kp].  y 16-byte aligned; nothing outside [y, y + B G G Kp) is written.
+ * muse_clip_vision_embed_ln: y[(b, t)] = LayerNorm((t == 0 ? class_embedding : patch[b (tokens - 1) + t - 1]) + position_embedding[t])
+ *   * w + b for t < tokens: patch f32 [batch * (tokens - 1), hidden], position_embedding [tokens, hidden], y f32 [batch * tokens, hidden];
+ *   biased variance of the centred values, eps inside the square root (nn.LayerNorm: CLIPVisionEmbeddings + pre_layrnorm in one pass).
+ *   hidden % 4 == 0 and hidden <= 2048 (the row lives in registers), else MUSE_ERR_UNSUPPORTED; all pointers 16-byte aligned.
+ * muse_l2_normalize_rows: y[r] = x[r] / sqrt(sum_c x[r][c]^2) for x f32 [rows, cols] contiguous, then * mult when has_mult, then
+ *   * exp(*log_mult) when log_mult (a DEVICE pointer to one float: CLIPModel.logit_scale, no host read) is not NULL.  No epsilon: a
+ *   zero row becomes NaN, as x / x.norm(dim=-1, keepdim=True).  In place capable. */
+int muse_resize_bicubic_norm_f32(const float* x, float* out, int32_t B, int32_t R, int32_t I, const float* mean3, const float* std3,
+                                 void* stream);
+int muse_clip_patch_rows(const float* x, void* y, int32_t y_dtype, int32_t B, int32_t I, int32_t P, int32_t Kp, void* stream);
+int muse_clip_vision_embed_ln(const float* patch, const float* class_embedding, const float* position_embedding, const float* w,
+                              const float* b, float* y, int32_t batch, int32_t tokens, int32_t hidden, float eps, void* stream);
+int muse_l2_normalize_rows(const float* x, float* y, int64_t rows, int32_t cols, float mult, int32_t has_mult, const float* log_mult,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

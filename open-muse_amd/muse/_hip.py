@@ -211,6 +211,10 @@ SIGNATURES = {
     "muse_paella_out_block": [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p],
     "muse_spatial_norm_nhwc": [c_void_p] * 12 + [c_int] * 9 + [c_float, c_int, c_void_p],
     "muse_resize_crop_u8": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "muse_resize_bicubic_norm_f32": [c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), C.POINTER(c_float), c_void_p],
+    "muse_clip_patch_rows": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "muse_clip_vision_embed_ln": [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p],
+    "muse_l2_normalize_rows": [c_void_p, c_void_p, c_i64, c_int, c_float, c_int, c_void_p, c_void_p],
 }
 _RESTYPES = {"muse_embed_bwd_scratch_floats": c_i64, "muse_embed_bwd2_scratch_bytes": c_i64}
 

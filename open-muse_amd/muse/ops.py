@@ -2701,3 +2701,83 @@ def resize_crop_u8(packed, table, B, R, out=None, host_table=None):
     check(lib().muse_resize_crop_u8(packed.data_ptr(), table.data_ptr(), out.data_ptr(), B, R, stream()), "muse_resize_crop_u8")
     _prof_end(e0, "resize_crop_u8", _nbytes(packed, out), "byte")
     return out
+
+
+# ---- CLIP image tower (csrc/clip_vision.hip; muse.CLIPImageEncoder / muse.CLIPScorer): forward only -----------------------------------
+def resize_bicubic_norm(images, size, mean, std, out=None):
+    """images f32 [B, 3, R, R] -> f32 [B, 3, size, size] = (F.interpolate(images, (size, size), mode="bicubic", antialias=True) -
+    mean[c]) / std[c] in one launch, nothing clamped (muse_resize_bicubic_norm_f32; the value is spelled out in include/muse_hip.h).
+    mean / std: three Python floats each."""
+    require_gpu(images, out)
+    if images.dtype != torch.float32 or images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3] or not images.is_contiguous():
+        raise _hip.MuseHipError(f"resize_bicubic_norm: images is a contiguous f32 [B, 3, R, R] tensor, got {images.dtype} {tuple(images.shape)}")
+    B, R, size = int(images.shape[0]), int(images.shape[2]), int(size)
+    if B < 1 or R < 1 or size < 1 or len(mean) != 3 or len(std) != 3:
+        raise _hip.MuseHipError(f"resize_bicubic_norm: B, R and size are at least 1 and mean / std hold three floats, got B {B}, R {R}, size {size}")
+    if out is None:
+        out = torch.empty((B, 3, size, size), dtype=torch.float32, device=images.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, size, size) or not out.is_contiguous():
+        raise _hip.MuseHipError(f"resize_bicubic_norm: out is a contiguous f32 [B, 3, size, size] tensor, got {out.dtype} {tuple(out.shape)}")
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    e0 = _prof_begin()
+    check(lib().muse_resize_bicubic_norm_f32(images.data_ptr(), out.data_ptr(), B, R, size, m3, s3, stream()), "muse_resize_bicubic_norm_f32")
+    _prof_end(e0, "resize_bicubic_norm", _nbytes(images, out), "byte")
+    return _touched(out)
+
+
+def clip_patch_rows(pixel_values, patch, out_dtype=torch.float32, out=None):
+    """pixel_values f32 [B, 3, I, I] -> [B * G * G, Kp] (f32 or bf16), G = I / patch, Kp = 3 patch^2 rounded up to a multiple of 8:
+    row (b, gy, gx), column (c, ky, kx) - the flattening of Conv2d(3, H, patch, stride=patch).weight; columns >= 3 patch^2 are zeros"""
+    require_gpu(pixel_values, out)
+    if (pixel_values.dtype != torch.float32 or pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or pixel_values.shape[2] != pixel_values.shape[3]
+            or not pixel_values.is_contiguous()):
+        raise _hip.MuseHipError(f"clip_patch_rows: pixel_values is a contiguous f32 [B, 3, I, I] tensor, got {pixel_values.dtype} {tuple(pixel_values.shape)}")
+    B, I, P = int(pixel_values.shape[0]), int(pixel_values.shape[2]), int(patch)
+    if B < 1 or P < 1 or I % P:
+        raise _hip.MuseHipError(f"clip_patch_rows: the image side {I} is a multiple of the patch side {P}, and the batch is not empty")
+    G, Kp = I // P, (3 * P * P + 7) & ~7
+    if out is None:
+        out = torch.empty((B * G * G, Kp), dtype=out_dtype, device=pixel_values.device)
+    elif out.dtype not in (torch.float32, torch.bfloat16) or tuple(out.shape) != (B * G * G, Kp) or not out.is_contiguous():
+        raise _hip.MuseHipError(f"clip_patch_rows: out is a contiguous f32 / bf16 [{B * G * G}, {Kp}] tensor, got {out.dtype} {tuple(out.shape)}")
+    e0 = _prof_begin()
+    check(lib().muse_clip_patch_rows(pixel_values.data_ptr(), out.data_ptr(), dt(out), B, I, P, Kp, stream()), "muse_clip_patch_rows")
+    _prof_end(e0, "clip_patch_rows", _nbytes(pixel_values, out), "byte")
+    return _touched(out)
+
+
+def clip_vision_embed_ln(patch, class_embedding, position_embedding, w, b, eps, batch):
+    """patch f32 [batch * (T - 1), H], class_embedding [H], position_embedding [T, H], w / b [H] -> f32 [batch * T, H]:
+    row (b, 0) = LN(class + pos[0]), row (b, t) = LN(patch[b, t - 1] + pos[t]), each * w + b, in one pass"""
+    require_gpu(patch, class_embedding, position_embedding, w, b)
+    T, H = position_embedding.shape
+    for name, t, shape in (("patch", patch, (batch * (T - 1), H)), ("class_embedding", class_embedding, (H,)),
+                           ("position_embedding", position_embedding, (T, H)), ("w", w, (H,)), ("b", b, (H,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _hip.MuseHipError(f"clip_vision_embed_ln: {name} is a contiguous f32 {shape} tensor, got {t.dtype} {tuple(t.shape)}")
+    y = torch.empty((batch * T, H), dtype=torch.float32, device=patch.device)
+    e0 = _prof_begin()
+    check(lib().muse_clip_vision_embed_ln(patch.data_ptr(), class_embedding.data_ptr(), position_embedding.data_ptr(), w.data_ptr(),
+                                          b.data_ptr(), y.data_ptr(), batch, T, H, eps, stream()), "muse_clip_vision_embed_ln")
+    _prof_end(e0, "clip_vision_embed_ln", _nbytes(patch, position_embedding, y), "byte")
+    return y
+
+
+def l2_normalize_rows(x, mult=None, log_mult=None, out=None):
+    """x f32 [N, D] -> x / ||x||_2 per row (* mult, a Python float) (* exp(log_mult), a one-element f32 DEVICE tensor: no host read).
+    No epsilon: a zero row becomes NaN, as x / x.norm(dim=-1, keepdim=True)."""
+    require_gpu(x, log_mult, out)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise _hip.MuseHipError(f"l2_normalize_rows: x is a contiguous f32 [rows, cols] tensor, got {x.dtype} {tuple(x.shape)}")
+    if log_mult is not None and (log_mult.dtype != torch.float32 or log_mult.numel() != 1):
+        raise _hip.MuseHipError("l2_normalize_rows: log_mult is a one-element f32 tensor")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous():
+        raise _hip.MuseHipError("l2_normalize_rows: out is a contiguous f32 tensor of x's shape")
+    N, D = x.shape
+    e0 = _prof_begin()
+    check(lib().muse_l2_normalize_rows(x.data_ptr(), out.data_ptr(), N, D, 1.0 if mult is None else float(mult), 0 if mult is None else 1,
+                                       ptr(log_mult), stream()), "muse_l2_normalize_rows")
+    _prof_end(e0, "l2_normalize_rows", _nbytes(x, out), "byte")
+    return _touched(out)

@@ -170,6 +170,8 @@ class PipelineMuse:
         return ids, intermediate
 
     def _decode(self, ids, output_type):
+        if output_type == "pt":     # the clamped [B, 3, H, W] f32 tensor, still on the device (muse.CLIPScorer takes it as it is)
+            return torch.clamp(self.vae.decode_code(ids), 0.0, 1.0).float().contiguous()
         images = torch.clamp(self.vae.decode_code(ids), 0.0, 1.0).permute(0, 2, 3, 1).float().cpu().numpy()
         if output_type == "np":
             return images
