@@ -272,7 +272,9 @@ int muse_soft_ce_bwd(const float* logits, const int64_t* labels, const float* so
                      int32_t K, int64_t ld, int64_t ldo, void* stream);
 
 /* AdamW over one flat f32 buffer (torch.optim.AdamW / apex FusedAdam(adam_w_mode) semantics,
- * training/train_maskgit_imagenet.py:242-261,438); optionally refreshes the bf16 compute copy of the weights. */
+ * training/train_maskgit_imagenet.py:242-261,438); optionally refreshes the bf16 compute copy of the weights.  p, g, m, v 16-byte
+ * aligned, p_bf16 (when given) 8-byte aligned: MUSE_ERR_ALIGN otherwise, nothing launched.  The arithmetic of one element is pinned,
+ * rounding by rounding, at adam_update1 of csrc/optim.hip and is the same in every AdamW entry point. */
 int muse_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int32_t step, float grad_scale, const int32_t* skip, void* stream);
 /* Exponential moving average of the weights, every tracked tensor in ONE launch (EMAModel.step, reference muse/modeling_ema.py:118-137,

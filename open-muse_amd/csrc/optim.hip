@@ -57,26 +57,36 @@ static int adam_fill_groups(AdamGroups& G, const float* hyper, int ngroups, int 
 }
 
 // ---- device: the update of one element ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void adam_update1(float& pp, float gr, float& mm, float& vv, const AdamHyper& h) {
-  pp = pp * h.decay;                               // param.mul_(1 - lr * weight_decay), factor rounded once on the host
-  mm = fmaf(h.omb1, gr - mm, mm);                  // exp_avg.lerp_(grad, 1 - beta1)
-  vv = fmaf(h.omb2, gr * gr, vv * h.b2);           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-  const float denom = sqrtf(vv) / h.bc2_sqrt + h.eps;
-  pp = pp - h.step_size * (mm / denom);            // param.addcdiv_(exp_avg, denom, value=-step_size)
-}
-// The gradient factor.  DEV = false (the host's grad_scale, a kernel argument): the plain product, which the compiler contracts into the
-// `gr - m` that follows (one fma on the unrounded product; invisible for a power of two, what grad_scale is).  DEV = true (the *_dev entry
-// points: the factor is read from device memory, grad_scale * clip coefficient written by muse_gradnorm_finalize): the product is rounded
-// once and that value goes into the update - "scale inside the kernel" and "scale the buffer, then step" are the same bits.
+// Every rounding is written out: the statements below run with contraction OFF, each `fmaf` is one fused multiply-add (one rounding) and
+// every other operator rounds its own result to f32.  sqrtf and `/` are the correctly rounded sequences, f32 denormals are kept.
+//   gr = round(g * s)                                  the gradient times its factor
+//   d  = round(gr - m)          (device factor)        |  fma(g, s, -m)   (host factor: the unrounded product, one rounding)
+//   m' = fma(omb1, d, m)                               exp_avg.lerp_(grad, 1 - beta1)
+//   v' = fma(omb2, round(gr * gr), round(v * b2))      exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+//   denom = round(round(sqrt(v') / bc2_sqrt) + eps)
+//   p' = fma(decay, p, round(-step_size * round(m' / denom)))
+// The last line is NOT param.mul_(1 - lr * weight_decay) followed by param.addcdiv_: the decayed parameter is never rounded on its own.
+// It is what the compiler made of the two source statements before the roundings were written down, kept so that no weight changes; it
+// is the more accurate of the two (one rounding less).
+// The host-factor form fuses g * s into the difference only (invisible for a power of two, which the host's grad_scale is); the device
+// factor (grad_scale * clip coefficient written by muse_gradnorm_finalize) is applied as one rounded product everywhere, so "scale
+// inside the kernel" and "scale the buffer, then step" are the same bits.  adam_quad and adam_one both run exactly this.
 template <bool DEV> __device__ __forceinline__ float grad_times(float g, float s) {
-  if constexpr (DEV) {
 #pragma clang fp contract(off)
-    float r = g * s;
-    asm volatile("" : "+v"(r));
-    return r;
-  } else {
-    return g * s;
-  }
+  float r = g * s;
+  if constexpr (DEV) asm volatile("" : "+v"(r));  // (no longer needed for the rounding: it keeps the *_dev kernels' instruction selection as it was)
+  return r;
+}
+template <bool DEV> __device__ __forceinline__ void adam_update1(float& pp, float g, float s, float& mm, float& vv, const AdamHyper& h) {
+#pragma clang fp contract(off)
+  const float gr = grad_times<DEV>(g, s);
+  const float d = DEV ? gr - mm : fmaf(g, s, -mm);
+  mm = fmaf(h.omb1, d, mm);
+  const float g2 = gr * gr, vb = vv * h.b2;
+  vv = fmaf(h.omb2, g2, vb);
+  const float denom = sqrtf(vv) / h.bc2_sqrt + h.eps;
+  const float t = -h.step_size * (mm / denom);     // (the sign on the uniform factor: negating m or t costs a vector instruction)
+  pp = fmaf(h.decay, pp, t);
 }
 // the kernel argument that carries the factor: the value itself, or (DEV) where to read it on the device
 template <bool DEV> using GradFactor = std::conditional_t<DEV, const float*, float>;
@@ -96,7 +106,7 @@ template <bool DEV> __device__ __forceinline__ void adam_quad(float* __restrict_
   float pp[4], gg[4], mm[4], vv[4];
   V4<float>::load(p + i, pp); V4<float>::load(g + i, gg); V4<float>::load(m + i, mm); V4<float>::load(v + i, vv);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) adam_update1(pp[j], grad_times<DEV>(gg[j], gscale), mm[j], vv[j], h);
+  for (int j = 0; j < 4; ++j) adam_update1<DEV>(pp[j], gg[j], gscale, mm[j], vv[j], h);
   V4<float>::store(p + i, pp); V4<float>::store(m + i, mm); V4<float>::store(v + i, vv);
   if (im.pb && im.half) {
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -115,7 +125,7 @@ template <bool DEV> __device__ __forceinline__ void adam_quad(float* __restrict_
 template <bool DEV> __device__ __forceinline__ void adam_one(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                              float* __restrict__ v, const AdamImage& im, long i, const AdamHyper& h, float gscale) {
   float pp = p[i], mm = m[i], vv = v[i];
-  adam_update1(pp, grad_times<DEV>(g[i], gscale), mm, vv, h);
+  adam_update1<DEV>(pp, g[i], gscale, mm, vv, h);
   p[i] = pp; m[i] = mm; v[i] = vv;
   if (im.pb && im.half) {
     ((_Float16*)im.pb)[i] = (_Float16)pp;
@@ -232,6 +242,7 @@ static int adamw_flat_launch(float* p, const float* g, float* m, float* v, void*
                              float weight_decay, int32_t step, float grad_scale, const float* scale_dev, const int32_t* skip, void* stream) {
   if (n <= 0) return 0;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return MUSE_ERR_ALIGN;
+  if (p_bf16 && (((uintptr_t)p_bf16) & 7)) return MUSE_ERR_ALIGN;
   const AdamHyper h = adam_hyper(lr, beta1, beta2, eps, weight_decay, step);
   const dim3 grid(ew_grid((n + 3) / 4));
   if (scale_dev)
