@@ -13,14 +13,13 @@ Outputs are float32 in both.
 """
 from __future__ import annotations
 
-import json
-import os
 from collections import OrderedDict
 
 import torch
 from torch import nn
 
 from . import ops
+from ._tower import TowerMixin, materialised_attention, read_checkpoint, write_checkpoint
 from .modeling_utils import FrozenDict, ModelMixin
 
 _DEFAULTS = dict(vocab_size=49408, hidden_size=512, intermediate_size=2048, projection_dim=512, num_hidden_layers=12, num_attention_heads=8,
@@ -109,7 +108,7 @@ class _TextModel(nn.Module):
         self.final_layer_norm = _Weight((cfg["hidden_size"],), True)
 
 
-class CLIPTextEncoder(ModelMixin):
+class CLIPTextEncoder(TowerMixin, ModelMixin):
     _cast_selects_compute_mode = True
 
     def __init__(self, config=None, **kwargs):
@@ -159,44 +158,12 @@ class CLIPTextEncoder(ModelMixin):
     def with_projection(self):
         return hasattr(self, "text_projection")
 
-    # ---- modes and packed operands --------------------------------------------------------------------------------------------------
-    def set_compute_dtype(self, dtype):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("CLIPTextEncoder computes in torch.float32 (exact) or torch.bfloat16; there is no bf16x3 / f16 mode")
-        self.compute_dtype = dtype
-        self._packed.clear()
-        return self
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._packed.clear()
-        for p in self.parameters():
-            if p.dtype != torch.float32:
-                raise ops._hip.MuseHipError("master parameters stay float32 (compute precision is selected with set_compute_dtype)")
-        return out
-
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """keys with or without the `text_model.` prefix; tensors become float32 masters (`assign=True` adopts a float32 tensor itself
         instead of copying it, as nn.Module's does)"""
         out = super().load_state_dict({_key(k): v.to(torch.float32) for k, v in state_dict.items()}, strict=strict, assign=assign)
         self._packed.clear()
         return out
-
-    def _w(self, key, make):
-        """operand of a product in the compute dtype, built once (dropped when weights are loaded / moved or the mode changes)"""
-        hit = self._packed.get(key)
-        if hit is None:
-            t = make()
-            hit = self._packed[key] = ops.cast_to_bf16(t.contiguous()) if self.compute_dtype == torch.bfloat16 else t.contiguous()
-        return hit
-
-    def _qkv(self, i, att):
-        """q | k | v projections as ONE packed [3H, H] operand and [3H] bias"""
-        w = self._w((i, "qkv"), lambda: torch.cat([att.q_proj.weight.data, att.k_proj.weight.data, att.v_proj.weight.data], 0))
-        b = self._packed.get((i, "qkv_b"))
-        if b is None:
-            b = self._packed[(i, "qkv_b")] = torch.cat([att.q_proj.bias.data, att.k_proj.bias.data, att.v_proj.bias.data], 0)
-        return w, b
 
     # ---- forward ------------------------------------------------------------------------------------------------------------------
     def _attention(self, qkv, B, S, nh, hd):
@@ -205,14 +172,8 @@ class CLIPTextEncoder(ModelMixin):
         if qkv.dtype == torch.bfloat16:
             return ops.causal_attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, nh, hd, alpha)
         ld = (S + 3) & ~3       # a k-contiguous f32 operand's rows are padded to 16 bytes; the softmax writes the pad columns as 0
-        scores = torch.empty((B * nh, S, ld), dtype=torch.float32, device=qkv.device)
-        ops.gemm(qkv, qkv, scores, S, S, hd, la=0, lb=0, lda=3 * H, ldb=3 * H, ldc=ld, b_off=H, alpha=alpha, batch=B * nh, zdiv=nh,
-                 sA=(S * 3 * H, hd), sB=(S * 3 * H, hd), sC=(nh * S * ld, S * ld))
-        ops.causal_softmax_(scores, B * nh, S, ld)
-        ctx = torch.empty((B * S, H), dtype=torch.float32, device=qkv.device)
-        ops.gemm(scores, qkv, ctx, S, hd, S, la=0, lb=1, lda=ld, ldb=3 * H, ldc=H, b_off=2 * H, batch=B * nh, zdiv=nh,
-                 sA=(nh * S * ld, S * ld), sB=(S * 3 * H, hd), sC=(S * H, hd))
-        return ctx
+        return materialised_attention(qkv, B, S, nh, hd, alpha=alpha, ld=ld, softmax=lambda scores: ops.causal_softmax_(scores, B * nh, S, ld),
+                                      ctx_dtype=torch.float32)
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, return_dict=None, output_hidden_states=None):
@@ -278,24 +239,11 @@ class CLIPTextEncoder(ModelMixin):
         """a LOCAL transformers directory: config.json + model.safetensors or pytorch_model.bin.  Keyword arguments override config
         entries (`projection_dim=768`, training/train_muse.py:337); one that contradicts the stored `text_projection` raises.  The tower
         carries a projection iff the checkpoint stores one (`with_projection=False` drops it: the reference's CLIPTextModel branch)."""
-        path = str(pretrained_model_name_or_path)
-        if subfolder:
-            path = os.path.join(path, subfolder)
         torch_dtype = config_overrides.pop("torch_dtype", None)
         want_projection = config_overrides.pop("with_projection", None)     # False = CLIPTextModel of a checkpoint that stores a projection
-        if not os.path.isfile(os.path.join(path, "config.json")):
-            raise EnvironmentError(f"Error no file named config.json found in directory {path}.")
-        with open(os.path.join(path, "config.json"), "r", encoding="utf-8") as f:
-            cfg = json.load(f)
+        path, cfg, sd = read_checkpoint(pretrained_model_name_or_path, subfolder)
         if "text_config" in cfg and "hidden_size" not in cfg:       # a full CLIPModel config: the text tower's part
             cfg = dict(cfg["text_config"], projection_dim=cfg.get("projection_dim", cfg["text_config"].get("projection_dim")))
-        if os.path.isfile(os.path.join(path, "model.safetensors")):
-            from safetensors.torch import load_file
-            sd = load_file(os.path.join(path, "model.safetensors"))
-        elif os.path.isfile(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        else:
-            raise EnvironmentError(f"Error no file named model.safetensors or pytorch_model.bin found in directory {path}.")
         if not any(k.startswith(("vision_model.", "visual_projection.", "logit_scale")) for k in sd):
             sd = {_key(k): v for k, v in sd.items()}
         sd = {k: v for k, v in sd.items() if k.startswith("text_model.") and not k.endswith("position_ids") or k == "text_projection.weight"}
@@ -317,11 +265,4 @@ class CLIPTextEncoder(ModelMixin):
 
     def save_pretrained(self, save_directory, **kwargs):
         """config.json + model.safetensors as transformers writes them: `CLIPTextModel[WithProjection].from_pretrained` loads the directory"""
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {k: v for k, v in self.config.items() if not k.startswith("_") and k != "torch_dtype"}    # the source config's spelling of `dtype`
-        cfg["dtype"] = "float32"
-        with open(os.path.join(save_directory, "config.json"), "w", encoding="utf-8") as f:
-            f.write(json.dumps(cfg, indent=2, sort_keys=True) + "\n")
-        save_file({k: v.detach().to("cpu").contiguous().clone() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
+        write_checkpoint(save_directory, self.config, self.state_dict())

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from . import ops
+from ._tower import TowerMixin, materialised_attention, read_checkpoint, write_checkpoint
 from .modeling_clip_text import CLIPTextOutput, _Encoder, _Weight
 from .modeling_utils import FrozenDict, ModelMixin
 
@@ -69,7 +70,7 @@ class _VisionModel(nn.Module):
         self.post_layernorm = _Weight((H,), True)
 
 
-class CLIPImageEncoder(ModelMixin):
+class CLIPImageEncoder(TowerMixin, ModelMixin):
     _cast_selects_compute_mode = True
 
     def __init__(self, config=None, **kwargs):
@@ -131,22 +132,6 @@ class CLIPImageEncoder(ModelMixin):
     def tokens(self):
         return (int(self.config.image_size) // int(self.config.patch_size)) ** 2 + 1
 
-    # ---- modes and packed operands --------------------------------------------------------------------------------------------------
-    def set_compute_dtype(self, dtype):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("CLIPImageEncoder computes in torch.float32 (exact) or torch.bfloat16; there is no bf16x3 / f16 mode")
-        self.compute_dtype = dtype
-        self._packed.clear()
-        return self
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._packed.clear()
-        for p in self.parameters():
-            if p.dtype != torch.float32:
-                raise ops._hip.MuseHipError("master parameters stay float32 (compute precision is selected with set_compute_dtype)")
-        return out
-
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """keys with or without the `vision_model.` prefix; a missing `logit_scale` keeps ln(1 / 0.07); tensors become float32 masters"""
         sd = {_key(k): v.to(torch.float32) for k, v in state_dict.items() if not k.endswith("position_ids")}
@@ -155,22 +140,6 @@ class CLIPImageEncoder(ModelMixin):
         out = super().load_state_dict(sd, strict=strict, assign=assign)
         self._packed.clear()
         return out
-
-    def _w(self, key, make):
-        """operand of a product in the compute dtype, built once (dropped when weights are loaded / moved or the mode changes)"""
-        hit = self._packed.get(key)
-        if hit is None:
-            t = make()
-            hit = self._packed[key] = ops.cast_to_bf16(t.contiguous()) if self.compute_dtype == torch.bfloat16 else t.contiguous()
-        return hit
-
-    def _qkv(self, i, att):
-        """q | k | v projections as ONE packed [3H, H] operand and [3H] bias"""
-        w = self._w((i, "qkv"), lambda: torch.cat([att.q_proj.weight.data, att.k_proj.weight.data, att.v_proj.weight.data], 0))
-        b = self._packed.get((i, "qkv_b"))
-        if b is None:
-            b = self._packed[(i, "qkv_b")] = torch.cat([att.q_proj.bias.data, att.k_proj.bias.data, att.v_proj.bias.data], 0)
-        return w, b
 
     def _patch_weight(self):
         """Conv2d(3, H, P, stride=P).weight flattened to [H, 3 P P] and zero-padded to the operand width of ops.clip_patch_rows"""
@@ -188,14 +157,8 @@ class CLIPImageEncoder(ModelMixin):
         if qkv.dtype == torch.bfloat16:
             return ops.attention_fwd_ex(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, S, nh, hd, alpha)[0]
         ld = (S + 3) & ~3       # a k-contiguous f32 operand's rows are padded to 16 bytes; the softmax writes the pad columns as 0
-        scores = torch.empty((B * nh, S, ld), dtype=torch.float32, device=qkv.device)
-        ops.gemm(qkv, qkv, scores, S, S, hd, la=0, lb=0, lda=3 * H, ldb=3 * H, ldc=ld, b_off=H, alpha=alpha, batch=B * nh, zdiv=nh,
-                 sA=(S * 3 * H, hd), sB=(S * 3 * H, hd), sC=(nh * S * ld, S * ld))
-        ops.softmax_(scores, B * nh * S, S, ld)
-        ctx = torch.empty((B * S, H), dtype=torch.float32, device=qkv.device)
-        ops.gemm(scores, qkv, ctx, S, hd, S, la=0, lb=1, lda=ld, ldb=3 * H, ldc=H, b_off=2 * H, batch=B * nh, zdiv=nh,
-                 sA=(nh * S * ld, S * ld), sB=(S * 3 * H, hd), sC=(S * H, hd))
-        return ctx
+        return materialised_attention(qkv, B, S, nh, hd, alpha=alpha, ld=ld, softmax=lambda scores: ops.softmax_(scores, B * nh * S, S, ld),
+                                      ctx_dtype=torch.float32)
 
     @torch.no_grad()
     def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None, interpolate_pos_encoding=False):
@@ -273,26 +236,9 @@ class CLIPImageEncoder(ModelMixin):
         """a LOCAL transformers directory: config.json + model.safetensors or pytorch_model.bin (one file: sharded checkpoints are
         refused) - a vision-only checkpoint or a full CLIPModel one (`vision_config`, prefixed keys; its text tower is dropped).  A
         preprocessor_config.json next to it supplies `image_mean` / `image_std`.  Keyword arguments override config entries."""
-        path = str(pretrained_model_name_or_path)
-        if subfolder:
-            path = os.path.join(path, subfolder)
-        if not os.path.isfile(os.path.join(path, "config.json")):
-            raise EnvironmentError(f"Error no file named config.json found in directory {path}.")
-        with open(os.path.join(path, "config.json"), "r", encoding="utf-8") as f:
-            cfg = json.load(f)
-        sharded = [n for n in ("model.safetensors.index.json", "pytorch_model.bin.index.json") if os.path.isfile(os.path.join(path, n))]
-        if sharded:
-            raise NotImplementedError(f"CLIPImageEncoder: {path} holds a sharded checkpoint ({sharded[0]}), which is outside the MI355X "
-                                      "hot-path build: save the encoder as one model.safetensors")
+        path, cfg, sd = read_checkpoint(pretrained_model_name_or_path, subfolder, refuse_sharded=cls.__name__)
         if "vision_config" in cfg and "hidden_size" not in cfg:       # a full CLIPModel config: the image tower's part
             cfg = dict(cfg["vision_config"], projection_dim=cfg.get("projection_dim", cfg["vision_config"].get("projection_dim")))
-        if os.path.isfile(os.path.join(path, "model.safetensors")):
-            from safetensors.torch import load_file
-            sd = load_file(os.path.join(path, "model.safetensors"))
-        elif os.path.isfile(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        else:
-            raise EnvironmentError(f"Error no file named model.safetensors or pytorch_model.bin found in directory {path}.")
         if any(k.startswith(("text_model.", "text_projection.")) for k in sd):
             sd = {k: v for k, v in sd.items() if k.startswith(_OWN)}
         pre = os.path.join(path, "preprocessor_config.json")
@@ -313,21 +259,13 @@ class CLIPImageEncoder(ModelMixin):
     def save_pretrained(self, save_directory, **kwargs):
         """config.json + model.safetensors in the vision-only layout (`CLIPVisionModelWithProjection.from_pretrained` loads the directory;
         it ignores the extra `logit_scale`), and the preprocessor_config.json that carries image_mean / image_std"""
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {k: v for k, v in self.config.items() if not k.startswith("_") and k != "torch_dtype"}
-        cfg["dtype"] = "float32"
-        with open(os.path.join(save_directory, "config.json"), "w", encoding="utf-8") as f:
-            f.write(json.dumps(cfg, indent=2, sort_keys=True) + "\n")
+        write_checkpoint(save_directory, self.config, self.state_dict())
         size = int(self.config.image_size)
         pre = dict(image_processor_type="CLIPImageProcessor", do_resize=True, size={"shortest_edge": size}, resample=3, do_center_crop=True,
                    crop_size={"height": size, "width": size}, do_rescale=True, rescale_factor=1.0 / 255.0, do_normalize=True,
                    image_mean=list(self.image_mean), image_std=list(self.image_std), do_convert_rgb=True)
         with open(os.path.join(save_directory, "preprocessor_config.json"), "w", encoding="utf-8") as f:
             f.write(json.dumps(pre, indent=2, sort_keys=True) + "\n")
-        save_file({k: v.detach().to("cpu").contiguous().clone() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
-
 
 # ---- the score ----------------------------------------------------------------------------------------------------------------------
 def clip_scores(image_embeds, text_embeds, logit_scale=None):

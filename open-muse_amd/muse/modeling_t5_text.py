@@ -19,15 +19,14 @@ Outputs are float32 in both.
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 from collections import OrderedDict
 
 import torch
 from torch import nn
 
 from . import ops
+from ._tower import TowerMixin, materialised_attention, read_checkpoint, write_checkpoint
 from .modeling_utils import FrozenDict, ModelMixin
 
 _DEFAULTS = dict(vocab_size=32128, d_model=512, d_kv=64, d_ff=2048, num_layers=6, num_heads=8, relative_attention_num_buckets=32,
@@ -126,7 +125,7 @@ class _Stack(nn.Module):
 _EMBED_KEYS = ("shared.weight", "encoder.embed_tokens.weight")
 
 
-class T5TextEncoder(ModelMixin):
+class T5TextEncoder(TowerMixin, ModelMixin):
     _cast_selects_compute_mode = True
 
     def __init__(self, config=None, **kwargs):
@@ -171,22 +170,6 @@ class T5TextEncoder(ModelMixin):
             else:
                 nn.init.normal_(p.data, std=f * p.shape[1] ** -0.5)
 
-    # ---- modes and packed operands --------------------------------------------------------------------------------------------------
-    def set_compute_dtype(self, dtype):
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("T5TextEncoder computes in torch.float32 (exact) or torch.bfloat16; there is no bf16x3 / f16 mode")
-        self.compute_dtype = dtype
-        self._packed.clear()
-        return self
-
-    def _apply(self, fn, recurse=True):
-        out = super()._apply(fn, recurse)
-        self._packed.clear()
-        for p in self.parameters():
-            if p.dtype != torch.float32:
-                raise ops._hip.MuseHipError("master parameters stay float32 (compute precision is selected with set_compute_dtype)")
-        return out
-
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         """the token embedding under either of its two names or both; tensors become float32 masters (`assign=True` adopts a float32
         tensor itself instead of copying it, as nn.Module's does)"""
@@ -202,14 +185,6 @@ class T5TextEncoder(ModelMixin):
         out = super().load_state_dict(sd, strict=strict, assign=assign)
         self._packed.clear()
         return out
-
-    def _w(self, key, make):
-        """operand of a product in the compute dtype, built once (dropped when weights are loaded / moved or the mode changes)"""
-        hit = self._packed.get(key)
-        if hit is None:
-            t = make()
-            hit = self._packed[key] = ops.cast_to_bf16(t.contiguous()) if self.compute_dtype == torch.bfloat16 else t.contiguous()
-        return hit
 
     def _rel(self, S):
         """f32 [heads, 2 S - 1]: the bias of every head at every signed distance, gathered on the device from layer 0's table"""
@@ -229,14 +204,8 @@ class T5TextEncoder(ModelMixin):
             return ops.bias_attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], rel, B, S, nh, hd)
         # a k-contiguous operand's rows are padded to 16 bytes; the softmax writes the pad columns as 0
         ld = (S + 7) & ~7 if bf16 else (S + 3) & ~3
-        scores = torch.empty((B * nh, S, ld), dtype=torch.float32, device=qkv.device)
-        ops.gemm(qkv, qkv, scores, S, S, hd, la=0, lb=0, lda=3 * H, ldb=3 * H, ldc=ld, b_off=H, batch=B * nh, zdiv=nh,
-                 sA=(S * 3 * H, hd), sB=(S * 3 * H, hd), sC=(nh * S * ld, S * ld))
-        probs = ops.bias_softmax_(scores, rel, B * nh, nh, S, ld, bf16_copy=bf16)
-        ctx = torch.empty((B * S, H), dtype=qkv.dtype, device=qkv.device)
-        ops.gemm(probs, qkv, ctx, S, hd, S, la=0, lb=1, lda=ld, ldb=3 * H, ldc=H, b_off=2 * H, batch=B * nh, zdiv=nh,
-                 sA=(nh * S * ld, S * ld), sB=(S * 3 * H, hd), sC=(S * H, hd))
-        return ctx
+        return materialised_attention(qkv, B, S, nh, hd, alpha=1.0, ld=ld, ctx_dtype=qkv.dtype,
+                                      softmax=lambda scores: ops.bias_softmax_(scores, rel, B * nh, nh, S, ld, bf16_copy=bf16))
 
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, return_dict=None, output_hidden_states=None):
@@ -284,24 +253,7 @@ class T5TextEncoder(ModelMixin):
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, torch_dtype=None, **config_overrides):
         """a LOCAL transformers directory: config.json + model.safetensors or pytorch_model.bin (one file: sharded checkpoints are
         refused).  A full T5 checkpoint's decoder and lm_head are dropped.  Keyword arguments override config entries."""
-        path = str(pretrained_model_name_or_path)
-        if subfolder:
-            path = os.path.join(path, subfolder)
-        if not os.path.isfile(os.path.join(path, "config.json")):
-            raise EnvironmentError(f"Error no file named config.json found in directory {path}.")
-        with open(os.path.join(path, "config.json"), "r", encoding="utf-8") as f:
-            cfg = json.load(f)
-        sharded = [n for n in ("model.safetensors.index.json", "pytorch_model.bin.index.json") if os.path.isfile(os.path.join(path, n))]
-        if sharded:
-            raise NotImplementedError(f"T5TextEncoder: {path} holds a sharded checkpoint ({sharded[0]}), which is outside the MI355X "
-                                      "hot-path build: save the encoder as one model.safetensors")
-        if os.path.isfile(os.path.join(path, "model.safetensors")):
-            from safetensors.torch import load_file
-            sd = load_file(os.path.join(path, "model.safetensors"))
-        elif os.path.isfile(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        else:
-            raise EnvironmentError(f"Error no file named model.safetensors or pytorch_model.bin found in directory {path}.")
+        _, cfg, sd = read_checkpoint(pretrained_model_name_or_path, subfolder, refuse_sharded=cls.__name__)
         sd = {k: v for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
         cfg.update(config_overrides)
         cfg.pop("architectures", None)
@@ -313,12 +265,5 @@ class T5TextEncoder(ModelMixin):
 
     def save_pretrained(self, save_directory, **kwargs):
         """config.json + model.safetensors as transformers writes them: `T5EncoderModel.from_pretrained` loads the directory"""
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {k: v for k, v in self.config.items() if not k.startswith("_") and k != "torch_dtype"}    # the source config's spelling of `dtype`
-        cfg["dtype"] = "float32"
-        with open(os.path.join(save_directory, "config.json"), "w", encoding="utf-8") as f:
-            f.write(json.dumps(cfg, indent=2, sort_keys=True) + "\n")
         # one tensor under two names: safetensors stores it once, under the name transformers keeps (`shared.weight`)
-        sd = {k: v.detach().to("cpu").contiguous().clone() for k, v in self.state_dict().items() if k != "encoder.embed_tokens.weight"}
-        save_file(sd, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
+        write_checkpoint(save_directory, self.config, {k: v for k, v in self.state_dict().items() if k != "encoder.embed_tokens.weight"})

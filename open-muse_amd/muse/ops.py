@@ -2409,7 +2409,7 @@ def probe_tr16(addr):
     return out
 
 
-# ---- CLIP text tower (csrc/clip_text.hip; muse.CLIPTextEncoder): forward only ------------------------------------------------------
+# ---- CLIP text tower (csrc/clip_text.hip, its fused attention csrc/attention_enc.hip; muse.CLIPTextEncoder): forward only ---------------
 def causal_attention_fwd(q, k, v, B, S, nh, hd, alpha, out=None):
     """fused causal softmax(alpha q k^T) v for q / k / v [B*S, H] bf16 views (row strides free: slices of one packed q | k | v
     projection; rows >= S of an image are never read) -> ctx [B*S, H] bf16.  No score matrix in memory."""
@@ -2468,7 +2468,7 @@ def eos_index(ids, eos_token_id):
     return idx, flat
 
 
-# ---- T5 text encoder (csrc/t5_text.hip; muse.T5TextEncoder): forward only -------------------------------------------------------------
+# ---- T5 text encoder (csrc/t5_text.hip, its fused attention csrc/attention_enc.hip; muse.T5TextEncoder): forward only -------------------
 def _rel_check(what, rel, nh, S):
     if rel.dtype != torch.float32 or not rel.is_contiguous() or tuple(rel.shape) != (nh, 2 * S - 1):
         raise _hip.MuseHipError(f"{what}: rel is a contiguous f32 [heads, 2 S - 1] = {(nh, 2 * S - 1)} tensor, got {rel.dtype} {tuple(rel.shape)}")

@@ -1,5 +1,5 @@
 """Plain torch restatement of the fused attention kernels' operation (csrc/attention.hip, attention2.hip, attention3.hip and the causal
-kernel of clip_text.hip), for tests/test_gpu_attention_edges.py and tests/test_attention_cpu.py.  Imports without a GPU.
+policy of attention_enc.hip), for tests/test_gpu_attention_edges.py and tests/test_attention_cpu.py.  Imports without a GPU.
 
 Four layers:
   * `reference`: ctx, lse, dq, dk, dv of softmax(alpha q k^T) v in float64 on the rounded inputs, full visibility or causal, and the

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the fused attention kernels (csrc/attention.hip, attention2.hip, attention3.hip and the causal kernel of clip_text.hip)
+"""GPU (-m gpu): the fused attention kernels (csrc/attention.hip, attention2.hip, attention3.hip and the causal policy of attention_enc.hip)
 with exact key probes and per-element bounds at every edge of their dispatch, B = 2 images x 3 heads, no sequence longer than 1025.
 tests/attention_cpu.py holds the float64 reference, the contract model, the probe builders and the checks; tests/test_attention_cpu.py
 proves on the CPU that those checks fail for a dropped key, a leaked pad key and a causal mask off by one.  profiles/attention_edges.md
@@ -35,7 +35,7 @@ Which case meets which branch (Sq x Skv; "self" = the SELF_LENS at all four head
     MUSE_ATTN2=1 and =0 (at 224 and 261 both settings must reach the general kernels)
   attention3.hip: 3 | 8 key blocks (Skv 65, 77, 96 | 225, 240, 256), one | several 256-query blocks (Sq 256 | 512), several key blocks
     (Skv 512) streamed (X3_STREAM) or as block pairs + merge
-  clip_text.hip causal kernel: S 1, 15, 16, 17, 32, 33, 77, 127, 128 (1 .. 8 waves; an odd number of key tiles; the S = 128 limit)
+  attention_enc.hip, causal policy: S 1, 15, 16, 17, 32, 33, 77, 127, 128 (1 .. 8 waves; an odd number of key tiles; the S = 128 limit)
 """
 import ctypes as C
 import functools

@@ -1,4 +1,4 @@
-"""GPU (MI355X): muse.CLIPTextEncoder and the kernels of csrc/clip_text.hip against transformers' own CLIP text model on the CPU.
+"""GPU (MI355X): muse.CLIPTextEncoder and the kernels of csrc/clip_text.hip and csrc/attention_enc.hip against transformers' own CLIP text model on the CPU.
 
 The tiny towers are built here from CLIPTextConfig under a fixed seed and made to behave like trained ones (2-D non-embedding
 weights x 4, biases ~ N(0, 0.1)): the softmax is not flat, so a missing or misplaced mask shows.  3 layers, intermediate = 4 x hidden,
@@ -196,7 +196,7 @@ def test_fused_causal_attention_kernel(heads, hd, S):
     A second run over image 0 alone, with the rows behind its last token NaN, must give the same bits.  That shows a V row >= S that
     reached the second product (0 * NaN) and nothing else: a K row >= S would be overwritten by the mask, a Q row >= S is never stored,
     and the caching allocator rounds a block up, so a read behind the tensor's last row need not fault.  That K, V and Q rows >= S
-    are not READ rests on the predicates `row < S` / `qr < S` in front of the three loads of causal_attn_kernel, checked by reading.
+    are not READ rests on the predicates `row < S` / `qr < S` in front of the three loads of enc::attn_kernel (csrc/attention_enc.hip), checked by reading.
     Measured on MI355X: rel_err 1.5e-3 .. 3.0e-3 (0 at S = 1)."""
     ops = _ops()
     B, H = 3, heads * hd

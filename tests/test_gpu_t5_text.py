@@ -1,4 +1,4 @@
-"""GPU (MI355X): muse.T5TextEncoder and the kernels of csrc/t5_text.hip against transformers' own T5EncoderModel on the CPU.
+"""GPU (MI355X): muse.T5TextEncoder and the kernels of csrc/t5_text.hip and csrc/attention_enc.hip against transformers' own T5EncoderModel on the CPU.
 
 The tiny encoders come from tests/t5_tiny.py (T5Config under a fixed seed, made to behave like trained ones: the bias table ~ N(0, 2),
 the other non-embedding 2-D weights x 2, norm weights 1 + 0.2 N(0, 1)): 3 layers, 2 heads of d_kv 64, d_ff 320, vocab 600, batch 3, with
@@ -132,7 +132,7 @@ def test_fused_bias_attention_kernel(heads, hd, S):
     is the last row of its storage, B * heads = 9 is odd, rel ~ N(0, 2).  No score scale.  Tolerance: rel_err < 1.5e-2, the bar the
     project sets for its bf16 fused forwards (bf16 P and bf16 output).  A second run over image 0 alone, with the rows behind its last
     token NaN, must give the same bits: a V row >= S that reached the second product (0 * NaN) would show.  That K, V and Q rows >= S
-    are not READ rests on the predicates `row < S` / `qr < S` in front of the three loads of bias_attn_kernel, checked by reading.
+    are not READ rests on the predicates `row < S` / `qr < S` in front of the three loads of enc::attn_kernel (csrc/attention_enc.hip), checked by reading.
     Measured on MI355X: rel_err 2.0e-3 .. 3.7e-3 (0 at S = 1); per case in MEASURED at the end of this file."""
     ops = _ops()
     B, H = 3, heads * hd
