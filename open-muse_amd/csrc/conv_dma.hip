@@ -302,9 +302,15 @@ __global__ __launch_bounds__(512, 2) void conv_dma_kernel(Params p) {
 //   into bit 2) and bit 2 of c' - eight per-lane base registers, everything else is the instruction's immediate offset.
 //   Pipeline per tap t (one K-tile): wait for the weights of tap t+1, barrier, then 48 MFMAs of tap t interleaved with the
 //   16 fragment reads of tap t+1 and the DMA of the weights of tap t+3 (+ in taps 0-2 a third of the next chunk's slab).
+//
+// The kernel has two forms - conv_slab_kernel (launch per tile) and conv_slab_persist_kernel (one workgroup per CU walks tiles) -
+// and ONE body: everything between here and conv_slab_kernel (the DMAs, the GroupNorm register path, the tile decode and per-lane
+// offsets, the fragment addresses, the K loop's SLAB_* slots and counted waits, the pooled window and the partial fold) is written
+// once and shared; the two __global__ functions are frames around it (prologue / tile walk, epilogue).
 namespace cslab {
 using g256::lds_read128;
 using g256::lds_void_t;
+using cdma::Frag16;
 using cdma::Params;
 using cdma::sw4;
 
@@ -315,8 +321,26 @@ constexpr int B_BASE = 2 * SLAB, BSTAGE = 16384;
 constexpr int CST = BN * 4 + 16;            // staged output row (epilogue)
 constexpr int LDS_BYTES = BM * CST;         // 135168 >= B_BASE + 3 * BSTAGE (135168)
 static_assert(B_BASE + 3 * BSTAGE <= LDS_BYTES, "LDS map");
+// the persistent form's LDS map (described at conv_slab_persist_kernel)
+constexpr int P_BUF1 = 92160, P_BBASE = 43008, P_STAGING = P_BUF1, P_HALF_ROWS = 128;
+constexpr int P_LDS_BYTES = P_STAGING + P_HALF_ROWS * CST;   // 159744
+// GN = true: two [2][Cin] f32 scale / shift tables behind the tile's map (this tile's image, the next tile's image): Cin <= 256
+constexpr int P_GSS = P_LDS_BYTES, P_GSS_MAX_CIN = 256, P_LDS_BYTES_GN = P_LDS_BYTES + 2 * 2 * P_GSS_MAX_CIN * 4;   // 163840 = all of it
+__host__ __device__ constexpr int p_stage_off(int st) { return st == 0 ? 32768 : (st - 1) * 16384; }   // relative to P_BBASE
+static_assert(P_BBASE + 3 * BSTAGE == P_BUF1 && P_BUF1 + SLAB <= P_LDS_BYTES && P_LDS_BYTES_GN <= 163840, "LDS map");
 
-struct Frag16 { bf16x8 ah[MI], al[MI], bh[NI], bl[NI]; };
+// What distinguishes the two forms inside the shared body: where slab buffer 1 and the weight ring sit in LDS, and what lies behind a
+// tile's last chunk (WALK: chunk 0 of the workgroup's next tile; otherwise nothing - out-of-bounds offsets, zero fill).
+struct LaunchMap {
+  static constexpr bool WALK = false;
+  static constexpr int BUF1 = SLAB, BBASE = B_BASE;
+  __host__ __device__ static constexpr int stage_off(int st) { return st * BSTAGE; }
+};
+struct WalkMap {
+  static constexpr bool WALK = true;
+  static constexpr int BUF1 = P_BUF1, BBASE = P_BBASE;
+  __host__ __device__ static constexpr int stage_off(int st) { return p_stage_off(st); }
+};
 
 #ifdef CDMA_TIMESTAMPS   // timing experiments (scripts/exp/conv_ts.py): per-block s_memtime stamps at the phase boundaries
 __device__ long* g_conv_ts = nullptr;
@@ -326,173 +350,202 @@ __device__ long* g_conv_ts = nullptr;
 #define CDMA_TS(IDX)
 #define CDMA_TSV(V, IDX)
 #endif
-// GN = true: GroupNorm + SiLU + the bf16x3 split of the INPUT happen here (muse/modeling_maskgit_vqgan.py:73-80: norm -> swish ->
-// conv).  The slab thirds are loaded as f32 into registers (same two vector-memory operations per third as the two plane DMAs,
-// so the counted waits keep their meaning; issued in taps 0 / 2 / 4 instead of 0 / 1 / 2), transformed two taps later - the
-// top-of-tap wait of tap s+2 leaves only tap s+1's operations outstanding - with the arithmetic of gn_apply_split8_kernel
-// (vqgan.hip; same bits) spread over that tap's MFMA slots, and written to the slab buffer in the layout the plane DMA produces.
-// Saves the write and the re-read of both planes (8 of the 12 bytes per element the unfused pair moves) and a launch.
-// POOL = true: the epilogue stores the 2 x 2 average of the tile (F.avg_pool2d(2, 2) of the output, DownsamplingBlock with
-// resample_with_conv = False) instead of the tile: out is [B, H/2, W/2, N] and the GroupNorm partials are those of the POOLED values.
-// Every 2 x 2 window lies inside one 16 x 16 patch; the full-resolution values and the order of the three adds are those of the
-// un-pooled epilogue followed by avgpool_stats_kernel (vqgan.hip): same bits, a quarter of the stores and no second pass.
-template <bool GN, bool POOL = false>
-__global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  CDMA_TS(0)
-  const int H = p.H, W = p.W, Cin = p.Cin;
-  const int tpr = W >> 4, tpi = (H >> 4) * tpr;     // patches per image row / per image
-  const int ntm = p.M >> 8, ntn = (p.N + BN - 1) / BN, ntiles = ntm * ntn;
-  const int bq = ntiles >> 3, br = ntiles & 7, xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
-  const int tid_ = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + bi;
-  const int mt = tid_ / ntn, n0 = (tid_ % ntn) * BN;
-  const int img = mt / tpi, prem = mt - img * tpi, ty = prem / tpr, tx = prem - ty * tpr;
-  const int y0 = ty << 4, x0 = tx << 4;
 
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
+// The shared body is TEXT (macros that expand inside the two kernels), not functions over a state struct: conv_slab_persist_kernel<true>
+// sits at 255 VGPRs, and only the same statements in the same order give hipcc the same instruction stream (profiles/conv_single_source.md).
+// Both kernels name `L` (LaunchMap / WalkMap), `GN` and `p`.
 
-  // ---- slab DMA: 21 pieces of 1 KiB per plane; wave w issues pieces w, w+8, w+16 of both planes (a piece index past 20
-  //      repeats the wave's previous piece: same bytes to the same place, keeps the per-wave DMA count uniform) ----
-  constexpr int XE = GN ? 4 : 2;             // bytes per activation element in global memory
-  const unsigned bytesA = (unsigned)((long)p.M * Cin * XE);
-  const rsrc_t rs_xh = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xh, bytesA), rs_xl = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xl, bytesA);
-  const unsigned oobA = (bytesA + 15u) & ~15u;
-  unsigned slab_off[3];
-  int slab_piece[3];
-  const int srcchunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);
-  {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      int piece = wave + 8 * k;
-      if (piece > 20) piece -= 8;
-      slab_piece[k] = piece;
-      const int r = piece * 16 + (lane >> 2), sy = r / 18, sx = r - sy * 18;
-      const int y = y0 - 1 + sy, x = x0 - 1 + sx;
-      const bool ok = r < 324 && y >= 0 && y < H && x >= 0 && x < W;
-      slab_off[k] = ok ? (unsigned)(((((long)img * H + y) * W + x) * Cin + srcchunk * 8) * XE) : oobA;
-    }
-  }
-  // GN: the image's scale / shift behind the tile's LDS map, [2][Cin] f32
-  float* const gss = (float*)(smem + LDS_BYTES);
-  if constexpr (GN) {
-    for (int c = threadIdx.x; c < Cin; c += NT) { gss[c] = p.gsc[(long)img * Cin + c]; gss[Cin + c] = p.gsh[(long)img * Cin + c]; }
-    __syncthreads();
-  }
-  u32x4 xr[2];                  // GN: the slab third in flight / being transformed (one at a time inside the K loop)
-  float scv[4], shv[4];
-  // third `k` of the slab of channel chunk `chunk`, f32, into registers (zero outside the image / past the last chunk)
-  auto issue_slab_f = [&](u32x4 (&r)[2], int k, int chunk) {
-    const unsigned vo = chunk * 32 < Cin ? slab_off[k] : oobA;
-    r[0] = buf_load16(rs_xh, vo, (unsigned)(chunk * 128));
-    r[1] = buf_load16(rs_xh, vo + 16u, (unsigned)(chunk * 128));
+// ---- SLAB_SETUP: problem geometry, wave roles, buffer descriptors, the tile decode.
+//      weight DMA (as in cdma): waves 0-3 the hi image, 4-7 the lo image, two 16-row pieces each per K-tile.
+//      geo_of: virtual block v -> tile (XCD-aware: the blocks of one XCD get consecutive tiles; the N-tiles of a patch run side by side) ----
+#define SLAB_SETUP                                                                                                                 \
+  const int H = p.H, W = p.W, Cin = p.Cin;                                                                                         \
+  const int tpr = W >> 4, tpi = (H >> 4) * tpr;                     /* patches per image row / per image */                        \
+  const int ntm = p.M >> 8, ntn = (p.N + BN - 1) / BN, ntiles = ntm * ntn;                                                         \
+  const int bq = ntiles >> 3, br = ntiles & 7;                                                                                     \
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                      \
+  const int wm = wave >> 1, wn = wave & 1;                                                                                         \
+  constexpr int XE = GN ? 4 : 2;                                    /* bytes per activation element in global memory */            \
+  const unsigned bytesA = (unsigned)((long)p.M * Cin * XE);                                                                        \
+  const rsrc_t rs_xh = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xh, bytesA), rs_xl = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xl, bytesA); \
+  const unsigned oobA = (bytesA + 15u) & ~15u;                                                                                     \
+  const int wimg = wave >> 2;                                                                                                      \
+  const unsigned bytesB = (unsigned)((long)p.N * p.K * 2);                                                                         \
+  const rsrc_t rs_w = make_rsrc(wimg ? p.wl : p.wh, bytesB);                                                                       \
+  const unsigned oobB = (bytesB + 15u) & ~15u;                                                                                     \
+  const int nchunks = Cin >> 5;                                                                                                    \
+  struct Geo { int img, prem, y0, x0, n0; };                                                                                       \
+  auto geo_of = [&](int v) {                                                                                                       \
+    const int xcd = v & 7, bi = v >> 3;                                                                                            \
+    const int tid_ = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + bi;                                           \
+    const int mt = tid_ / ntn;                                                                                                     \
+    Geo g;                                                                                                                         \
+    g.n0 = (tid_ - mt * ntn) * BN;                                                                                                 \
+    g.img = mt / tpi; g.prem = mt - g.img * tpi;                                                                                   \
+    const int ty = g.prem / tpr, tx = g.prem - ty * tpr;                                                                           \
+    g.y0 = ty << 4; g.x0 = tx << 4;                                                                                                \
+    return g;                                                                                                                      \
   };
-  // half `h` (four channels) of this lane's eight channels of chunk `chunk`
-  auto load_gss = [&](int chunk, int h) {
-    const float* q = gss + chunk * 32 + srcchunk * 8 + h * 4;
-#pragma unroll
+
+// chunk `chunk` of the K loop belongs to the current tile (the loop looks one chunk past the last one: WALK = chunk 0 of the next tile)
+#define SLAB_IN_TILE(chunk) (L::WALK ? (chunk) < nchunks : (chunk) * 32 < Cin)
 #ifndef GNX_CONST_SS      // (timing experiments, scripts/exp/conv_gn_variants.sh: what the scale / shift reads and the SiLU cost)
-    for (int j = 0; j < 4; ++j) { scv[j] = q[j]; shv[j] = q[Cin + j]; }
+#define GNX_SS(q, j) { scv[j] = (q)[j]; shv[j] = (q)[Cin + j]; }
 #else
-    for (int j = 0; j < 4; ++j) { scv[j] = 1.25f; shv[j] = 0.125f; }
-    (void)q;
+#define GNX_SS(q, j) { scv[j] = 1.25f; shv[j] = 0.125f; (void)(q); }
 #endif
-  };
-  // element e (0..7) of a third: GroupNorm affine + SiLU, exactly gn_apply_split8_kernel's expression; in place
-  auto xform_elem = [&](u32x4 (&r)[2], int e) {
-    float t = fmaf(__uint_as_float(r[e >> 2][e & 3]), scv[e & 3], shv[e & 3]);
 #ifndef GNX_NO_SILU
-    t = gn_silu(t);
+#define GNX_SILU(t) t = gn_silu(t);
+#else
+#define GNX_SILU(t)
 #endif
-    asm volatile("" : "+v"(t));   // the ROUNDED product is what gets split: no contraction of (x * r) - hi into one fma
-    r[e >> 2][e & 3] = __float_as_uint(t);
+
+// ---- SLAB_BODY: the lambdas of the K loop.  Expands after SLAB_SETUP and after the kernel has declared slab_off[3] / voffB[2] (the
+//      lane's DMA sources in this tile), slab_off_n[3] / voffB_n[2] (in the next tile; launch per tile: out of range), gss_cur /
+//      gss_nxt (GN: the [2][Cin] scale / shift tables of this and the next tile's image) and scv[4] / shv[4].
+//   slab_piece    slab DMA: 21 pieces of 1 KiB per plane; wave w issues pieces w, w+8, w+16 of both planes (a piece index past 20 repeats
+//                 the wave's previous piece: same bytes to the same place, keeps the per-wave DMA count uniform)
+//   offsets_of    lane ln's sources of tile g: the three slab thirds (out of range = zero fill: the SAME padding, rows past 323) and
+//                 the two weight rows; valid = false: a tile that does not exist, everything out of range
+//   issue_slab    third `k` of the slab of channel chunk `chunk` into buffer `buf`
+//   issue_b       weights of (chunk, tap) into ring stage `st`: k index = tap * Cin + chunk * 32
+//   GN = true: GroupNorm + SiLU + the bf16x3 split of the INPUT happen here (muse/modeling_maskgit_vqgan.py:73-80: norm -> swish -> conv).
+//   The slab thirds are loaded as f32 into registers (same two vector-memory operations per third as the two plane DMAs, so the counted
+//   waits keep their meaning; issued in taps 0 / 2 / 4 instead of 0 / 1 / 2), transformed two taps later - the top-of-tap wait of tap
+//   s+2 leaves only tap s+1's operations outstanding - with the arithmetic of gn_apply_split8_kernel (vqgan.hip; same bits) spread over
+//   that tap's MFMA slots, and written to the slab buffer in the layout the plane DMA produces.  Saves the write and the re-read of both
+//   planes (8 of the 12 bytes per element the unfused pair moves) and a launch.
+//   issue_slab_f  third `k` of the slab of chunk `chunk`, f32, into registers (zero outside the image / where there is no next tile)
+//   load_gss      scale / shift of half `h` (four channels) of this lane's eight channels of chunk `chunk`
+//   xform_elem    element e (0..7) of a third: GroupNorm affine + SiLU, exactly gn_apply_split8_kernel's expression; in place.  (The empty
+//                 asm: the ROUNDED product is what gets split: no contraction of (x * r) - hi into one fma)
+//   store_slab_f  hi / lo split of third k and its two 16-byte LDS writes (where the plane DMA would have put them); zero padding stays zero
+//   issue_gss     scale / shift of image `img` into table `dst`: 2 * Cin / 64 pieces of 64 floats, one LDS-DMA per wave (the pieces repeat)
+//   baseA, addrB  fragment read addresses (slab buffer 0); flip_base moves baseA to the other slab buffer and back ----
+#define SLAB_BODY                                                                                                                  \
+  int slab_piece[3];                                                                                                               \
+  _Pragma("unroll")                                                                                                                \
+  for (int k = 0; k < 3; ++k) { int piece = wave + 8 * k; if (piece > 20) piece -= 8; slab_piece[k] = piece; }                     \
+  const int srcchunkA = (lane & 3) ^ (((lane >> 4) & 1) << 1);                                                                     \
+  auto offsets_of = [&](const Geo& g, bool valid, unsigned (&so)[3], unsigned (&vb)[2], int ln) {                                  \
+    const int srcchunkA = (ln & 3) ^ (((ln >> 4) & 1) << 1);                                                                       \
+    const int srcchunkB = (ln & 3) ^ sw4((ln >> 4) & 3);                                                                           \
+    _Pragma("unroll")                                                                                                              \
+    for (int k = 0; k < 3; ++k) {                                                                                                  \
+      const int r = slab_piece[k] * 16 + (ln >> 2), sy = r / 18, sx = r - sy * 18;                                                 \
+      const int y = g.y0 - 1 + sy, x = g.x0 - 1 + sx;                                                                              \
+      const bool ok = valid && r < 324 && y >= 0 && y < H && x >= 0 && x < W;                                                      \
+      so[k] = ok ? (unsigned)(((((long)g.img * H + y) * W + x) * Cin + srcchunkA * 8) * XE) : oobA;                                \
+    }                                                                                                                              \
+    _Pragma("unroll")                                                                                                              \
+    for (int j = 0; j < 2; ++j) {                                                                                                  \
+      const int n = g.n0 + ((wave & 3) * 2 + j) * 16 + (ln >> 2);                                                                  \
+      vb[j] = (valid && n < p.N) ? (unsigned)(((long)n * p.K + srcchunkB * 8) * 2) : oobB;                                         \
+    }                                                                                                                              \
+  };                                                                                                                               \
+  auto issue_slab = [&](int buf, int k, int chunk) {                                                                               \
+    const bool cur = SLAB_IN_TILE(chunk);                                                                                          \
+    const unsigned vo = cur ? slab_off[k] : slab_off_n[k];                                                                         \
+    const int soff = L::WALK ? (cur ? chunk * 64 : 0) : chunk * 64;                                                                \
+    unsigned char* dst = smem + (buf ? L::BUF1 : 0) + slab_piece[k] * 1024;                                                        \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xh, (lds_void_t*)dst, 16, (int)vo, soff, 0, 0);                                    \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xl, (lds_void_t*)(dst + PLANE), 16, (int)vo, soff, 0, 0);                          \
+  };                                                                                                                               \
+  auto issue_b = [&](int st, int chunk, int tap) {                                                                                 \
+    const bool cur = SLAB_IN_TILE(chunk);                                                                                          \
+    const int soff = (tap * Cin + (L::WALK ? (cur ? chunk * 32 : 0) : chunk * 32)) * 2;                                            \
+    _Pragma("unroll")                                                                                                              \
+    for (int j = 0; j < 2; ++j)                                                                                                    \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_t*)(smem + L::BBASE + L::stage_off(st) + wimg * 8192 + ((wave & 3) * 2 + j) * 1024), \
+                                               16, (int)(cur ? voffB[j] : voffB_n[j]), soff, 0, 0);                                \
+  };                                                                                                                               \
+  auto issue_slab_f = [&](u32x4 (&r)[2], int k, int chunk) {                                                                       \
+    const bool cur = SLAB_IN_TILE(chunk);                                                                                          \
+    const unsigned vo = cur ? slab_off[k] : slab_off_n[k];                                                                         \
+    const unsigned soff = L::WALK ? (cur ? (unsigned)(chunk * 128) : 0u) : (unsigned)(chunk * 128);                                \
+    r[0] = buf_load16(rs_xh, vo, soff);                                                                                            \
+    r[1] = buf_load16(rs_xh, vo + 16u, soff);                                                                                      \
+  };                                                                                                                               \
+  auto load_gss = [&](int chunk, int h) {                                                                                          \
+    const float* q = (L::WALK ? (chunk < nchunks ? gss_cur + chunk * 32 : gss_nxt) : gss_cur + chunk * 32) + srcchunkA * 8 + h * 4; \
+    _Pragma("unroll")                                                                                                              \
+    for (int j = 0; j < 4; ++j) GNX_SS(q, j)                                                                                       \
+  };                                                                                                                               \
+  auto xform_elem = [&](u32x4 (&r)[2], int e) {                                                                                    \
+    float t = fmaf(__uint_as_float(r[e >> 2][e & 3]), scv[e & 3], shv[e & 3]);                                                     \
+    GNX_SILU(t)                                                                                                                    \
+    asm volatile("" : "+v"(t));                                                                                                    \
+    r[e >> 2][e & 3] = __float_as_uint(t);                                                                                         \
+  };                                                                                                                               \
+  auto store_slab_f = [&](u32x4 (&r)[2], int buf, int k, int chunk) {                                                              \
+    u32x4 hi4, lo4;                                                                                                                \
+    _Pragma("unroll")                                                                                                              \
+    for (int h = 0; h < 2; ++h) {                                                                                                  \
+      u32x2 hi, lo;                                                                                                                \
+      split4(r[h], hi, lo);                                                                                                        \
+      hi4[2 * h] = hi[0]; hi4[2 * h + 1] = hi[1];                                                                                  \
+      lo4[2 * h] = lo[0]; lo4[2 * h + 1] = lo[1];                                                                                  \
+    }                                                                                                                              \
+    if ((L::WALK ? (chunk < nchunks ? slab_off[k] : slab_off_n[k]) : slab_off[k]) == oobA) { hi4 = u32x4{0u, 0u, 0u, 0u}; lo4 = hi4; } \
+    unsigned char* dst = smem + (buf ? L::BUF1 : 0) + slab_piece[k] * 1024 + lane * 16;                                            \
+    *(u32x4*)dst = hi4;                                                                                                            \
+    *(u32x4*)(dst + PLANE) = lo4;                                                                                                  \
+  };                                                                                                                               \
+  auto issue_gss = [&](float* dst, int img) {                                                                                      \
+    const int npc = Cin >> 6, piece = wave % (2 * npc), isshift = piece >= npc ? 1 : 0, pc = piece - isshift * npc;                \
+    const int batch = p.M / (H * W);                                                                                               \
+    const rsrc_t rs = make_rsrc(isshift ? p.gsh : p.gsc, (unsigned)((long)batch * Cin * 4));                                       \
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(dst + isshift * Cin + pc * 64), 4, (int)((unsigned)((long)img * Cin + pc * 64 + lane) * 4u), 0, 0, 0); \
+  };                                                                                                                               \
+  unsigned baseA[4][2], addrB;                                                                                                     \
+  {                                                                                                                                \
+    const int pr = lane & 15, g = lane >> 4, P = 72 * wm + pr;                                                                     \
+    _Pragma("unroll")                                                                                                              \
+    for (int e = 0; e < 4; ++e)                                                                                                    \
+      _Pragma("unroll")                                                                                                            \
+      for (int b = 0; b < 2; ++b) {                                                                                                \
+        const int bit2 = ((P >> 2) & 1) ^ (((P & 3) + e) >> 2) ^ b;                                                                \
+        baseA[e][b] = (unsigned)((P << 6) | ((g << 4) ^ (bit2 << 5)));                                                             \
+      }                                                                                                                            \
+    addrB = (unsigned)(L::BBASE + (wn * 64 + pr) * 64 + ((g ^ sw4((pr >> 2) & 3)) << 4));                                          \
+  }                                                                                                                                \
+  auto flip_base = [&](int d) {                                                                                                    \
+    _Pragma("unroll")                                                                                                              \
+    for (int e = 0; e < 4; ++e) { baseA[e][0] += d; baseA[e][1] += d; }                                                            \
   };
-  // hi / lo split of third k and its two 16-byte LDS writes (where the plane DMA would have put them); zero padding stays zero
-  auto store_slab_f = [&](u32x4 (&r)[2], int buf, int k) {
-    u32x4 hi4, lo4;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      u32x2 hi, lo;
-      split4(r[h], hi, lo);
-      hi4[2 * h] = hi[0]; hi4[2 * h + 1] = hi[1];
-      lo4[2 * h] = lo[0]; lo4[2 * h + 1] = lo[1];
-    }
-    if (slab_off[k] == oobA) { hi4 = u32x4{0u, 0u, 0u, 0u}; lo4 = hi4; }
-    unsigned char* dst = smem + buf * SLAB + slab_piece[k] * 1024 + lane * 16;
-    *(u32x4*)dst = hi4;
-    *(u32x4*)(dst + PLANE) = lo4;
-  };
+// GN: a tile's chunk 0 through the register path before the K loop, from its three thirds in pr[3][2] (the compiler waits for the six loads)
+#define SLAB_CHUNK0_F(pr, chunk)                                                                                                   \
+  _Pragma("unroll")                                                                                                                \
+  for (int h = 0; h < 2; ++h) {                                                                                                    \
+    load_gss(chunk, h);                                                                                                            \
+    _Pragma("unroll")                                                                                                              \
+    for (int k = 0; k < 3; ++k)                                                                                                    \
+      _Pragma("unroll")                                                                                                            \
+      for (int e = 0; e < 4; ++e) xform_elem(pr[k], h * 4 + e);                                                                    \
+  }                                                                                                                                \
+  _Pragma("unroll")                                                                                                                \
+  for (int k = 0; k < 3; ++k) store_slab_f(pr[k], 0, k, chunk);
 
-  // third `k` of the slab of channel chunk `chunk` into buffer `buf`
-  auto issue_slab = [&](int buf, int k, int chunk) {
-    const unsigned vo = chunk * 32 < Cin ? slab_off[k] : oobA;
-    const int soff = chunk * 64;
-    unsigned char* dst = smem + buf * SLAB + slab_piece[k] * 1024;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xh, (lds_void_t*)dst, 16, (int)vo, soff, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xl, (lds_void_t*)(dst + PLANE), 16, (int)vo, soff, 0, 0);
-  };
-
-  // ---- weight DMA (as in cdma): waves 0-3 the hi image, 4-7 the lo image, two 16-row pieces each per K-tile ----
-  const int wimg = wave >> 2;
-  const unsigned bytesB = (unsigned)((long)p.N * p.K * 2);
-  const rsrc_t rs_w = make_rsrc(wimg ? p.wl : p.wh, bytesB);
-  const unsigned oobB = (bytesB + 15u) & ~15u;
-  unsigned voffB[2];
-  {
-    const int srcchunk = (lane & 3) ^ sw4((lane >> 4) & 3);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + ((wave & 3) * 2 + j) * 16 + (lane >> 2);
-      voffB[j] = n < p.N ? (unsigned)(((long)n * p.K + srcchunk * 8) * 2) : oobB;
-    }
-  }
-  // weights of (chunk, tap) into ring stage `stage`: k index = tap * Cin + chunk * 32
-  auto issue_b = [&](int stage, int chunk, int tap) {
-    const bool ok = chunk * 32 < Cin;
-    const int soff = (tap * Cin + chunk * 32) * 2;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_t*)(smem + B_BASE + stage * BSTAGE + wimg * 8192 + ((wave & 3) * 2 + j) * 1024),
-                                               16, (int)(ok ? voffB[j] : oobB), soff, 0, 0);
-  };
-
-  // ---- fragment read addresses ----
-  unsigned baseA[4][2], addrB;
-  {
-    const int pr = lane & 15, g = lane >> 4, P = 72 * wm + pr;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int bit2 = ((P >> 2) & 1) ^ (((P & 3) + e) >> 2) ^ b;
-        baseA[e][b] = (unsigned)((P << 6) | ((g << 4) ^ (bit2 << 5)));
-      }
-    addrB = (unsigned)(B_BASE + (wn * 64 + pr) * 64 + ((g ^ sw4((pr >> 2) & 3)) << 4));
-  }
-
-  auto flip_base = [&](int d) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { baseA[e][0] += d; baseA[e][1] += d; }
-  };
-
-  f32x4 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  Frag16 f0, f1;
-
-  // read #Q (0..15) of tap TAP (0..8) from the slab buffer baseA points into / weight stage ST into F.   A reads: c' = (i + ky) * 18 + kx.
+// ---- the K loop's slots.  Besides SLAB_BODY's names they use acc, xr, gn (the next tile's geometry), chunk0 and `first` (this is the
+//      tile's first pass through the loop body AND its operands were waited for before the loop: the walk; the launch-per-tile kernel's
+//      prologue leaves its weight DMAs in flight: first = false) ----
+// read #Q (0..15) of tap TAP (0..8) from the slab buffer baseA points into / weight stage ST into F.   A reads: c' = (i + ky) * 18 + kx.
 #define SLAB_CP(TAP, I) (((I) + (TAP) / 3) * 18 + (TAP) % 3)
-#define SLAB_READ(F, ST, TAP, Q)                                                                                             \
+#define SLAB_READ(F, ST, TAP, Q)                                                                                                  \
   {                                                                                                                               \
     constexpr int q_ = (Q) & 3;                                                                                                   \
     constexpr int cp_ = SLAB_CP(TAP, q_);                                                                                         \
     if constexpr ((Q) < 4) lds_read128<cp_ * 64>(F.ah[q_], baseA[cp_ & 3][(cp_ >> 2) & 1]);                                       \
     else if constexpr ((Q) < 8) lds_read128<PLANE + cp_ * 64>(F.al[q_], baseA[cp_ & 3][(cp_ >> 2) & 1]);                          \
-    else if constexpr ((Q) < 12) lds_read128<(ST) * BSTAGE + q_ * 1024>(F.bh[q_], addrB);                                         \
-    else lds_read128<(ST) * BSTAGE + 8192 + q_ * 1024>(F.bl[q_], addrB);                                                          \
+    else if constexpr ((Q) < 12) lds_read128<L::stage_off(ST) + q_ * 1024>(F.bh[q_], addrB);                                      \
+    else lds_read128<L::stage_off(ST) + 8192 + q_ * 1024>(F.bl[q_], addrB);                                                       \
   }
+// all 16 fragments of a tile's tap 0 (before the loop, and after the walk's epilogue)
+#define SLAB_READ_TAP0(F)                                                                              \
+  SLAB_READ(F, 0, 0, 0) SLAB_READ(F, 0, 0, 1) SLAB_READ(F, 0, 0, 2) SLAB_READ(F, 0, 0, 3)              \
+  SLAB_READ(F, 0, 0, 4) SLAB_READ(F, 0, 0, 5) SLAB_READ(F, 0, 0, 6) SLAB_READ(F, 0, 0, 7)              \
+  SLAB_READ(F, 0, 0, 8) SLAB_READ(F, 0, 0, 9) SLAB_READ(F, 0, 0, 10) SLAB_READ(F, 0, 0, 11)            \
+  SLAB_READ(F, 0, 0, 12) SLAB_READ(F, 0, 0, 13) SLAB_READ(F, 0, 0, 14) SLAB_READ(F, 0, 0, 15)
 #if defined(CDMA_TWO_PRODUCTS)   // accuracy experiment (scripts/exp/conv_two_products.sh): drop one cross term of the bf16x3 product
 #define SLAB_PAIR(F, Q)                                                                                                        \
   {                                                                                                                            \
@@ -514,12 +567,14 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
 #endif
   // slot Q of tap T (0..17 inside the two-chunk loop body; chunk parity CP = T / 9, tap TAP = T % 9) computing from CUR while
   // prefetching the fragments of tap T+1 into NXT.  DMA: slot 0/1 = a third of the NEXT chunk's slab (taps 0..2 only), slot 2 =
-  // the weights of tap T+3.
+  // the weights of tap T+3.  The walk also fetches the next tile's scale / shift table, at (tap 3, slot 5) of a tile's first chunk
+  // pair (landed and barrier-published long before tap 11 first reads it).
 #ifndef CDMA_ABLATE_NO_DMA
 #define SLAB_ISSUE(T, Q)                                                                          \
   if constexpr (!GN && (Q) == 0 && ((T) % 9) < 3) issue_slab(1 - (T) / 9, (T) % 9, chunk0 + (T) / 9 + 1);  \
   if constexpr (GN && (Q) == 0 && ((T) % 9) == 0) issue_slab_f(xr, 0, chunk0 + (T) / 9 + 1);           \
   if constexpr (GN && (Q) == 12 && (((T) % 9) == 2 || ((T) % 9) == 4)) issue_slab_f(xr, ((T) % 9) / 2, chunk0 + (T) / 9 + 1);  \
+  if constexpr (GN && (T) == 3 && (Q) == 5) { if (first) issue_gss(gss_nxt, gn.img); }       \
   if constexpr ((Q) == 2) issue_b(((T) + 3) % 3, chunk0 + ((T) + 3) / 9, ((T) + 3) % 9);
 // GN: one register set: third 0 is issued at the top of tap 0, thirds 1 / 2 at slot 12 of taps 2 / 4 (once the previous third has
 // left the registers); third k is transformed in tap 2k + 2: scale / shift halves at slots 1 / 6, one element per slot 2..5 and
@@ -527,11 +582,11 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
 #define SLAB_XF(T, Q)                                                                             \
   if constexpr (GN && ((T) % 9) >= 2 && ((T) % 9) <= 6 && ((T) % 9) % 2 == 0) {                    \
     constexpr int k_ = ((T) % 9) / 2 - 1;                                                         \
-    if constexpr ((Q) == 1) load_gss(chunk0 + (T) / 9 + 1, 0);                                    \
-    if constexpr ((Q) >= 2 && (Q) < 6) xform_elem(xr, (Q) - 2);                                   \
-    if constexpr ((Q) == 6) load_gss(chunk0 + (T) / 9 + 1, 1);                                    \
-    if constexpr ((Q) >= 7 && (Q) < 11) xform_elem(xr, (Q) - 3);                                  \
-    if constexpr ((Q) == 11) store_slab_f(xr, 1 - (T) / 9, k_);                                   \
+    if constexpr ((Q) == 1) load_gss(chunk0 + (T) / 9 + 1, 0); \
+    if constexpr ((Q) >= 2 && (Q) < 6) xform_elem(xr, (Q) - 2);                         \
+    if constexpr ((Q) == 6) load_gss(chunk0 + (T) / 9 + 1, 1); \
+    if constexpr ((Q) >= 7 && (Q) < 11) xform_elem(xr, (Q) - 3);                        \
+    if constexpr ((Q) == 11) store_slab_f(xr, 1 - (T) / 9, k_, chunk0 + (T) / 9 + 1);  \
   }
 #else
 #define SLAB_ISSUE(T, Q)
@@ -548,72 +603,137 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
   // them are outstanding: 2 (weights of T+2) + 2 more when tap T-1 also issued a slab third (T-1 in 0..2 of its chunk).
   // GN: thirds are issued at (tap 0, slot 0) and (taps 2 / 4, slot 12), i.e. after the weights of tap T+1 when T-1 is 0, 2 or 4 or
   // T-2 is 2 or 4: two more at the top of taps 1, 3, 4, 5 and 6; the third itself is waited for by the compiler where the
-  // transform first reads it (a tap and a half after its issue)
+  // transform first reads it (a tap and a half after its issue).
+  // `first` (the walk): taps 0 and 1 of a tile's first pass need no vector-memory wait at all, their operands were waited for in
+  // the previous tile / the epilogue; the extra scale / shift DMA of that pass makes the waits of its taps 4 and 5 merely stricter.
 #ifndef CDMA_ABLATE_NO_DMA
-#define SLAB_WAIT(T)                                                                     \
-  if constexpr (GN ? (((T) % 9) == 1 || (((T) % 9) >= 3 && ((T) % 9) <= 6)) : (((T) % 9) >= 1 && ((T) % 9) <= 3))  \
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                          \
+#define SLAB_WAIT(T)                                                                                                        \
+  if constexpr ((T) < 2) {                                                                                                  \
+    if (first) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                          \
+    else if constexpr ((T) == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                               \
+    else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                                                        \
+  } else if constexpr (GN ? (((T) % 9) == 1 || (((T) % 9) >= 3 && ((T) % 9) <= 6)) : (((T) % 9) >= 1 && ((T) % 9) <= 3))   \
+    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                                                             \
   else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
 #else
 #define SLAB_WAIT(T) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
   // the base registers point into the slab buffer the NEXT tap's fragments come from: flipped when that tap starts a new chunk
-  // (ds_read immediates are 16 bits, the two buffers span 84 KiB)
+  // (ds_read immediates are 16 bits, the two buffers span 84 KiB and more)
 #define SLAB_TAP(CUR, NXT, T)                                                                         \
   SLAB_WAIT(T)                                                                                        \
   __builtin_amdgcn_s_barrier();                                                                       \
-  if constexpr ((T) == 8) flip_base(SLAB);                                                            \
-  if constexpr ((T) == 17) flip_base(-SLAB);                                                          \
+  if constexpr ((T) == 8) flip_base(L::BUF1);                                                  \
+  if constexpr ((T) == 17) flip_base(-L::BUF1);                                                \
   __builtin_amdgcn_sched_barrier(0);                                                                  \
   SLAB_SLOT(CUR, NXT, T, 0) SLAB_SLOT(CUR, NXT, T, 1) SLAB_SLOT(CUR, NXT, T, 2) SLAB_SLOT(CUR, NXT, T, 3)     \
   SLAB_SLOT(CUR, NXT, T, 4) SLAB_SLOT(CUR, NXT, T, 5) SLAB_SLOT(CUR, NXT, T, 6) SLAB_SLOT(CUR, NXT, T, 7)     \
   SLAB_SLOT(CUR, NXT, T, 8) SLAB_SLOT(CUR, NXT, T, 9) SLAB_SLOT(CUR, NXT, T, 10) SLAB_SLOT(CUR, NXT, T, 11)   \
   SLAB_SLOT(CUR, NXT, T, 12) SLAB_SLOT(CUR, NXT, T, 13) SLAB_SLOT(CUR, NXT, T, 14) SLAB_SLOT(CUR, NXT, T, 15)
+// two channel chunks (18 taps): slab buffer = chunk parity, weight stage = tap % 3, registers ping-pong
+#define SLAB_TWO_CHUNKS(F0, F1)                                                                                                       \
+  SLAB_TAP(F0, F1, 0) SLAB_TAP(F1, F0, 1) SLAB_TAP(F0, F1, 2) SLAB_TAP(F1, F0, 3) SLAB_TAP(F0, F1, 4) SLAB_TAP(F1, F0, 5)             \
+  SLAB_TAP(F0, F1, 6) SLAB_TAP(F1, F0, 7) SLAB_TAP(F0, F1, 8) SLAB_TAP(F1, F0, 9) SLAB_TAP(F0, F1, 10) SLAB_TAP(F1, F0, 11)           \
+  SLAB_TAP(F0, F1, 12) SLAB_TAP(F1, F0, 13) SLAB_TAP(F0, F1, 14) SLAB_TAP(F1, F0, 15) SLAB_TAP(F0, F1, 16) SLAB_TAP(F1, F0, 17)
+
+// ---- shared by the two epilogues, over the staged f32 tile at `staged` (they use gs / gq, col, qx, qy0, wave, n0) ----
+#define SLAB_STAT4(w)                                                                                                              \
+  if (p.gn_partial) {                                                                                                              \
+    _Pragma("unroll")                                                                                                              \
+    for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }                                         \
+  }
+// w = the 2 x 2 average of the window at patch rows 2 * qy0 + 4 * k (+ 1), pixels 2 * qx (+ 1), four channels at `col`; ADD_RESIDUAL:
+// what is added to quad v[d] of the window first.  Every window lies inside one 16 x 16 patch; the full-resolution values and the order
+// of the three adds are those of the un-pooled epilogue followed by avgpool_stats_kernel (vqgan.hip): same bits
+#define SLAB_POOLED_WINDOW(w, staged, k, ADD_RESIDUAL)                                                                             \
+  f32x4 v[4];                                                                                                                      \
+  _Pragma("unroll")                                                                                                                \
+  for (int d = 0; d < 4; ++d) {                                                                                                    \
+    v[d] = *(const f32x4*)(staged + ((2 * qy0 + 4 * k + (d >> 1)) * 16 + 2 * qx + (d & 1)) * CST + col * 4);                       \
+    ADD_RESIDUAL                                                                                                                   \
+  }                                                                                                                                \
+  const f32x4 w = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;   /* avgpool_stats_kernel's order */
+// GroupNorm partials of the tile: thread TX owns column chunk TX & 31 in every store iteration of the epilogues -> fold the 16 threads per
+// chunk (through the staged bytes, [8 waves][32 chunks][2]), then the chunks of each group, in a fixed order, into slot SLOT (the tile's
+// image * patches per image + patch) of the partial slab.  GROUP: the group of channel nn
+#define SLAB_FOLD_PARTIALS(staged, BARRIER, LANE, TX, SLOT, GROUP)                                                                 \
+  if (p.gn_partial) {                                                                                                              \
+    gs += __shfl_xor(gs, 32, 64);                                                                                                  \
+    gq += __shfl_xor(gq, 32, 64);                                                                                                  \
+    BARRIER;                                                                                                                       \
+    double* red = (double*)(staged);                                                                                               \
+    if (LANE < 32) { red[(wave * 32 + LANE) * 2] = gs; red[(wave * 32 + LANE) * 2 + 1] = gq; }                                     \
+    BARRIER;                                                                                                                       \
+    if (TX < 32) {                                                                                                                 \
+      double cs = 0.0, cq = 0.0;                                                                                                   \
+      _Pragma("unroll")                                                                                                            \
+      for (int w8 = 0; w8 < 8; ++w8) { cs += red[(w8 * 32 + TX) * 2]; cq += red[(w8 * 32 + TX) * 2 + 1]; }                         \
+      const int cpc = p.gn_cpg >> 2;   /* column chunks per group (1, 2, 4, 8 ...) */                                              \
+      for (int o = 1; o < cpc; o <<= 1) { cs += __shfl_xor(cs, o, 64); cq += __shfl_xor(cq, o, 64); }                              \
+      const int nn = n0 + (int)TX * 4;                                                                                             \
+      if ((TX & (cpc - 1)) == 0 && nn < p.N) {                                                                                     \
+        double* o2 = p.gn_partial + ((SLOT) * p.gn_groups + GROUP) * 2;                                                            \
+        o2[0] = cs; o2[1] = cq;                                                                                                    \
+      }                                                                                                                            \
+    }                                                                                                                              \
+  }
+
+// Launch-per-tile form.  GN = true: the GroupNorm register path above.
+// POOL = true: the epilogue stores the 2 x 2 average of the tile (F.avg_pool2d(2, 2) of the output, DownsamplingBlock with
+// resample_with_conv = False) instead of the tile: out is [B, H/2, W/2, N] and the GroupNorm partials are those of the POOLED values:
+// a quarter of the stores and no second pass.
+template <bool GN, bool POOL = false>
+__global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using L = LaunchMap;
+  CDMA_TS(0)
+  SLAB_SETUP
+  const Geo g = geo_of(blockIdx.x), gn = g;
+  const int img = g.img, n0 = g.n0, y0 = g.y0, x0 = g.x0;
+  // The K loop is the walk's with no first pass and a next tile that lies out of range: behind the last chunk, zero fill.
+  constexpr bool first = false;
+  unsigned slab_off[3], voffB[2];
+  const unsigned slab_off_n[3] = {oobA, oobA, oobA}, voffB_n[2] = {oobB, oobB};
+  // GN: the image's scale / shift behind the tile's LDS map, [2][Cin] f32
+  float* const gss_cur = (float*)(smem + LDS_BYTES);
+  float* const gss_nxt = gss_cur;
+  u32x4 xr[2];                  // GN: the slab third in flight / being transformed (one at a time inside the K loop)
+  float scv[4], shv[4];
+  if constexpr (GN) {
+    for (int c = threadIdx.x; c < Cin; c += NT) { gss_cur[c] = p.gsc[(long)img * Cin + c]; gss_cur[Cin + c] = p.gsh[(long)img * Cin + c]; }
+    __syncthreads();
+  }
+  SLAB_BODY
+  offsets_of(g, true, slab_off, voffB, lane);
+
+  f32x4 acc[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  Frag16 f0, f1;
 
   // prologue: slab of chunk 0 and the weights of taps 0, 1, 2 in flight; tap 0's fragments into f0
   int chunk0 = 0;
-  u32x4 pr[GN ? 3 : 1][2];      // (prologue only: the fragment registers are still free)
-  if constexpr (GN) { issue_slab_f(pr[0], 0, 0); issue_slab_f(pr[GN ? 1 : 0], 1, 0); issue_slab_f(pr[GN ? 2 : 0], 2, 0); }
-  else { issue_slab(0, 0, 0); issue_slab(0, 1, 0); issue_slab(0, 2, 0); }
-  issue_b(0, 0, 0); issue_b(1, 0, 1); issue_b(2, 0, 2);
-  CDMA_TS(1)
-  if constexpr (GN) {   // chunk 0's slab through the register path before the loop (the compiler waits for its six loads)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      load_gss(0, h);
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xform_elem(pr[GN ? k : 0], h * 4 + e);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) store_slab_f(pr[GN ? k : 0], 0, k);
+  if constexpr (GN) {   // chunk 0's slab through the register path (the fragment registers are still free)
+    u32x4 pr[3][2];
+    issue_slab_f(pr[0], 0, 0); issue_slab_f(pr[1], 1, 0); issue_slab_f(pr[2], 2, 0);
+    issue_b(0, 0, 0); issue_b(1, 0, 1); issue_b(2, 0, 2);
+    CDMA_TS(1)
+    SLAB_CHUNK0_F(pr, 0)
+  } else {
+    issue_slab(0, 0, 0); issue_slab(0, 1, 0); issue_slab(0, 2, 0);
+    issue_b(0, 0, 0); issue_b(1, 0, 1); issue_b(2, 0, 2);
+    CDMA_TS(1)
   }
   asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   CDMA_TS(2)
-  SLAB_READ(f0, 0, 0, 0) SLAB_READ(f0, 0, 0, 1) SLAB_READ(f0, 0, 0, 2) SLAB_READ(f0, 0, 0, 3)
-  SLAB_READ(f0, 0, 0, 4) SLAB_READ(f0, 0, 0, 5) SLAB_READ(f0, 0, 0, 6) SLAB_READ(f0, 0, 0, 7)
-  SLAB_READ(f0, 0, 0, 8) SLAB_READ(f0, 0, 0, 9) SLAB_READ(f0, 0, 0, 10) SLAB_READ(f0, 0, 0, 11)
-  SLAB_READ(f0, 0, 0, 12) SLAB_READ(f0, 0, 0, 13) SLAB_READ(f0, 0, 0, 14) SLAB_READ(f0, 0, 0, 15)
+  SLAB_READ_TAP0(f0)
   __builtin_amdgcn_sched_barrier(0);
 
-  // two channel chunks (18 taps) per iteration: slab buffer = chunk parity, weight stage = tap % 3, registers ping-pong
-  const int nchunks = Cin >> 5;
-  for (; chunk0 < nchunks; chunk0 += 2) {
-    SLAB_TAP(f0, f1, 0) SLAB_TAP(f1, f0, 1) SLAB_TAP(f0, f1, 2) SLAB_TAP(f1, f0, 3) SLAB_TAP(f0, f1, 4) SLAB_TAP(f1, f0, 5)
-    SLAB_TAP(f0, f1, 6) SLAB_TAP(f1, f0, 7) SLAB_TAP(f0, f1, 8) SLAB_TAP(f1, f0, 9) SLAB_TAP(f0, f1, 10) SLAB_TAP(f1, f0, 11)
-    SLAB_TAP(f0, f1, 12) SLAB_TAP(f1, f0, 13) SLAB_TAP(f0, f1, 14) SLAB_TAP(f1, f0, 15) SLAB_TAP(f0, f1, 16) SLAB_TAP(f1, f0, 17)
-  }
-#undef SLAB_TAP
-#undef SLAB_WAIT
-#undef SLAB_SLOT
-#undef SLAB_XF
-#undef SLAB_ISSUE
-#undef SLAB_PAIR
-#undef SLAB_READ
-#undef SLAB_CP
+  for (; chunk0 < nchunks; chunk0 += 2) { SLAB_TWO_CHUNKS(f0, f1) }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // trailing (zero) DMAs and fragment reads done before LDS is reused
   __builtin_amdgcn_sched_barrier(0);
   CDMA_TS(3)
@@ -660,18 +780,9 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        f32x4 v[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          v[d] = *(const f32x4*)(smem + ((2 * qy0 + 4 * k + (d >> 1)) * 16 + 2 * qx + (d & 1)) * CST + col * 4);
-          if (p.residual) v[d] += rv[4 * k + d];
-        }
-        const f32x4 w = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;   // avgpool_stats_kernel's order
+        SLAB_POOLED_WINDOW(w, smem, k, if (p.residual) v[d] += rv[4 * k + d];)
         *(f32x4*)(p.out + (pixo + (long)(2 * k) * Wo) * p.N + n) = w;
-        if (p.gn_partial) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
-        }
+        SLAB_STAT4(w)
       }
     }
   } else if (n < p.N) {
@@ -689,32 +800,10 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
 #else
       if (w[0] == 123.456f) p.out[0] = w[1];   // keeps the staged read alive, stores nothing
 #endif
-      if (p.gn_partial) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
-      }
+      SLAB_STAT4(w)
     }
   }
-  if (p.gn_partial) {
-    gs += __shfl_xor(gs, 32, 64);
-    gq += __shfl_xor(gq, 32, 64);
-    __syncthreads();
-    double* red = (double*)smem;   // [8 waves][32 chunks][2]
-    if (lane < 32) { red[(wave * 32 + lane) * 2] = gs; red[(wave * 32 + lane) * 2 + 1] = gq; }
-    __syncthreads();
-    if (threadIdx.x < 32) {
-      double cs = 0.0, cq = 0.0;
-#pragma unroll
-      for (int w8 = 0; w8 < 8; ++w8) { cs += red[(w8 * 32 + threadIdx.x) * 2]; cq += red[(w8 * 32 + threadIdx.x) * 2 + 1]; }
-      const int cpc = p.gn_cpg >> 2;
-      for (int o = 1; o < cpc; o <<= 1) { cs += __shfl_xor(cs, o, 64); cq += __shfl_xor(cq, o, 64); }
-      const int nn = n0 + (int)threadIdx.x * 4;
-      if ((threadIdx.x & (cpc - 1)) == 0 && nn < p.N) {
-        double* o2 = p.gn_partial + (((long)img * tpi + prem) * p.gn_groups + nn / p.gn_cpg) * 2;   // chunk = patch index in the image
-        o2[0] = cs; o2[1] = cq;
-      }
-    }
-  }
+  SLAB_FOLD_PARTIALS(smem, __syncthreads(), lane, threadIdx.x, (long)img * tpi + g.prem, nn / p.gn_cpg)
   CDMA_TS(5)
 }
 
@@ -732,162 +821,30 @@ __global__ __launch_bounds__(512, 2) void conv_slab_kernel(Params p) {
 //   the next tile starts; taps 0 and 1 of a tile's first iteration need no vector-memory wait at all (their operands were
 //   waited for in the previous tile / the epilogue), from tap 2 on the counted waits of the K loop apply unchanged (loads
 //   and stores retire in order within their kind; a counted wait that still sees stores is merely conservative).
-constexpr int P_BUF1 = 92160, P_BBASE = 43008, P_STAGING = P_BUF1, P_HALF_ROWS = 128;
-constexpr int P_LDS_BYTES = P_STAGING + P_HALF_ROWS * CST;   // 159744
-// GN = true: two [2][Cin] f32 scale / shift tables behind the tile's map (this tile's image, the next tile's image): Cin <= 256
-constexpr int P_GSS = P_LDS_BYTES, P_GSS_MAX_CIN = 256, P_LDS_BYTES_GN = P_LDS_BYTES + 2 * 2 * P_GSS_MAX_CIN * 4;   // 163840 = all of it
-__host__ __device__ constexpr int p_stage_off(int st) { return st == 0 ? 32768 : (st - 1) * 16384; }   // relative to P_BBASE
-static_assert(P_BBASE + 3 * BSTAGE == P_BUF1 && P_BUF1 + SLAB <= P_LDS_BYTES && P_LDS_BYTES_GN <= 163840, "LDS map");
-
+//
 // GN = true is the persistent form of conv_slab_kernel<true> (round 6): the f32 activation goes through registers, GroupNorm affine +
-// SiLU + hi / lo split are applied on the way into the slab buffer - same slots, same arithmetic, same bits as the launch-per-tile
-// kernel - and the look-ahead across the tile boundary carries the NEXT tile's first chunk through that same register path with the
-// next tile's image's scale / shift (second table, fetched by one 256-byte LDS-DMA per wave early in the tile).
+// SiLU + hi / lo split are applied on the way into the slab buffer - the slots are those of SLAB_ISSUE / SLAB_XF above and the
+// arithmetic that of xform_elem / store_slab_f, the very code the launch-per-tile kernel expands - and the look-ahead across the tile
+// boundary carries the NEXT tile's first chunk through that same register path with the next tile's image's scale / shift (second
+// table, fetched by one 256-byte LDS-DMA per wave early in the tile).
 // POOL = true: the pooled epilogue of conv_slab_kernel<true, true> (2 x 2 average of the tile, GroupNorm partials of the pooled values):
 // each staged half of the tile (eight patch rows) holds whole windows, so a pass stores its four pooled rows.
 template <bool GN, bool POOL = false>
 __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int H = p.H, W = p.W, Cin = p.Cin;
-  const int tpr = W >> 4, tpi = (H >> 4) * tpr;
-  const int ntm = p.M >> 8, ntn = (p.N + BN - 1) / BN, ntiles = ntm * ntn;
-  const int bq = ntiles >> 3, br = ntiles & 7;
+  using L = WalkMap;
+  SLAB_SETUP
   const int nblocks = gridDim.x;
-
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-
-  constexpr int XE = GN ? 4 : 2;             // bytes per activation element in global memory
-  const unsigned bytesA = (unsigned)((long)p.M * Cin * XE);
-  const rsrc_t rs_xh = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xh, bytesA), rs_xl = make_rsrc(GN ? (const void*)p.xf : (const void*)p.xl, bytesA);
-  const unsigned oobA = (bytesA + 15u) & ~15u;
-  const int wimg = wave >> 2;
-  const unsigned bytesB = (unsigned)((long)p.N * p.K * 2);
-  const rsrc_t rs_w = make_rsrc(wimg ? p.wl : p.wh, bytesB);
-  const unsigned oobB = (bytesB + 15u) & ~15u;
-  const int nchunks = Cin >> 5;
   const unsigned bytesO = (unsigned)((long)p.M * p.N * 4);   // < 4 GiB (host check)
   const unsigned bytesOut = POOL ? bytesO >> 2 : bytesO;     // POOL: out is [B, H/2, W/2, N]; the residual stays full-resolution
   const rsrc_t rs_out = make_rsrc(p.out, bytesOut);
   const rsrc_t rs_res = make_rsrc(p.residual ? (const void*)p.residual : (const void*)p.out, p.residual ? bytesO : bytesOut);
-
-  int slab_piece[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { int piece = wave + 8 * k; if (piece > 20) piece -= 8; slab_piece[k] = piece; }
-  const int srcchunkA = (lane & 3) ^ (((lane >> 4) & 1) << 1);
-
-  // geometry of virtual block v (the XCD-aware walk of the launch-per-tile kernels: v -> tile)
-  struct Geo { int img, prem, y0, x0, n0; };
-  auto geo_of = [&](int v) {
-    const int xcd = v & 7, bi = v >> 3;
-    const int tid_ = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + bi;
-    const int mt = tid_ / ntn;
-    Geo g;
-    g.n0 = (tid_ - mt * ntn) * BN;
-    g.img = mt / tpi; g.prem = mt - g.img * tpi;
-    const int ty = g.prem / tpr, tx = g.prem - ty * tpr;
-    g.y0 = ty << 4; g.x0 = tx << 4;
-    return g;
-  };
-  // (`ln` = the lane id behind an empty asm: per-lane geometry is recomputed per tile instead of living in registers across the K loop)
-  auto offsets_of = [&](const Geo& g, bool valid, unsigned (&so)[3], unsigned (&vb)[2], int ln) {
-    const int srcchunkA = (ln & 3) ^ (((ln >> 4) & 1) << 1);
-    const int srcchunkB = (ln & 3) ^ sw4((ln >> 4) & 3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int r = slab_piece[k] * 16 + (ln >> 2), sy = r / 18, sx = r - sy * 18;
-      const int y = g.y0 - 1 + sy, x = g.x0 - 1 + sx;
-      const bool ok = valid && r < 324 && y >= 0 && y < H && x >= 0 && x < W;
-      so[k] = ok ? (unsigned)(((((long)g.img * H + y) * W + x) * Cin + srcchunkA * 8) * XE) : oobA;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = g.n0 + ((wave & 3) * 2 + j) * 16 + (ln >> 2);
-      vb[j] = (valid && n < p.N) ? (unsigned)(((long)n * p.K + srcchunkB * 8) * 2) : oobB;
-    }
-  };
-
   unsigned slab_off[3], voffB[2], slab_off_n[3], voffB_n[2];
-  // slab third k of chunk `chunk` of the current tile, or (chunk == nchunks) of chunk 0 of the next tile
-  auto issue_slab = [&](int buf, int k, int chunk) {
-    const bool cur = chunk < nchunks;
-    const unsigned vo = cur ? slab_off[k] : slab_off_n[k];
-    const int soff = cur ? chunk * 64 : 0;
-    unsigned char* dst = smem + (buf ? P_BUF1 : 0) + slab_piece[k] * 1024;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xh, (lds_void_t*)dst, 16, (int)vo, soff, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_xl, (lds_void_t*)(dst + PLANE), 16, (int)vo, soff, 0, 0);
-  };
-  auto issue_b = [&](int stage_off, int chunk, int tap) {
-    const bool cur = chunk < nchunks;
-    const int soff = (tap * Cin + (cur ? chunk * 32 : 0)) * 2;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void_t*)(smem + P_BBASE + stage_off + wimg * 8192 + ((wave & 3) * 2 + j) * 1024),
-                                               16, (int)(cur ? voffB[j] : voffB_n[j]), soff, 0, 0);
-  };
-
-  // ---- GN: the register path of the slab (conv_slab_kernel<true>), with the tile-boundary case ----
-  float* gss_cur = (float*)(smem + P_GSS);                       // [2][Cin] of the current tile's image
+  float* gss_cur = (float*)(smem + P_GSS);                       // GN: [2][Cin] of the current tile's image
   float* gss_nxt = gss_cur + 2 * P_GSS_MAX_CIN;                  // ... of the next tile's image
   u32x4 xr[2];
   float scv[4], shv[4];
-  auto issue_slab_f = [&](u32x4 (&r)[2], int k, int chunk) {
-    const bool cur = chunk < nchunks;
-    const unsigned vo = cur ? slab_off[k] : slab_off_n[k];
-    const unsigned soff = cur ? (unsigned)(chunk * 128) : 0u;
-    r[0] = buf_load16(rs_xh, vo, soff);
-    r[1] = buf_load16(rs_xh, vo + 16u, soff);
-  };
-  auto load_gss = [&](int chunk, int h) {
-    const float* q = (chunk < nchunks ? gss_cur + chunk * 32 : gss_nxt) + srcchunkA * 8 + h * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { scv[j] = q[j]; shv[j] = q[Cin + j]; }
-  };
-  auto xform_elem = [&](u32x4 (&r)[2], int e) {
-    float t = fmaf(__uint_as_float(r[e >> 2][e & 3]), scv[e & 3], shv[e & 3]);
-    t = gn_silu(t);
-    asm volatile("" : "+v"(t));   // the ROUNDED product is what gets split: no contraction of (x * r) - hi into one fma
-    r[e >> 2][e & 3] = __float_as_uint(t);
-  };
-  auto store_slab_f = [&](u32x4 (&r)[2], int buf, int k, int chunk) {
-    u32x4 hi4, lo4;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      u32x2 hi, lo;
-      split4(r[h], hi, lo);
-      hi4[2 * h] = hi[0]; hi4[2 * h + 1] = hi[1];
-      lo4[2 * h] = lo[0]; lo4[2 * h + 1] = lo[1];
-    }
-    if ((chunk < nchunks ? slab_off[k] : slab_off_n[k]) == oobA) { hi4 = u32x4{0u, 0u, 0u, 0u}; lo4 = hi4; }
-    unsigned char* dst = smem + (buf ? P_BUF1 : 0) + slab_piece[k] * 1024 + lane * 16;
-    *(u32x4*)dst = hi4;
-    *(u32x4*)(dst + PLANE) = lo4;
-  };
-  // scale / shift of image `img` into table `dst`: 2 * Cin / 64 pieces of 64 floats, one LDS-DMA per wave (the pieces repeat over the waves)
-  auto issue_gss = [&](float* dst, int img) {
-    const int npc = Cin >> 6, piece = wave % (2 * npc), isshift = piece >= npc ? 1 : 0, pc = piece - isshift * npc;
-    const int batch = p.M / (H * W);
-    const rsrc_t rs = make_rsrc(isshift ? p.gsh : p.gsc, (unsigned)((long)batch * Cin * 4));
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(dst + isshift * Cin + pc * 64), 4, (int)((unsigned)((long)img * Cin + pc * 64 + lane) * 4u), 0, 0, 0);
-  };
-
-  unsigned baseA[4][2], addrB;
-  {
-    const int pr = lane & 15, g = lane >> 4, P = 72 * wm + pr;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const int bit2 = ((P >> 2) & 1) ^ (((P & 3) + e) >> 2) ^ b;
-        baseA[e][b] = (unsigned)((P << 6) | ((g << 4) ^ (bit2 << 5)));
-      }
-    addrB = (unsigned)(P_BBASE + (wn * 64 + pr) * 64 + ((g ^ sw4((pr >> 2) & 3)) << 4));
-  }
-  auto flip_base = [&](int d) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { baseA[e][0] += d; baseA[e][1] += d; }
-  };
-
+  SLAB_BODY
   // LDS-only barrier: a full block barrier is also a fence for global memory, i.e. an `s_waitcnt vmcnt(0)` on the output
   // stores still in flight - exactly the wait the persistent walk exists to avoid
   auto lds_barrier = [&]() {
@@ -899,70 +856,7 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
   f32x4 acc[MI][NI];
   Frag16 f0, f1;
 
-#define SLAB_CP(TAP, I) (((I) + (TAP) / 3) * 18 + (TAP) % 3)
-#define SLAB_READ(F, ST, TAP, Q)                                                                                                  \
-  {                                                                                                                               \
-    constexpr int q_ = (Q) & 3;                                                                                                   \
-    constexpr int cp_ = SLAB_CP(TAP, q_);                                                                                         \
-    if constexpr ((Q) < 4) lds_read128<cp_ * 64>(F.ah[q_], baseA[cp_ & 3][(cp_ >> 2) & 1]);                                       \
-    else if constexpr ((Q) < 8) lds_read128<PLANE + cp_ * 64>(F.al[q_], baseA[cp_ & 3][(cp_ >> 2) & 1]);                          \
-    else if constexpr ((Q) < 12) lds_read128<p_stage_off(ST) + q_ * 1024>(F.bh[q_], addrB);                                       \
-    else lds_read128<p_stage_off(ST) + 8192 + q_ * 1024>(F.bl[q_], addrB);                                                        \
-  }
-#define SLAB_PAIR(F, Q)                                                                                                        \
-  {                                                                                                                            \
-    constexpr int i_ = (Q) >> 2, j_ = (Q) & 3;                                                                                 \
-    acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F.bl[j_], F.ah[i_], acc[i_][j_], 0, 0, 0);                            \
-    acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F.bh[j_], F.al[i_], acc[i_][j_], 0, 0, 0);                            \
-    acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(F.bh[j_], F.ah[i_], acc[i_][j_], 0, 0, 0);                            \
-  }
-  // GN: thirds issued at (tap 0, slot 0) and (taps 2 / 4, slot 12), transformed in taps 2 / 4 / 6 - the slots of conv_slab_kernel<true>;
-  // the next tile's scale / shift table at (tap 3, slot 5) of a tile's first chunk pair (landed and barrier-published long before
-  // tap 11 first reads it)
-#define SLAB_ISSUE(T, Q)                                                                          \
-  if constexpr (!GN && (Q) == 0 && ((T) % 9) < 3) issue_slab(1 - (T) / 9, (T) % 9, chunk0 + (T) / 9 + 1);  \
-  if constexpr (GN && (Q) == 0 && ((T) % 9) == 0) issue_slab_f(xr, 0, chunk0 + (T) / 9 + 1);           \
-  if constexpr (GN && (Q) == 12 && (((T) % 9) == 2 || ((T) % 9) == 4)) issue_slab_f(xr, ((T) % 9) / 2, chunk0 + (T) / 9 + 1);  \
-  if constexpr (GN && (T) == 3 && (Q) == 5) { if (first) issue_gss(gss_nxt, gn.img); }               \
-  if constexpr ((Q) == 2) issue_b(p_stage_off(((T) + 3) % 3), chunk0 + ((T) + 3) / 9, ((T) + 3) % 9);
-#define SLAB_XF(T, Q)                                                                             \
-  if constexpr (GN && ((T) % 9) >= 2 && ((T) % 9) <= 6 && ((T) % 9) % 2 == 0) {                    \
-    constexpr int k_ = ((T) % 9) / 2 - 1;                                                         \
-    if constexpr ((Q) == 1) load_gss(chunk0 + (T) / 9 + 1, 0);                                    \
-    if constexpr ((Q) >= 2 && (Q) < 6) xform_elem(xr, (Q) - 2);                                   \
-    if constexpr ((Q) == 6) load_gss(chunk0 + (T) / 9 + 1, 1);                                    \
-    if constexpr ((Q) >= 7 && (Q) < 11) xform_elem(xr, (Q) - 3);                                  \
-    if constexpr ((Q) == 11) store_slab_f(xr, 1 - (T) / 9, k_, chunk0 + (T) / 9 + 1);             \
-  }
-#define SLAB_SLOT(CUR, NXT, T, Q)                                                   \
-  SLAB_PAIR(CUR, Q)                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                \
-  SLAB_ISSUE(T, Q)                                                                  \
-  SLAB_READ(NXT, (((T) + 1) % 3), (((T) + 1) % 9), Q)                               \
-  SLAB_XF(T, Q)                                                                     \
-  __builtin_amdgcn_sched_barrier(0);
-  // counted waits as in the launch-per-tile kernels (GN: two more at the top of taps 1, 3, 4, 5, 6 of a chunk); the extra scale /
-  // shift DMA of a tile's first pass makes the waits of its taps 4 and 5 merely stricter
-#define SLAB_WAIT(T)                                                                                                        \
-  if constexpr ((T) < 2) {                                                                                                  \
-    if (first) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                          \
-    else if constexpr ((T) == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                               \
-    else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                                                        \
-  } else if constexpr (GN ? (((T) % 9) == 1 || (((T) % 9) >= 3 && ((T) % 9) <= 6)) : (((T) % 9) >= 1 && ((T) % 9) <= 3))   \
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");                                                             \
-  else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-#define SLAB_TAP(CUR, NXT, T)                                                                         \
-  SLAB_WAIT(T)                                                                                        \
-  __builtin_amdgcn_s_barrier();                                                                       \
-  if constexpr ((T) == 8) flip_base(P_BUF1);                                                          \
-  if constexpr ((T) == 17) flip_base(-P_BUF1);                                                        \
-  __builtin_amdgcn_sched_barrier(0);                                                                  \
-  SLAB_SLOT(CUR, NXT, T, 0) SLAB_SLOT(CUR, NXT, T, 1) SLAB_SLOT(CUR, NXT, T, 2) SLAB_SLOT(CUR, NXT, T, 3)     \
-  SLAB_SLOT(CUR, NXT, T, 4) SLAB_SLOT(CUR, NXT, T, 5) SLAB_SLOT(CUR, NXT, T, 6) SLAB_SLOT(CUR, NXT, T, 7)     \
-  SLAB_SLOT(CUR, NXT, T, 8) SLAB_SLOT(CUR, NXT, T, 9) SLAB_SLOT(CUR, NXT, T, 10) SLAB_SLOT(CUR, NXT, T, 11)   \
-  SLAB_SLOT(CUR, NXT, T, 12) SLAB_SLOT(CUR, NXT, T, 13) SLAB_SLOT(CUR, NXT, T, 14) SLAB_SLOT(CUR, NXT, T, 15)
-
-  // ---- first tile: its operands as the "next tile" of an empty predecessor ----
+  // ---- first tile: its operands as the "next tile" of an empty predecessor (chunk `nchunks` = chunk 0 of the next tile) ----
   int v = blockIdx.x;
   Geo g = geo_of(v);
   offsets_of(g, true, slab_off_n, voffB_n, lane);
@@ -971,21 +865,12 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
     for (int c = threadIdx.x; c < Cin; c += NT) { gss_nxt[c] = p.gsc[(long)g.img * Cin + c]; gss_nxt[Cin + c] = p.gsh[(long)g.img * Cin + c]; }
     u32x4 pr[3][2];
     issue_slab_f(pr[0], 0, nchunks); issue_slab_f(pr[1], 1, nchunks); issue_slab_f(pr[2], 2, nchunks);
-    issue_b(p_stage_off(0), nchunks, 0); issue_b(p_stage_off(1), nchunks, 1); issue_b(p_stage_off(2), nchunks, 2);
+    issue_b(0, nchunks, 0); issue_b(1, nchunks, 1); issue_b(2, nchunks, 2);
     __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      load_gss(nchunks, h);
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xform_elem(pr[k], h * 4 + e);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) store_slab_f(pr[k], 0, k, nchunks);
+    SLAB_CHUNK0_F(pr, nchunks)
   } else {
     issue_slab(0, 0, nchunks); issue_slab(0, 1, nchunks); issue_slab(0, 2, nchunks);
-    issue_b(p_stage_off(0), nchunks, 0); issue_b(p_stage_off(1), nchunks, 1); issue_b(p_stage_off(2), nchunks, 2);
+    issue_b(0, nchunks, 0); issue_b(1, nchunks, 1); issue_b(2, nchunks, 2);
   }
   // (Measured and rejected: starting the blocks in eight phases an eighth of a tile apart, to keep 256 CUs from writing their
   //  32 MB of output at the same instant.  scripts/exp/conv_seam.py: T(Cin) = 13-15 us + 8.1 us per 32-channel chunk per tile
@@ -993,10 +878,7 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  SLAB_READ(f0, 0, 0, 0) SLAB_READ(f0, 0, 0, 1) SLAB_READ(f0, 0, 0, 2) SLAB_READ(f0, 0, 0, 3)
-  SLAB_READ(f0, 0, 0, 4) SLAB_READ(f0, 0, 0, 5) SLAB_READ(f0, 0, 0, 6) SLAB_READ(f0, 0, 0, 7)
-  SLAB_READ(f0, 0, 0, 8) SLAB_READ(f0, 0, 0, 9) SLAB_READ(f0, 0, 0, 10) SLAB_READ(f0, 0, 0, 11)
-  SLAB_READ(f0, 0, 0, 12) SLAB_READ(f0, 0, 0, 13) SLAB_READ(f0, 0, 0, 14) SLAB_READ(f0, 0, 0, 15)
+  SLAB_READ_TAP0(f0)
   __builtin_amdgcn_sched_barrier(0);
 
   for (;;) {
@@ -1010,7 +892,7 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
     const Geo gn = geo_of(has_next ? vn : v);
     {
       int ln = lane;
-      asm volatile("" : "+v"(ln));
+      asm volatile("" : "+v"(ln));   // per-lane geometry is recomputed per tile instead of living in registers across the K loop
       offsets_of(gn, has_next, slab_off_n, voffB_n, ln);
     }
 #pragma unroll
@@ -1021,9 +903,7 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
     CDMA_TSV(v, 0)
     bool first = true;
     for (int chunk0 = 0; chunk0 < nchunks; chunk0 += 2) {
-      SLAB_TAP(f0, f1, 0) SLAB_TAP(f1, f0, 1) SLAB_TAP(f0, f1, 2) SLAB_TAP(f1, f0, 3) SLAB_TAP(f0, f1, 4) SLAB_TAP(f1, f0, 5)
-      SLAB_TAP(f0, f1, 6) SLAB_TAP(f1, f0, 7) SLAB_TAP(f0, f1, 8) SLAB_TAP(f1, f0, 9) SLAB_TAP(f0, f1, 10) SLAB_TAP(f1, f0, 11)
-      SLAB_TAP(f0, f1, 12) SLAB_TAP(f1, f0, 13) SLAB_TAP(f0, f1, 14) SLAB_TAP(f1, f0, 15) SLAB_TAP(f0, f1, 16) SLAB_TAP(f1, f0, 17)
+      SLAB_TWO_CHUNKS(f0, f1)
       first = false;
     }
 
@@ -1108,16 +988,9 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
           const unsigned prowstep = (unsigned)((long)(W >> 1) * p.N * 4);
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            f32x4 v[4];
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-              v[d] = *(const f32x4*)(smem + P_STAGING + ((2 * qy0 + 4 * k + (d >> 1)) * 16 + 2 * qx + (d & 1)) * CST + col * 4);
-            const f32x4 w = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;   // avgpool_stats_kernel's order
+            SLAB_POOLED_WINDOW(w, smem + P_STAGING, k, )
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), rs_out, (int)pbase, (int)(prowstep * (half * 4 + 2 * k)), 0);
-            if (p.gn_partial) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
-            }
+            SLAB_STAT4(w)
           }
         }
       } else if (n < p.N) {
@@ -1125,61 +998,62 @@ __global__ __launch_bounds__(512, 2) void conv_slab_persist_kernel(Params p) {
         for (int it = 0; it < NITH; ++it) {
           const f32x4 w = *(const f32x4*)(smem + P_STAGING + (rbase + 16 * it) * CST + col * 4);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, w), rs_out, (int)obase, (int)(rowstep * (half * NITH + it)), 0);
-          if (p.gn_partial) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { gs += (double)w[e]; gq += (double)w[e] * (double)w[e]; }
-          }
+          SLAB_STAT4(w)
         }
       }
     }
     CDMA_TSV(v, 4)
-    if (p.gn_partial) {
-      gs += __shfl_xor(gs, 32, 64);
-      gq += __shfl_xor(gq, 32, 64);
-      lds_barrier();
-      double* red = (double*)(smem + P_STAGING);   // [8 waves][32 chunks][2]
-      if (lane_e < 32) { red[(wave * 32 + lane_e) * 2] = gs; red[(wave * 32 + lane_e) * 2 + 1] = gq; }
-      lds_barrier();
-      if (tx < 32) {
-        double cs = 0.0, cq = 0.0;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) { cs += red[(w8 * 32 + tx) * 2]; cq += red[(w8 * 32 + tx) * 2 + 1]; }
-        const int cpc = p.gn_cpg >> 2;
-        for (int o = 1; o < cpc; o <<= 1) { cs += __shfl_xor(cs, o, 64); cq += __shfl_xor(cq, o, 64); }
-        const int nn = n0 + tx * 4;
-        if ((tx & (cpc - 1)) == 0 && nn < p.N) {
-          double* o2 = p.gn_partial + (((long)g.img * tpi + g.prem) * p.gn_groups + (nn >> __builtin_ctz(p.gn_cpg))) * 2;   // gn_cpg is a power of two (host check)
-          o2[0] = cs; o2[1] = cq;
-        }
-      }
-    }
+    SLAB_FOLD_PARTIALS(smem + P_STAGING, lds_barrier(), lane_e, tx, (long)g.img * tpi + g.prem, (nn >> __builtin_ctz(p.gn_cpg)))   // gn_cpg is a power of two (host check)
     CDMA_TSV(v, 5)
     if (!has_next) break;
     v = vn; g = gn;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    SLAB_READ(f0, 0, 0, 0) SLAB_READ(f0, 0, 0, 1) SLAB_READ(f0, 0, 0, 2) SLAB_READ(f0, 0, 0, 3)
-    SLAB_READ(f0, 0, 0, 4) SLAB_READ(f0, 0, 0, 5) SLAB_READ(f0, 0, 0, 6) SLAB_READ(f0, 0, 0, 7)
-    SLAB_READ(f0, 0, 0, 8) SLAB_READ(f0, 0, 0, 9) SLAB_READ(f0, 0, 0, 10) SLAB_READ(f0, 0, 0, 11)
-    SLAB_READ(f0, 0, 0, 12) SLAB_READ(f0, 0, 0, 13) SLAB_READ(f0, 0, 0, 14) SLAB_READ(f0, 0, 0, 15)
+    SLAB_READ_TAP0(f0)
     __builtin_amdgcn_sched_barrier(0);
     // (the top-of-tap-0 wait + barrier of the next tile orders its first DMAs / fragment reads behind these staging reads)
   }
+}
+#undef SLAB_FOLD_PARTIALS
+#undef SLAB_POOLED_WINDOW
+#undef SLAB_STAT4
+#undef SLAB_TWO_CHUNKS
 #undef SLAB_TAP
 #undef SLAB_WAIT
 #undef SLAB_SLOT
 #undef SLAB_XF
 #undef SLAB_ISSUE
 #undef SLAB_PAIR
+#undef SLAB_READ_TAP0
 #undef SLAB_READ
 #undef SLAB_CP
-}
+#undef SLAB_CHUNK0_F
+#undef SLAB_BODY
+#undef GNX_SILU
+#undef GNX_SS
+#undef SLAB_IN_TILE
+#undef SLAB_SETUP
 
 }  // namespace cslab
 
 #ifdef CDMA_TIMESTAMPS
 extern "C" int muse_debug_conv_ts(long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(cslab::g_conv_ts), &buf, sizeof(buf)); }
 #endif
+// Everything of cdma::Params but the activation pointers, and the validity of the fused GroupNorm statistics: groups of 4 * 2^k channels
+// inside one 128-channel tile; whole_tiles: the kernel may cut 256-pixel tiles across images, so an image has to be whole tiles (the
+// patch-slab shapes are by construction)
+static int conv_params(cdma::Params& p, const void* w_hi, const void* w_lo, const float* bias, const float* residual, float* out,
+                       double* gn_partial, int32_t gn_groups, long M, int32_t H, int32_t W, int32_t Cin, int32_t Cout, bool whole_tiles) {
+  p.wh = (const bf16_t*)w_hi; p.wl = (const bf16_t*)w_lo;
+  p.bias = bias; p.residual = residual; p.out = out;
+  p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
+  if (gn_partial) {
+    const int cpg = p.gn_cpg;
+    if (gn_groups <= 0 || (Cout % gn_groups) || (whole_tiles && ((H * W) % 256)) || cpg < 4 || cpg > 128 || (cpg & (cpg - 1))) return MUSE_ERR_UNSUPPORTED;
+  }
+  p.M = (int)M; p.N = Cout; p.K = 9 * Cin; p.H = H; p.W = W; p.Cin = Cin;
+  return 0;
+}
 extern "C" int muse_conv2d_nhwc_split2(const void* in_hi, const void* in_lo, const void* w_hi, const void* w_lo, const float* bias,
                                        const float* residual, float* out, double* gn_partial, int32_t gn_groups, int32_t batch,
                                        int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KS, void* stream) {
@@ -1192,14 +1066,8 @@ extern "C" int muse_conv2d_nhwc_split2(const void* in_hi, const void* in_lo, con
   // 32-bit buffer offsets: each plane / weight image must stay below 4 GiB (and M below 2^31)
   if (M * Cin * 2 >= (1L << 32) - 64 || (long)Cout * 9 * Cin * 2 >= (1L << 32) - 64 || M >= (1L << 31) - 256) return MUSE_ERR_UNSUPPORTED;
   cdma::Params p;
-  p.xh = (const bf16_t*)in_hi; p.xl = (const bf16_t*)in_lo; p.wh = (const bf16_t*)w_hi; p.wl = (const bf16_t*)w_lo;
-  p.bias = bias; p.residual = residual; p.out = out;
-  p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
-  if (gn_partial) {  // fused GroupNorm statistics: whole 256-pixel tiles per image, groups of 4 * 2^k channels inside one 128-channel tile
-    const int cpg = p.gn_cpg;
-    if (gn_groups <= 0 || (Cout % gn_groups) || ((H * W) % 256) || cpg < 4 || cpg > 128 || (cpg & (cpg - 1))) return MUSE_ERR_UNSUPPORTED;
-  }
-  p.M = (int)M; p.N = Cout; p.K = 9 * Cin; p.H = H; p.W = W; p.Cin = Cin;
+  p.xh = (const bf16_t*)in_hi; p.xl = (const bf16_t*)in_lo;
+  if (const int rc = conv_params(p, w_hi, w_lo, bias, residual, out, gn_partial, gn_groups, M, H, W, Cin, Cout, true)) return rc;
   const int ntm = (p.M + cdma::BM - 1) / cdma::BM, ntn = (p.N + cdma::BN - 1) / cdma::BN;
   static const int use_slab = []() { const char* e = getenv("MUSE_CONV_SLAB"); return e ? atoi(e) : 1; }();
   if (use_slab && (H % 16) == 0 && (W % 16) == 0 && (Cin % 64) == 0) {   // patch-slab kernel (K order: chunk, tap, channel)
@@ -1244,14 +1112,7 @@ static int conv_gn_split2_launch(const float* x, const float* gn_scale, const fl
   if ((((uintptr_t)x) | ((uintptr_t)w_hi) | ((uintptr_t)w_lo) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15) return MUSE_ERR_ALIGN;
   cdma::Params p;
   p.xh = p.xl = nullptr; p.xf = x; p.gsc = gn_scale; p.gsh = gn_shift;
-  p.wh = (const bf16_t*)w_hi; p.wl = (const bf16_t*)w_lo;
-  p.bias = bias; p.residual = residual; p.out = out;
-  p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
-  if (gn_partial) {
-    const int cpg = p.gn_cpg;
-    if (gn_groups <= 0 || (Cout % gn_groups) || cpg < 4 || cpg > 128 || (cpg & (cpg - 1))) return MUSE_ERR_UNSUPPORTED;
-  }
-  p.M = (int)M; p.N = Cout; p.K = 9 * Cin; p.H = H; p.W = W; p.Cin = Cin;
+  if (const int rc = conv_params(p, w_hi, w_lo, bias, residual, out, gn_partial, gn_groups, M, H, W, Cin, Cout, false)) return rc;
   const int ntn = (p.N + cslab::BN - 1) / cslab::BN;
   // persistent form (round 6): one workgroup per CU walks the tiles, the K loop's look-ahead runs on into the next tile.  Taken when a
   // CU gets at least MUSE_CONV_PERSIST_MIN tiles (default 2), Cin <= 256 (two scale / shift tables behind the LDS map) and the output
