@@ -163,6 +163,19 @@ int muse_attention_fwd_ex(const muse_attn_desc* d, float* lse, void* stream);
 int muse_attention_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, float* dsum,
                           void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv,
                           int64_t bsdv, void* stream);
+/* The same with nn.Dropout on the attention probabilities (muse/modeling_transformer.py:237) applied inside the kernels: no
+ * probability tensor and no mask tensor exist.  The keep bit of (image * heads + head = bh, query q, key k) is the bit
+ * muse_dropout(seed, offset) produces for flat element e = (bh * seq_q + q) * ld_mask + k of a [batch*heads, seq_q, ld_mask] tensor
+ * (Philox block offset + (e >> 2), word e & 3, kept iff u >= p), so with ld_mask = the materialised route's row pitch (seq_kv rounded
+ * up to 8) both routes drop the same elements.  ld_mask: a multiple of 4, >= seq_kv.  Arithmetic: lse and the softmax row sum use the
+ * undropped P; o = sum_k bf16(P keep / (1 - p)) v (one rounding of the f32 product); backward dsum = sum_d d_o o,
+ * dS = P (keep / (1 - p) dP - dsum), dV = bf16(P keep / (1 - p))^T d_o.  The backward is given the same (p, seed, offset, ld_mask).
+ * p == 0 is muse_attention_fwd_ex / _bwd_ex (bit-identical); p < 0, p >= 1 or a bad ld_mask: MUSE_ERR_BAD_ARG. */
+int muse_attention_drop_fwd_ex(const muse_attn_desc* d, float* lse, float p, uint64_t seed, uint64_t offset, int64_t ld_mask,
+                               void* stream);
+int muse_attention_drop_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, float* dsum,
+                               void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv,
+                               int64_t bsdv, float p, uint64_t seed, uint64_t offset, int64_t ld_mask, void* stream);
 /* The same seam for the "bf16x3" compute mode (f32 tensors, TF32-class products: configs/cc12m_uvit_clip.yaml:102-103 trains with
  * mixed_precision "no" + enable_tf32): q / k / v / o / d_o / dq / dk / dv are FLOAT tensors (strides in elements, multiples of 4),
  * every product of the forward and the backward is three bf16 MFMA products of (hi, lo) operand planes the kernel makes itself

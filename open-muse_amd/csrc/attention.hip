@@ -20,6 +20,7 @@
 // head_dim 48 contracts as one K=32 MFMA plus one K=16 MFMA (v_mfma_f32_16x16x16_bf16) instead of two half-empty K=32 ones.
 #include "common.h"
 #include "attention_params.h"
+#include "philox.h"
 #include "../../include/muse_hip.h"
 #include <stdlib.h>
 
@@ -177,6 +178,44 @@ __device__ __forceinline__ float quad_g_max(float v) {
   return v;
 }
 
+// ---- attention dropout (the DROP instantiations) ----------------------------------------------------------------------------
+// The keep bit of (bh, q, k) is the one muse_dropout(seed, offset) gives flat element e = (bh * sq + q) * ld_mask + k: word e & 3 of
+// Philox block offset + (e >> 2).  ld_mask is a multiple of 4 and a lane's four scores of a 16-key tile are keys 16 t + 4 g + 0..3 of
+// one query, so one block serves them.  u01_open_high(r) >= p is, with T = ceil(p * 2^24) (exact: (r >> 8) * 2^-24 has no rounding),
+// (r >> 8) >= T, i.e. r >= T << 8 = drop_thr: one compare per score.
+__device__ __forceinline__ u4 drop_block(const AttnParams& P, uint64_t blk) {
+  return philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), MUSE_DROPOUT_TAG, 0u, P.seed_lo, P.seed_hi);
+}
+// Philox block of query row `q` (absolute) of head bh, key 0
+__device__ __forceinline__ uint64_t drop_row(const AttnParams& P, int bh, int q) {
+  return P.drop_off + ((uint64_t)bh * (unsigned)P.sq + (unsigned)q) * P.ld4;
+}
+// v * keep / (1 - p) for the four keys of block `blk`
+__device__ __forceinline__ f32x4 drop4(const f32x4& v, const AttnParams& P, uint64_t blk) {
+  const u4 r = drop_block(P, blk);
+  f32x4 o;
+  o[0] = r.x >= P.drop_thr ? v[0] * P.drop_scale : 0.f;
+  o[1] = r.y >= P.drop_thr ? v[1] * P.drop_scale : 0.f;
+  o[2] = r.z >= P.drop_thr ? v[2] * P.drop_scale : 0.f;
+  o[3] = r.w >= P.drop_thr ? v[3] * P.drop_scale : 0.f;
+  return o;
+}
+// dK,dV: a lane holds ONE key (lane & 15) and four queries 4 g + 0..3, i.e. one word of four blocks.  The four lanes of a quad hold
+// four consecutive keys of the same queries: lane a of the quad draws the block of query 4 g + a and turns it into 4 keep bits; a
+// lane then reads, from quad lane r, bit (lane & 3): its key's bit of query 4 g + r.  -> scale where kept, else 0
+template <int R>
+__device__ __forceinline__ float quad_keep(unsigned bits, int lane, float scale) {
+  const unsigned m = (unsigned)__builtin_amdgcn_update_dpp(0, (int)bits, R * 0x55, 0xf, 0xf, true);   // quad_perm:[R,R,R,R]
+  return (m >> (lane & 3)) & 1u ? scale : 0.f;
+}
+__device__ __forceinline__ f32x4 drop_quad(const AttnParams& P, uint64_t blk, int lane) {
+  const u4 r = drop_block(P, blk);
+  const unsigned bits = (r.x >= P.drop_thr ? 1u : 0u) | (r.y >= P.drop_thr ? 2u : 0u) | (r.z >= P.drop_thr ? 4u : 0u) | (r.w >= P.drop_thr ? 8u : 0u);
+  f32x4 o;
+  o[0] = quad_keep<0>(bits, lane, P.drop_scale); o[1] = quad_keep<1>(bits, lane, P.drop_scale);
+  o[2] = quad_keep<2>(bits, lane, P.drop_scale); o[3] = quad_keep<3>(bits, lane, P.drop_scale);
+  return o;
+}
 
 // blockIdx -> logical work item such that consecutive logical items (chunks of one head) run on one XCD (block b runs on XCD b % 8)
 __device__ __forceinline__ int xcd_remap() {
@@ -205,10 +244,11 @@ template <int HD> struct FwdAcc {
 // One online-softmax update over TN consecutive 16-key tiles starting at tile t0 of the LDS images (TN even):
 // scores (keys at tile index >= MASK_FROM within the step get the -1e30 init where they lie past the sequence end),
 // row max, rescale, P = exp2(...), O += P V and l += P 1 (the row sum as one more MFMA against a ones operand: VALU is the
-// busy pipe of this kernel, the matrix pipe has room).
-template <int HD, int TN, int MASK_FROM>
+// busy pipe of this kernel, the matrix pipe has room).  DROP: O += bf16(P keep / (1 - p)) V, one rounding of the f32 product; the row
+// sum and the maximum keep the undropped P.  dctr = Philox block of this lane's query at the image's key 4 g (tile t adds 4 t).
+template <int HD, int TN, int MASK_FROM, bool DROP>
 __device__ __forceinline__ void fwd_substep(const unsigned char* Kimg, const unsigned char* Vimg, int t0, const FragHD<HD>& qf,
-                                            float c, int kvalid, FwdAcc<HD>& A, int lane) {
+                                            float c, int kvalid, FwdAcc<HD>& A, int lane, const AttnParams& P, uint64_t dctr) {
   using C = HeadCfg<HD>;
   f32x4 sacc[TN];
   float mt = NEG_BIG;
@@ -241,9 +281,12 @@ __device__ __forceinline__ void fwd_substep(const unsigned char* Kimg, const uns
   for (int s = 0; s < TN / 2; ++s) {
     const bf16x8 pb = pack8(sacc[2 * s], sacc[2 * s + 1]);
     A.l = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones.v, pb, A.l, 0, 0, 0);
+    bf16x8 pd = pb;
+    if constexpr (DROP)
+      pd = pack8(drop4(sacc[2 * s], P, dctr + 4 * (t0 + 2 * s)), drop4(sacc[2 * s + 1], P, dctr + 4 * (t0 + 2 * s + 1)));
 #pragma unroll
     for (int d = 0; d < C::ND; ++d)
-      A.o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_seq<HD>(Vimg, 16 * t0 + 32 * s, 16 * d, lane), pb, A.o[d], 0, 0, 0);
+      A.o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_seq<HD>(Vimg, 16 * t0 + 32 * s, 16 * d, lane), pd, A.o[d], 0, 0, 0);
   }
 }
 
@@ -266,12 +309,12 @@ constexpr int fwd_waves_per_simd(int hd_rs, int maxt, int nw) {
 // Keys past the sequence end are masked through the MFMA's C operand (-1e30 instead of 0), which costs nothing for the
 // tiles that cannot contain the end: with FULL = false only the last two 16-key tiles of a K/V tile can (the host picks
 // MAXT = 2 * ceil(S_kv / 32) for one-tile problems and S_kv % 256 == 0 or > 224 for streamed ones), FULL = true masks every tile.
-template <int HD, int MAXT, int NW, bool FULL>
+template <int HD, int MAXT, int NW, bool FULL, bool DROP>
 __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, NW)) void attn_fwd_kernel(const AttnParams P) {
   using C = HeadCfg<HD>;
   constexpr int NT = NW * 64;
   constexpr int ROWS = MAXT * 16;
-  constexpr int CT = 6;                     // 16-key tiles per online-softmax step (register budget)
+  constexpr int CT = DROP ? 4 : 6;          // 16-key tiles per online-softmax step (register budget; the Philox rounds need room too)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* Kimg = smem;
   unsigned char* Vimg = smem + ROWS * C::RS;
@@ -290,19 +333,26 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
 
   FragHD<HD> qf;
   FwdAcc<HD> A;
+  uint64_t drow = 0;   // DROP: Philox block of this lane's query at key 4 g
+  auto drop_tile = [&](int qt) {
+    if constexpr (DROP) drow = drop_row(P, bh, q_begin + qt * 16 + (lane & 15)) + g;
+  };
 
   auto step = [&](int kv0) {   // this wave's q-tile against the whole LDS tile
-    const int kvalid = P.skv - kv0 - 4 * g;   // this lane's keys kv0 + 16 t + 4 g + r are real iff 16 t + r < kvalid
+    int kvalid = P.skv - kv0 - 4 * g;   // this lane's keys kv0 + 16 t + 4 g + r are real iff 16 t + r < kvalid
+    // (DROP: opaque, so that the every-tile-masked form's 64 mask values are made per q-tile, not hoisted out of the loop and spilled)
+    if constexpr (DROP) asm volatile("" : "+v"(kvalid));
+    const uint64_t dctr = drow + (kv0 >> 2);
 #pragma unroll
     for (int t0 = 0; t0 < MAXT; t0 += CT) {
       if (t0) __builtin_amdgcn_sched_barrier(0);   // keep the next step's LDS reads from being hoisted over this one (registers)
       if (MAXT - t0 >= CT) {
-        if (FULL) fwd_substep<HD, CT, 0>(Kimg, Vimg, t0, qf, c, kvalid, A, lane);
-        else if (MAXT - t0 == CT) fwd_substep<HD, CT, CT - 2>(Kimg, Vimg, t0, qf, c, kvalid, A, lane);
-        else fwd_substep<HD, CT, CT>(Kimg, Vimg, t0, qf, c, kvalid, A, lane);   // (MAXT and CT even: the end cannot be in here)
+        if (FULL) fwd_substep<HD, CT, 0, DROP>(Kimg, Vimg, t0, qf, c, kvalid, A, lane, P, dctr);
+        else if (MAXT - t0 == CT) fwd_substep<HD, CT, CT - 2, DROP>(Kimg, Vimg, t0, qf, c, kvalid, A, lane, P, dctr);
+        else fwd_substep<HD, CT, CT, DROP>(Kimg, Vimg, t0, qf, c, kvalid, A, lane, P, dctr);   // (MAXT and CT even: the end cannot be in here)
       } else {
         constexpr int TN = MAXT % CT ? MAXT % CT : 2;
-        fwd_substep<HD, TN, FULL ? 0 : TN - 2>(Kimg, Vimg, t0, qf, c, kvalid, A, lane);
+        fwd_substep<HD, TN, FULL ? 0 : TN - 2, DROP>(Kimg, Vimg, t0, qf, c, kvalid, A, lane, P, dctr);
       }
     }
   };
@@ -328,6 +378,7 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
       const int nxt = qt + NW < nfull ? qt + NW : ntq - 1;                    // next whole tile, or the shared one
       qn = frag_global<HD>(rq, ldq_b, q_begin + nxt * 16, lane);
       fwd_reset<HD>(A);
+      drop_tile(qt);
       step(0);
       finish(qt);
     }
@@ -335,12 +386,13 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
       const int qs = ntq - 1;
       qf = nfull > wave ? qn : frag_global<HD>(rq, ldq_b, q_begin + qs * 16, lane);
       fwd_reset<HD>(A);
+      drop_tile(qs);
       const int kvalid = P.skv - 4 * g;
       // Only pairs that hold a real key.  The every-tile-masked 16-tile form (97 <= S_kv <= 224) has pairs past the sequence end, and a
       // wave whose first pair is all mask starts from m = -1e30 with every score -1e30: fmaf(s, c, -m c) is then the rounding error of
       // m c (+-1e21, its sign set by alpha), i.e. P = exp2(+1e21) = inf at head_dim 16 / 48 / 64 and O = inf * 0 = NaN in the shared tile's
       // rows.  A wave without a real pair keeps the reset state, which the merge below weighs with exp2(-huge) = 0.
-      for (int s = wave; s < MAXT / 2 && 32 * s < P.skv; s += NW) fwd_substep<HD, 2, 0>(Kimg, Vimg, 2 * s, qf, c, kvalid, A, lane);
+      for (int s = wave; s < MAXT / 2 && 32 * s < P.skv; s += NW) fwd_substep<HD, 2, 0, DROP>(Kimg, Vimg, 2 * s, qf, c, kvalid, A, lane, P, drow);
       __syncthreads();                                   // every wave is done with the K / V images
       constexpr int PW = HD + 2;                         // floats per (wave, row): O | m | l
       float* part = (float*)smem;
@@ -372,6 +424,7 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
     const bool active = wave < ntq;
     qf = frag_global<HD>(rq, ldq_b, q_begin + wave * 16, lane);
     fwd_reset<HD>(A);
+    drop_tile(wave);
     for (int j = 0; j < P.ntile; ++j) {
       const int kv0 = j * ROWS;
       if (j) __syncthreads();
@@ -389,11 +442,11 @@ __global__ __launch_bounds__(NW * 64, fwd_waves_per_simd(HeadCfg<HD>::RS, MAXT, 
 // Each wave owns 16-query tiles and walks the keys in pairs of 16-key tiles.
 // =================================================================================================================
 // one 32-key pair: dS for the wave's q-tile, acc += dS K.  MASK: keys past the sequence end (only the last pair of the last
-// streamed tile can hold them) get the -1e30 score init, so P = 0 there.
-template <int HD, bool MASK>
+// streamed tile can hold them) get the -1e30 score init, so P = 0 there.  DROP: dS = P (keep / (1 - p) dP - dsum); dctr as in the forward.
+template <int HD, bool MASK, bool DROP>
 __device__ __forceinline__ void dq_pair(const unsigned char* Kimg, const unsigned char* Vimg, int s, const FragHD<HD>& qf,
                                         const FragHD<HD>& df, float c, float lq2, float dsq, int kvalid,
-                                        f32x4 (&acc)[HeadCfg<HD>::ND], int lane) {
+                                        f32x4 (&acc)[HeadCfg<HD>::ND], int lane, const AttnParams& P, uint64_t dctr) {
   using C = HeadCfg<HD>;
   f32x4 dsv[2];
 #pragma unroll
@@ -405,7 +458,8 @@ __device__ __forceinline__ void dq_pair(const unsigned char* Kimg, const unsigne
       for (int r = 0; r < 4; ++r) ci[r] = (k0 + r < kvalid) ? 0.f : NEG_BIG;
     }
     const f32x4 sa = mma_hd<HD>(frag_lds<HD>(Kimg, k0, lane), qf, ci);
-    const f32x4 dp = mma_hd<HD>(frag_lds<HD>(Vimg, k0, lane), df, f32x4{0.f, 0.f, 0.f, 0.f});
+    f32x4 dp = mma_hd<HD>(frag_lds<HD>(Vimg, k0, lane), df, f32x4{0.f, 0.f, 0.f, 0.f});
+    if constexpr (DROP) dp = drop4(dp, P, dctr + (k0 >> 2));
 #pragma unroll
     for (int r = 0; r < 4; ++r) dsv[half][r] = __builtin_amdgcn_exp2f(fmaf(sa[r], c, -lq2)) * (dp[r] - dsq);
   }
@@ -415,7 +469,7 @@ __device__ __forceinline__ void dq_pair(const unsigned char* Kimg, const unsigne
     acc[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_seq<HD>(Kimg, 32 * s, 16 * d, lane), dsb, acc[d], 0, 0, 0);
 }
 
-template <int HD, int NW>
+template <int HD, int NW, bool DROP>
 __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const AttnParams P) {
   using C = HeadCfg<HD>;
   constexpr int NT = NW * 64;
@@ -439,6 +493,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const AttnParams P
 
   FragHD<HD> qf, df;
   float lq2 = 0.f, dsq = 0.f;   // lse * log2(e), dsum of this lane's query
+  uint64_t drow = 0;            // DROP: Philox block of this lane's query at key 4 g
   f32x4 acc[C::ND];
   struct QIn { FragHD<HD> q, d, o; float l; };   // what a q-tile needs from global memory (prefetched one tile ahead)
 
@@ -458,13 +513,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const AttnParams P
     dsq = quad_g_sum(dot_hd<HD>(t.d, t.o));
     lq2 = t.l * LOG2E;
     if (write_dsum && q < q_end && g == 0) P.dsum[(long)bh * P.sqp + q] = dsq;
+    if constexpr (DROP) drow = drop_row(P, bh, q) + g;
 #pragma unroll
     for (int d = 0; d < C::ND; ++d) acc[d] = f32x4{0.f, 0.f, 0.f, 0.f};
   };
   auto step = [&](int kv0, int npair) {   // all pairs of the LDS tile; only the last one can hold the sequence end
     const int kvalid = P.skv - kv0 - 4 * g;
-    for (int s = 0; s < npair - 1; ++s) dq_pair<HD, false>(Kimg, Vimg, s, qf, df, c, lq2, dsq, kvalid, acc, lane);
-    dq_pair<HD, true>(Kimg, Vimg, npair - 1, qf, df, c, lq2, dsq, kvalid, acc, lane);
+    const uint64_t dctr = drow + (kv0 >> 2);
+    for (int s = 0; s < npair - 1; ++s) dq_pair<HD, false, DROP>(Kimg, Vimg, s, qf, df, c, lq2, dsq, kvalid, acc, lane, P, dctr);
+    dq_pair<HD, true, DROP>(Kimg, Vimg, npair - 1, qf, df, c, lq2, dsq, kvalid, acc, lane, P, dctr);
   };
   auto finish_tile = [&](int qt) {
     const int q = q_begin + qt * 16 + (lane & 15);
@@ -492,7 +549,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const AttnParams P
       const int qs = ntq - 1;
       begin_tile(qs, tn, wave == 0);
       const int kvalid = P.skv - 4 * g;
-      for (int s = wave; s < npair; s += NW) dq_pair<HD, true>(Kimg, Vimg, s, qf, df, c, lq2, dsq, kvalid, acc, lane);
+      for (int s = wave; s < npair; s += NW) dq_pair<HD, true, DROP>(Kimg, Vimg, s, qf, df, c, lq2, dsq, kvalid, acc, lane, P, drow);
       __syncthreads();                                   // every wave is done with the K / V images
       float* part = (float*)smem;
       float* mine = part + (wave * 16 + (lane & 15)) * HD;
@@ -527,11 +584,14 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const AttnParams P
 // backward, part 2: dK, dV.  Each wave owns 16-key tiles and walks the queries in pairs of 16-query tiles; the queries'
 // lse / dsum ride in LDS next to the Q and dO images (lse = +1e30 for rows past the sequence end, so their P is 0: no
 // per-element masks in this kernel; key rows past the end only produce output rows that are never stored).
+// DROP: dV += bf16(P keep / (1 - p))^T dO and dS = P (keep / (1 - p) dP - dsum); dctr = Philox block of query (LDS tile's row 0) + 4 g +
+// (lane & 3) at this lane's key (see drop_quad); LDS row r0 adds r0 * ld4.
 // =================================================================================================================
-template <int HD>
+template <int HD, bool DROP>
 __device__ __forceinline__ void dkv_pair(const unsigned char* Qimg, const unsigned char* Dimg, const float* Limg, const float* Simg,
                                          int s, const FragHD<HD>& kf, const FragHD<HD>& vf, float c,
-                                         f32x4 (&dk)[HeadCfg<HD>::ND], f32x4 (&dv)[HeadCfg<HD>::ND], int lane) {
+                                         f32x4 (&dk)[HeadCfg<HD>::ND], f32x4 (&dv)[HeadCfg<HD>::ND], int lane,
+                                         const AttnParams& P, uint64_t dctr) {
   using C = HeadCfg<HD>;
   const int g = lane >> 4;
   f32x4 pv[2], dsv[2];
@@ -542,10 +602,20 @@ __device__ __forceinline__ void dkv_pair(const unsigned char* Qimg, const unsign
     const f32x4 dp = mma_hd<HD>(frag_lds<HD>(Dimg, r0, lane), vf, f32x4{0.f, 0.f, 0.f, 0.f});
     const f32x4 l4 = *(const f32x4*)(Limg + r0 + 4 * g);
     const f32x4 d4 = *(const f32x4*)(Simg + r0 + 4 * g);
+    if constexpr (DROP) {
+      const f32x4 ks = drop_quad(P, dctr + (uint64_t)(unsigned)r0 * P.ld4, lane);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      pv[half][r] = __builtin_amdgcn_exp2f(fmaf(sa[r], c, -l4[r]));
-      dsv[half][r] = pv[half][r] * (dp[r] - d4[r]);
+      for (int r = 0; r < 4; ++r) {
+        const float pr = __builtin_amdgcn_exp2f(fmaf(sa[r], c, -l4[r]));
+        pv[half][r] = pr * ks[r];
+        dsv[half][r] = pr * (ks[r] * dp[r] - d4[r]);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        pv[half][r] = __builtin_amdgcn_exp2f(fmaf(sa[r], c, -l4[r]));
+        dsv[half][r] = pv[half][r] * (dp[r] - d4[r]);
+      }
     }
   }
   const bf16x8 pb = pack8(pv[0], pv[1]), dsb = pack8(dsv[0], dsv[1]);
@@ -556,7 +626,7 @@ __device__ __forceinline__ void dkv_pair(const unsigned char* Qimg, const unsign
   }
 }
 
-template <int HD, int NW>
+template <int HD, int NW, bool DROP>
 __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const AttnParams P) {
   using C = HeadCfg<HD>;
   constexpr int NT = NW * 64;
@@ -583,6 +653,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const AttnParams 
 
   FragHD<HD> kf, vf;
   f32x4 dv[C::ND], dk[C::ND];
+  uint64_t dblk = 0;   // DROP: Philox block of query 4 g + (lane & 3) at this lane's key (drop_quad)
 
   auto load_q_tile = [&](int q0, int rows) {
     load_tile<HD, NT, 288>(Qimg, rq, ldq_b, q0, rows);
@@ -600,8 +671,9 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const AttnParams 
     t.v = frag_global<HD>(rv, (unsigned)P.ldv * 2, k_begin + kt * 16, lane);
     return t;
   };
-  auto begin_tile = [&](const KIn& t) {
+  auto begin_tile = [&](int kt, const KIn& t) {
     kf = t.k; vf = t.v;
+    if constexpr (DROP) dblk = drop_row(P, bh, 4 * g + (lane & 3)) + ((unsigned)(k_begin + kt * 16 + (lane & 15)) >> 2);
 #pragma unroll
     for (int d = 0; d < C::ND; ++d) { dv[d] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[d] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   };
@@ -625,15 +697,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const AttnParams 
     load_q_tile(0, rows);
     __syncthreads();
     for (int kt = wave; kt < nfull; kt += NW) {
-      begin_tile(tn);
+      begin_tile(kt, tn);
       tn = fetch_tile(kt + NW < nfull ? kt + NW : ntk - 1);
-      for (int s = 0; s < npair; ++s) dkv_pair<HD>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane);
+      for (int s = 0; s < npair; ++s) dkv_pair<HD, DROP>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane, P, dblk);
       finish_tile(kt);
     }
     if (P.shared) {   // wave w: query pairs w, w + NW, ... against the last key tile; partial dK, dV summed through LDS
       const int ks = ntk - 1;
-      begin_tile(tn);
-      for (int s = wave; s < npair; s += NW) dkv_pair<HD>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane);
+      begin_tile(ks, tn);
+      for (int s = wave; s < npair; s += NW) dkv_pair<HD, DROP>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane, P, dblk);
       __syncthreads();                                   // every wave is done with the Q / dO images
       float* part = (float*)smem;
       float* mine = part + (wave * 16 + (lane & 15)) * (2 * HD);
@@ -658,14 +730,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const AttnParams 
     }
   } else {
     const bool active = wave < ntk;
-    begin_tile(fetch_tile(wave));
+    begin_tile(wave, fetch_tile(wave));
     for (int j = 0; j < P.ntile; ++j) {
       const int q0 = j * P.tile_rows;
       const int rows = min(P.tile_rows, (P.sq - q0 + 31) & ~31);
       if (j) __syncthreads();
       load_q_tile(q0, rows);
       __syncthreads();
-      if (active) for (int s = 0; s < (rows >> 5); ++s) dkv_pair<HD>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane);
+      if (active) for (int s = 0; s < (rows >> 5); ++s)
+        dkv_pair<HD, DROP>(Qimg, Dimg, Limg, Simg, s, kf, vf, c, dk, dv, lane, P, dblk + (uint64_t)(unsigned)q0 * P.ld4);
     }
     if (active) finish_tile(wave);
   }
@@ -708,19 +781,19 @@ static Plan make_plan(int stationary, int streamed, bool extra_f32, int part_flo
   return p;
 }
 
-template <int HD, int MAXT, int NW, bool FULL>
+template <int HD, int MAXT, int NW, bool FULL, bool DROP>
 static int fwd_launch_k(AttnParams P, int chunk_rows, int nchunk, int ntile, int shared, int batch, hipStream_t st) {
   using C = HeadCfg<HD>;
   P.nchunk = nchunk; P.chunk_rows = chunk_rows; P.tile_rows = MAXT * 16; P.ntile = ntile; P.shared = shared;
   size_t lds = 2 * (size_t)MAXT * 16 * C::RS;
   if (shared) lds = max_sz(lds, (size_t)NW * 16 * (HD + 2) * 4);
-  auto k = attn_fwd_kernel<HD, MAXT, NW, FULL>;
+  auto k = attn_fwd_kernel<HD, MAXT, NW, FULL, DROP>;
   set_max_dynamic_lds((const void*)k, lds);
   hipLaunchKernelGGL(k, dim3(batch * P.nh * nchunk), dim3(NW * 64), lds, st, P);
   return (int)hipGetLastError();
 }
 // forward: the kernel variant is (16-key tiles per K/V tile, waves, mask mode)
-template <int HD>
+template <int HD, bool DROP>
 static int attn_fwd_launch(const AttnParams& P, int batch, hipStream_t st) {
   const int qt = (P.sq + 15) / 16;                 // 16-query tiles per head
   if (P.skv <= 288) {
@@ -730,36 +803,36 @@ static int attn_fwd_launch(const AttnParams& P, int batch, hipStream_t st) {
     const bool big = (whole ? qt : 16) > 6;        // 8 waves when there are q-tiles for them
     const int sh = whole ? use_shared(qt, big ? 8 : 4) : 0;
     switch (nt) {
-      case 2: return big ? fwd_launch_k<HD, 2, 8, false>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 2, 4, false>(P, rows, nchunk, 1, sh, batch, st);
-      case 4: return big ? fwd_launch_k<HD, 4, 8, false>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 4, 4, false>(P, rows, nchunk, 1, sh, batch, st);
-      case 6: return big ? fwd_launch_k<HD, 6, 8, false>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 6, 4, false>(P, rows, nchunk, 1, sh, batch, st);
-      case 16: return fwd_launch_k<HD, 16, 8, false>(P, rows, nchunk, 1, big ? sh : 0, batch, st);
-      case 18: return fwd_launch_k<HD, 18, 8, false>(P, rows, nchunk, 1, big ? sh : 0, batch, st);
-      default: return fwd_launch_k<HD, 16, 8, true>(P, rows, nchunk, 1, big ? sh : 0, batch, st);   // 8..14 tiles: the 16-tile kernel, every tile masked
+      case 2: return big ? fwd_launch_k<HD, 2, 8, false, DROP>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 2, 4, false, DROP>(P, rows, nchunk, 1, sh, batch, st);
+      case 4: return big ? fwd_launch_k<HD, 4, 8, false, DROP>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 4, 4, false, DROP>(P, rows, nchunk, 1, sh, batch, st);
+      case 6: return big ? fwd_launch_k<HD, 6, 8, false, DROP>(P, rows, nchunk, 1, sh, batch, st) : fwd_launch_k<HD, 6, 4, false, DROP>(P, rows, nchunk, 1, sh, batch, st);
+      case 16: return fwd_launch_k<HD, 16, 8, false, DROP>(P, rows, nchunk, 1, big ? sh : 0, batch, st);
+      case 18: return fwd_launch_k<HD, 18, 8, false, DROP>(P, rows, nchunk, 1, big ? sh : 0, batch, st);
+      default: return fwd_launch_k<HD, 16, 8, true, DROP>(P, rows, nchunk, 1, big ? sh : 0, batch, st);   // 8..14 tiles: the 16-tile kernel, every tile masked
     }
   }
   // streamed K/V (256 keys per tile), one q-tile per wave, 128-query chunks
   const int ntile = (P.skv + 255) / 256, nchunk = (P.sq + 127) / 128;
   const int tail = P.skv - (ntile - 1) * 256;      // keys in the last tile
-  if (tail > 224) return fwd_launch_k<HD, 16, 8, false>(P, 128, nchunk, ntile, 0, batch, st);
-  return fwd_launch_k<HD, 16, 8, true>(P, 128, nchunk, ntile, 0, batch, st);
+  if (tail > 224) return fwd_launch_k<HD, 16, 8, false, DROP>(P, 128, nchunk, ntile, 0, batch, st);
+  return fwd_launch_k<HD, 16, 8, true, DROP>(P, 128, nchunk, ntile, 0, batch, st);
 }
 
-template <int HD, int NW>
+template <int HD, int NW, bool DROP>
 static int bwd_launch_dq(const AttnParams& P, const Plan& pl, int items, hipStream_t st) {
-  auto k = attn_bwd_dq_kernel<HD, NW>;
+  auto k = attn_bwd_dq_kernel<HD, NW, DROP>;
   set_max_dynamic_lds((const void*)k, pl.lds);
   hipLaunchKernelGGL(k, dim3(items), dim3(NW * 64), pl.lds, st, P);
   return (int)hipGetLastError();
 }
-template <int HD, int NW>
+template <int HD, int NW, bool DROP>
 static int bwd_launch_dkv(const AttnParams& P, const Plan& pl, int items, hipStream_t st) {
-  auto k = attn_bwd_dkv_kernel<HD, NW>;
+  auto k = attn_bwd_dkv_kernel<HD, NW, DROP>;
   set_max_dynamic_lds((const void*)k, pl.lds);
   hipLaunchKernelGGL(k, dim3(items), dim3(NW * 64), pl.lds, st, P);
   return (int)hipGetLastError();
 }
-template <int HD>
+template <int HD, bool DROP>
 static int attn_bwd_launch(AttnParams P, int batch, hipStream_t st) {
   const Plan plq = make_plan<HD>(P.sq, P.skv, false, HD);       // dQ: queries stationary, keys streamed
   const Plan plk = make_plan<HD>(P.skv, P.sq, true, 2 * HD);    // dK,dV: keys stationary, queries streamed
@@ -768,9 +841,9 @@ static int attn_bwd_launch(AttnParams P, int batch, hipStream_t st) {
   Pk.nchunk = plk.nchunk; Pk.chunk_rows = plk.chunk_rows; Pk.tile_rows = plk.tile_rows; Pk.ntile = plk.ntile; Pk.shared = plk.shared;
   const int iq = batch * P.nh * plq.nchunk, ik = batch * P.nh * plk.nchunk;
   // dQ first: it also produces dsum, which dK,dV consumes
-  const int rc = plq.nw == 4 ? bwd_launch_dq<HD, 4>(Pq, plq, iq, st) : bwd_launch_dq<HD, 8>(Pq, plq, iq, st);
+  const int rc = plq.nw == 4 ? bwd_launch_dq<HD, 4, DROP>(Pq, plq, iq, st) : bwd_launch_dq<HD, 8, DROP>(Pq, plq, iq, st);
   if (rc) return rc;
-  return plk.nw == 4 ? bwd_launch_dkv<HD, 4>(Pk, plk, ik, st) : bwd_launch_dkv<HD, 8>(Pk, plk, ik, st);
+  return plk.nw == 4 ? bwd_launch_dkv<HD, 4, DROP>(Pk, plk, ik, st) : bwd_launch_dkv<HD, 8, DROP>(Pk, plk, ik, st);
 }
 
 static int check_desc(const muse_attn_desc* d) {
@@ -809,29 +882,39 @@ extern "C" int muse_attention_fwd_ex(const muse_attn_desc* d, float* lse, void* 
     if (r2 != 0) return r2 > 0 ? 0 : -r2;
   }
   switch (d->head_dim) {
-    case 16: return attn_fwd_launch<16>(P, d->batch, st);
-    case 32: return attn_fwd_launch<32>(P, d->batch, st);
-    case 48: return attn_fwd_launch<48>(P, d->batch, st);
-    case 64: return attn_fwd_launch<64>(P, d->batch, st);
+    case 16: return attn_fwd_launch<16, false>(P, d->batch, st);
+    case 32: return attn_fwd_launch<32, false>(P, d->batch, st);
+    case 48: return attn_fwd_launch<48, false>(P, d->batch, st);
+    case 64: return attn_fwd_launch<64, false>(P, d->batch, st);
   }
   return MUSE_ERR_UNSUPPORTED;
 }
 
-extern "C" int muse_attention_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse,
-                                     float* dsum, void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk,
-                                     void* dv, int64_t lddv, int64_t bsdv, void* stream) {
+// argument checks and kernel parameters of the backward entry points
+static int bwd_params(AttnParams& P, const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse,
+                      float* dsum, void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk,
+                      void* dv, int64_t lddv, int64_t bsdv) {
   const int rc = check_desc(d);
   if (rc) return rc;
   if ((lddo | bsdo | lddq | bsdq | lddk | bsdk | lddv | bsdv) & 7) return MUSE_ERR_ALIGN;
   if ((((uintptr_t)d_o) | ((uintptr_t)dq) | ((uintptr_t)dk) | ((uintptr_t)dv)) & 7) return MUSE_ERR_ALIGN;
   if ((int64_t)d->seq_q * lddo * 2 >= (1LL << 31)) return MUSE_ERR_UNSUPPORTED;
-  if (d->batch <= 0) return 0;
-  AttnParams P = base_params(d);
+  P = base_params(d);
   P.o = (const bf16_t*)d->o; P.d_o = (const bf16_t*)d_o; P.lddo = lddo; P.bdo = bsdo;
   P.lse = (float*)lse; P.dsum = dsum;
   P.dq = (bf16_t*)dq; P.lddq = lddq; P.bdq = bsdq;
   P.dk = (bf16_t*)dk; P.lddk = lddk; P.bdk = bsdk;
   P.dv = (bf16_t*)dv; P.lddv = lddv; P.bdv = bsdv;
+  return 0;
+}
+
+extern "C" int muse_attention_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse,
+                                     float* dsum, void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk,
+                                     void* dv, int64_t lddv, int64_t bsdv, void* stream) {
+  AttnParams P;
+  const int rc = bwd_params(P, d, d_o, lddo, bsdo, lse, dsum, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv);
+  if (rc) return rc;
+  if (d->batch <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   {   // (the fused backward wants 16-byte aligned gradient rows: its stores are 16 bytes wide)
     const bool al16 = (((uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) == 0;
@@ -839,10 +922,68 @@ extern "C" int muse_attention_bwd_ex(const muse_attn_desc* d, const void* d_o, i
     if (r2 != 0) return r2 > 0 ? 0 : -r2;
   }
   switch (d->head_dim) {
-    case 16: return attn_bwd_launch<16>(P, d->batch, st);
-    case 32: return attn_bwd_launch<32>(P, d->batch, st);
-    case 48: return attn_bwd_launch<48>(P, d->batch, st);
-    case 64: return attn_bwd_launch<64>(P, d->batch, st);
+    case 16: return attn_bwd_launch<16, false>(P, d->batch, st);
+    case 32: return attn_bwd_launch<32, false>(P, d->batch, st);
+    case 48: return attn_bwd_launch<48, false>(P, d->batch, st);
+    case 64: return attn_bwd_launch<64, false>(P, d->batch, st);
+  }
+  return MUSE_ERR_UNSUPPORTED;
+}
+
+// ---- attention dropout inside the kernels (always the kernels of this file: attention2.hip has no dropout form) ---------------
+static void drop_params(AttnParams& P, float p, uint64_t seed, uint64_t offset, int64_t ld_mask) {
+  P.drop_off = offset;
+  P.seed_lo = (unsigned)seed; P.seed_hi = (unsigned)(seed >> 32);
+  P.ld4 = (unsigned)(ld_mask >> 2);
+  // keep iff (r >> 8) * 2^-24 >= p  <=>  r >= ceil(p * 2^24) << 8   (p * 2^24 is exact in double; p <= 1 - 2^-24, so no overflow)
+  const double t = (double)p * 16777216.0;
+  uint64_t T = (uint64_t)t;
+  if ((double)T < t) ++T;
+  P.drop_thr = (unsigned)(T << 8);
+  P.drop_scale = 1.0f / (1.0f - p);
+}
+static int check_drop(const muse_attn_desc* d, float p, int64_t ld_mask) {
+  if (!d || !(p >= 0.0f && p < 1.0f) || (ld_mask & 3) || ld_mask < d->seq_kv || ld_mask >= (1LL << 31)) return MUSE_ERR_BAD_ARG;
+  return 0;
+}
+
+extern "C" int muse_attention_drop_fwd_ex(const muse_attn_desc* d, float* lse, float p, uint64_t seed, uint64_t offset, int64_t ld_mask,
+                                          void* stream) {
+  int rc = check_drop(d, p, ld_mask);
+  if (rc) return rc;
+  if (p == 0.0f) return muse_attention_fwd_ex(d, lse, stream);
+  if ((rc = check_desc(d))) return rc;
+  if (d->batch <= 0) return 0;
+  AttnParams P = base_params(d);
+  P.out = (bf16_t*)d->o; P.lse = lse;
+  drop_params(P, p, seed, offset, ld_mask);
+  hipStream_t st = (hipStream_t)stream;
+  switch (d->head_dim) {
+    case 16: return attn_fwd_launch<16, true>(P, d->batch, st);
+    case 32: return attn_fwd_launch<32, true>(P, d->batch, st);
+    case 48: return attn_fwd_launch<48, true>(P, d->batch, st);
+    case 64: return attn_fwd_launch<64, true>(P, d->batch, st);
+  }
+  return MUSE_ERR_UNSUPPORTED;
+}
+
+extern "C" int muse_attention_drop_bwd_ex(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse,
+                                          float* dsum, void* dq, int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk,
+                                          void* dv, int64_t lddv, int64_t bsdv, float p, uint64_t seed, uint64_t offset,
+                                          int64_t ld_mask, void* stream) {
+  int rc = check_drop(d, p, ld_mask);
+  if (rc) return rc;
+  if (p == 0.0f) return muse_attention_bwd_ex(d, d_o, lddo, bsdo, lse, dsum, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv, stream);
+  AttnParams P;
+  if ((rc = bwd_params(P, d, d_o, lddo, bsdo, lse, dsum, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv))) return rc;
+  if (d->batch <= 0) return 0;
+  drop_params(P, p, seed, offset, ld_mask);
+  hipStream_t st = (hipStream_t)stream;
+  switch (d->head_dim) {
+    case 16: return attn_bwd_launch<16, true>(P, d->batch, st);
+    case 32: return attn_bwd_launch<32, true>(P, d->batch, st);
+    case 48: return attn_bwd_launch<48, true>(P, d->batch, st);
+    case 64: return attn_bwd_launch<64, true>(P, d->batch, st);
   }
   return MUSE_ERR_UNSUPPORTED;
 }

@@ -19,6 +19,11 @@ struct AttnParams {
   int tile_rows, ntile;                    // streamed rows per LDS tile (multiple of 32), number of tiles
   int shared;                              // 1: the workgroup's last stationary tile is split over all waves (see below)
   float alpha;
+  // attention dropout (read by the DROP instantiations of attention.hip only): keep bit of (bh, q, k) = word e & 3 of Philox block
+  // drop_off + (e >> 2), e = (bh * sq + q) * 4 * ld4 + k, key (seed_lo, seed_hi); kept iff word >= drop_thr; kept values * drop_scale
+  unsigned long long drop_off;
+  unsigned seed_lo, seed_hi, drop_thr, ld4;
+  float drop_scale;
 };
 
 // attention2.hip: 1 = launched, 0 = shape not taken (the caller runs the general kernels), < 0 = launch error

@@ -1,0 +1,20 @@
+// Philox4x32-10 (counter-based; Salmon et al. 2011) and the two uniform conversions of the library's random streams: shared by
+// sampling.hip (muse_sample_step's draws, muse_dropout's keep masks) and attention.hip (the same keep masks, drawn in the kernel).
+#pragma once
+#include <stdint.h>
+
+struct u4 { uint32_t x, y, z, w; };
+__device__ __forceinline__ u4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return u4{c0, c1, c2, c3};
+}
+__device__ __forceinline__ float u01_open_low(uint32_t r) { return ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f); }   // (0, 1]
+__device__ __forceinline__ float u01_open_high(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }            // [0, 1)
+
+#define MUSE_DROPOUT_TAG 0x6D757365u   // counter word 2 of the dropout stream (word 3 is 0)

@@ -8,23 +8,9 @@
 // All are latency-class kernels (a few MB at most); the point is one launch instead of ~10 ATen launches per decoding step and
 // bit-exact agreement with the reference when the random draws are supplied by the caller.
 #include "common.h"
+#include "philox.h"   // Philox4x32-10, used when the caller supplies no random draws
 #include "../../include/muse_hip.h"
 #include <float.h>
-
-// ---- Philox4x32-10 (counter-based; Salmon et al. 2011), used when the caller supplies no random draws -------------------
-struct u4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ u4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return u4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ float u01_open_low(uint32_t r) { return ((float)(r >> 8) + 1.0f) * (1.0f / 16777216.0f); }   // (0, 1]
-__device__ __forceinline__ float u01_open_high(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }            // [0, 1)
 
 __device__ __forceinline__ float clamp_log(float t) { return logf(fmaxf(t, 1e-20f)); }   // muse/sampling.py:9-10
 
@@ -255,7 +241,7 @@ __global__ void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long 
   const long n4 = (n + 3) >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const uint64_t c = offset + (uint64_t)i;
-    const u4 r = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), 0x6D757365u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const u4 r = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), MUSE_DROPOUT_TAG, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

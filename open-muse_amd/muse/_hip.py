@@ -69,6 +69,9 @@ SIGNATURES = {
     "muse_attention_fwd_ex": [C.POINTER(AttnDesc), c_void_p, c_void_p],
     "muse_attention_bwd_ex": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                               c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p],
+    "muse_attention_drop_fwd_ex": [C.POINTER(AttnDesc), c_void_p, c_float, C.c_uint64, C.c_uint64, c_i64, c_void_p],
+    "muse_attention_drop_bwd_ex": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+                                   c_i64, c_i64, c_void_p, c_i64, c_i64, c_float, C.c_uint64, C.c_uint64, c_i64, c_void_p],
     "muse_attention_x3_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_bwd": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
                               c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, *_IMG, c_void_p],

@@ -477,7 +477,8 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
         x = ops.embed_fwd(ids, self.embed.word_embeddings.weight.data, self.embed.position_embeddings.weight.data)
         # nn.Dropout sites of the reference (training mode only): embeddings :956, attention probabilities :237, feed-forward
         # :797.  Masks are Philox streams (seed drawn per forward from torch's CPU generator, one offset range per site); the
-        # backward regenerates them.  Attention dropout needs the probabilities, so it runs on the materialised path.
+        # backward regenerates them.  Attention dropout: bf16 mode draws the masks inside the fused attention kernels (the bits the
+        # materialised route draws for its [B*nh, S, Sp] probabilities; MUSE_ATTN_DROPOUT_FUSED=0 takes that route), f32 mode materialises.
         pd_h = float(self.hidden_dropout) if self.training else 0.0
         pd_a = float(self.attention_dropout) if self.training else 0.0
         seed = int(torch.randint(0, 2 ** 62, (1,))) if (pd_h > 0.0 or pd_a > 0.0) else 0
@@ -485,7 +486,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
         site = lambda li, k: ((li * 2 + k + 1) << 40)   # noqa: E731  (k = 0 attention, 1 feed-forward; 0 = embeddings)
         if pd_h > 0.0:
             ops.dropout(x, pd_h, seed, 0, out=x)
-        fused = self.fused_attention and ops.attention_supported(cd, S, hd) and pd_a == 0.0
+        fused = self.fused_attention and ops.attention_supported(cd, S, hd) and (pd_a == 0.0 or ops.attention_dropout_fused())
         saved = {"layers": [], "cd": cd, "ids": ids, "B": B, "S": S, "Sp": Sp, "fused": fused, "drop": (seed, pd_h, pd_a)} if need_grad else None
 
         for li in range(self.num_hidden_layers):
@@ -501,7 +502,10 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
 
             ln1, mu1, rs1 = ops.layernorm_fwd(x, w_ln1, eps, cd)
             qkv = ops.linear(ln1, w_qkv)
-            if fused:
+            if fused and pd_a > 0.0:   # the same with the dropout of :237 drawn in the kernel
+                ctx, P = ops.attention_drop_fwd_ex(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, S, S, nh, hd, alpha,
+                                                   pd_a, seed, site(li, 0), Sp)
+            elif fused:
                 # softmax(alpha Q K^T) V in one kernel, S x S never leaves the CU (reference :206-210 / :226-240)
                 ctx, P = ops.attention_fwd(qkv, B, S, nh, hd, alpha)   # P := row log-sum-exp
             else:
@@ -720,7 +724,12 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
             dctx = dgrad(dao, w_out, b0 + 4)
             qkv, P = s["qkv"], s["P"]
             if sv["fused"]:
-                dqkv = ops.attention_bwd(qkv, s["ctx"], dctx, P, B, S, nh, hd, alpha)
+                if pd_a > 0.0:
+                    dqkv = torch.empty_like(qkv)
+                    ops.attention_drop_bwd_ex(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], s["ctx"], dctx, P, B, S, S, nh, hd, alpha,
+                                              pd_a, seed, site(li, 0), Sp, dq=dqkv[:, :H], dk=dqkv[:, H:2 * H], dv=dqkv[:, 2 * H:])
+                else:
+                    dqkv = ops.attention_bwd(qkv, s["ctx"], dctx, P, B, S, nh, hd, alpha)
                 wgrad(dqkv, s["ln1"], view(GW, b0 + 1, (3 * H, H)), acc[b0 + 1])
                 dln1 = dgrad(dqkv, w_qkv, b0 + 1)
                 dx = ops.layernorm_bwd(dln1, s["x"], w_ln1, s["mu1"], s["rs1"], torch.float32, view(GW, b0 + 0, (H,)),

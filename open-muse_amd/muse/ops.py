@@ -1101,7 +1101,12 @@ def _attn_desc(q, k, v, o, B, Sq, Skv, nh, hd, alpha):
     return d
 
 
-def attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, out=None):
+def _drop_args(drop):
+    p, seed, offset, ld_mask = drop
+    return float(p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(ld_mask)
+
+
+def attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, out=None, drop=None):
     """fused softmax(alpha q k^T) v for separate q [B*Sq, H], k / v [B*Skv, H] views (row strides free: slices of a packed
     projection are fine); -> (ctx [B*Sq, H] bf16, lse [B*nh, seq_pad(Sq)] f32).  Self- and cross-attention."""
     require_gpu(q, k, v)
@@ -1110,12 +1115,15 @@ def attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, out=None):
     lse = torch.empty((B * nh, lib().muse_attention_seq_pad(Sq)), dtype=torch.float32, device=q.device)
     d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
     e0 = _prof_begin()
-    check(lib().muse_attention_fwd_ex(C.byref(d), lse.data_ptr(), stream()), "muse_attention_fwd_ex")
+    if drop is None:
+        check(lib().muse_attention_fwd_ex(C.byref(d), lse.data_ptr(), stream()), "muse_attention_fwd_ex")
+    else:   # (attention_drop_fwd_ex)
+        check(lib().muse_attention_drop_fwd_ex(C.byref(d), lse.data_ptr(), *_drop_args(drop), stream()), "muse_attention_drop_fwd_ex")
     _prof_end(e0, "attn_fwd_bf16", 4.0 * B * nh * Sq * Skv * hd)
     return ctx, lse
 
 
-def attention_bwd_ex(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None, dk=None, dv=None):
+def attention_bwd_ex(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None, dk=None, dv=None, drop=None):
     """-> (dq [B*Sq, H], dk, dv [B*Skv, H]) bf16; dq / dk / dv may be views (e.g. the three column blocks of a packed gradient)"""
     require_gpu(q, k, v, ctx, dctx, lse)
     H = nh * hd
@@ -1126,10 +1134,33 @@ def attention_bwd_ex(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None
     d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
     (pdo, lddo), (pdq, lddq), (pdk, lddk), (pdv, lddv) = _row_view(dctx, H), _row_view(dq, H), _row_view(dk, H), _row_view(dv, H)
     e0 = _prof_begin()
-    check(lib().muse_attention_bwd_ex(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), dsum.data_ptr(), pdq, lddq, Sq * lddq,
-                                      pdk, lddk, Skv * lddk, pdv, lddv, Skv * lddv, stream()), "muse_attention_bwd_ex")
+    if drop is None:
+        check(lib().muse_attention_bwd_ex(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), dsum.data_ptr(), pdq, lddq, Sq * lddq,
+                                          pdk, lddk, Skv * lddk, pdv, lddv, Skv * lddv, stream()), "muse_attention_bwd_ex")
+    else:   # (attention_drop_bwd_ex)
+        check(lib().muse_attention_drop_bwd_ex(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), dsum.data_ptr(), pdq, lddq, Sq * lddq,
+                                               pdk, lddk, Skv * lddk, pdv, lddv, Skv * lddv, *_drop_args(drop), stream()),
+              "muse_attention_drop_bwd_ex")
     _prof_end(e0, "attn_bwd_bf16", 10.0 * B * nh * Sq * Skv * hd)
     return dq, dk, dv
+
+
+def attention_dropout_fused():
+    """MUSE_ATTN_DROPOUT_FUSED=0 (read per call, like MUSE_ATTN2): attention dropout on the materialised route (scores, softmax_,
+    dropout, P V as four launches with P and the dropped P kept for the backward) instead of inside the fused kernels"""
+    return os.environ.get("MUSE_ATTN_DROPOUT_FUSED", "1") != "0"
+
+
+def attention_drop_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, p, seed, offset, ld_mask, out=None):
+    """attention_fwd_ex with nn.Dropout(p) on the probabilities inside the kernel: element (bh, q, k) is kept iff muse_dropout(seed, offset)
+    keeps flat element (bh * Sq + q) * ld_mask + k (ld_mask: multiple of 4, >= Skv; the materialised route's row pitch round_up(Skv, 8)
+    reproduces its masks).  lse is that of the undropped softmax.  -> (ctx, lse)"""
+    return attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, out=out, drop=(p, seed, offset, ld_mask))
+
+
+def attention_drop_bwd_ex(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, p, seed, offset, ld_mask, dq=None, dk=None, dv=None):
+    """backward of attention_drop_fwd_ex (same p, seed, offset, ld_mask: the masks are drawn again) -> (dq, dk, dv) as attention_bwd_ex"""
+    return attention_bwd_ex(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=dq, dk=dk, dv=dv, drop=(p, seed, offset, ld_mask))
 
 
 X3_STREAM = os.environ.get("MUSE_X3_STREAM", "1") != "0"   # sequences of several 256-key blocks: the streaming kernels (0: block pairs + merge)

@@ -411,16 +411,17 @@ class TapeOps:
         return dv
 
     def _attention(self, x, ctx, att, B, Sq, Skv, nh, residual=None, drop=None):
-        """`drop` = (p, seed, offset): nn.Dropout on the attention probabilities (training mode of models with attention_dropout > 0;
-        needs the probabilities, so it runs on the materialised path whatever the compute dtype).
+        """`drop` = (p, seed, offset): nn.Dropout on the attention probabilities (training mode of models with attention_dropout > 0):
+        drawn inside the fused kernels in bf16 mode (the bits of the materialised [B*nh, Sq, Sp] route, which MUSE_ATTN_DROPOUT_FUSED=0
+        and the other modes take).
         reference Attention :834-915.  bf16 compute mode: fused attention kernel (S x S never materialised; self- and
         cross-attention) on a packed q|k|v (self) or k|v (cross) projection.  f32 parity mode: the reference's algorithm
         materialised: scores = alpha q k^T (batched per head), softmax, P v, out projection."""
         Cq = x.shape[1]
         hd = Cq // nh
         pdrop = drop[0] if drop is not None else 0.0
-        if (self.compute_dtype == torch.bfloat16 and ops.attention_supported(torch.bfloat16, Sq, hd, Skv) and pdrop == 0.0
-                and att.key.weight.shape[1] % 8 == 0):
+        if (self.compute_dtype == torch.bfloat16 and ops.attention_supported(torch.bfloat16, Sq, hd, Skv)
+                and (pdrop == 0.0 or ops.attention_dropout_fused()) and att.key.weight.shape[1] % 8 == 0):
             alpha = 1.0 / float(torch.sqrt(torch.tensor(hd, dtype=torch.float32)))
             xb = self._c(x)                   # (already bf16 when it is an AdaLN output; cached otherwise)
             self_attn = ctx is x
@@ -432,9 +433,10 @@ class TapeOps:
                 q = ops.linear(xb, self._wb(att.query), bias=self._b(att.query))
                 qkv = ops.linear(cb, self._wb(att.key, att.value), bias=self._b(att.key, att.value))   # [B*Skv, 2C] bf16
                 k, v = qkv[:, :Cq], qkv[:, Cq:]
-            o, lse = ops.attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha)
+            fdrop = (*drop, (Skv + 7) // 8 * 8) if pdrop > 0.0 else None      # + the materialised route's row pitch
+            o, lse = ops.attention_fwd_ex(q, k, v, B, Sq, Skv, nh, hd, alpha, drop=fdrop)
             y = ops.linear(o, self._wb(att.out), out_dtype=torch.float32, residual=residual, bias=self._b(att.out))
-            return y, dict(fused=True, self_attn=self_attn, xb=xb, cb=cb, q=q, qkv=qkv, o=o, lse=lse,
+            return y, dict(fused=True, self_attn=self_attn, xb=xb, cb=cb, q=q, qkv=qkv, o=o, lse=lse, drop=fdrop,
                            dims=(B, Sq, Skv, nh, hd, Cq, alpha))
         if ((self.__dict__.get("_f32_split3", False) or self.__dict__.get("_f32_f16", False)) and _X3_ATTENTION and pdrop == 0.0
                 and ops.attention_x3_supported(Sq, Skv, hd)
@@ -579,7 +581,7 @@ class TapeOps:
             k, v = qkv[:, Cq:2 * Cq], qkv[:, 2 * Cq:]
             dqkv = torch.empty_like(qkv)
             ops.attention_bwd_ex(q, k, v, sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, dq=dqkv[:, :Cq], dk=dqkv[:, Cq:2 * Cq],
-                                 dv=dqkv[:, 2 * Cq:])
+                                 dv=dqkv[:, 2 * Cq:], drop=sv["drop"])
             gqkv = self._mm_dw(dqkv, sv["xb"], (3 * Cq, Cq))
             G[name + ".query.weight"], G[name + ".key.weight"], G[name + ".value.weight"] = gqkv[:Cq], gqkv[Cq:2 * Cq], gqkv[2 * Cq:]
             if ub:
@@ -591,7 +593,7 @@ class TapeOps:
         k, v = qkv[:, :Cq], qkv[:, Cq:]
         dq = torch.empty_like(q)
         dkv = torch.empty_like(qkv)
-        ops.attention_bwd_ex(q, k, v, sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, dq=dq, dk=dkv[:, :Cq], dv=dkv[:, Cq:])
+        ops.attention_bwd_ex(q, k, v, sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, dq=dq, dk=dkv[:, :Cq], dv=dkv[:, Cq:], drop=sv["drop"])
         G[name + ".query.weight"] = self._mm_dw(dq, sv["xb"], att.query.weight.shape)
         Ck = att.key.weight.shape[1]
         gkv = self._mm_dw(dkv, sv["cb"], (2 * Cq, Ck))
