@@ -367,6 +367,42 @@ int muse_adamw_flat_groups_dev(float* p, const float* g, float* m, float* v, voi
 int muse_adamw_multi_groups_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
                                 const float* group_hyper, int32_t ngroups, int32_t step, const float* scale_dev, const int32_t* skip,
                                 void* stream);
+/* Lion (the reference's `lion` optimizer choice, training/optimizer.py:57-79) in AdamW's eight forms: the same kernels instantiated with
+ * another update rule, so tables (6 / 7 columns; column 3, AdamW's v, is ignored and may be 0), chunk_first, segments, images, `skip`,
+ * `scale_dev` and the error codes are exactly those of the muse_adamw_* entry point of the same name.  There is no eps, no step count and
+ * no second moment: the state is m alone (20 B of traffic per parameter against AdamW's 28).
+ * Hyper-parameters are DOUBLE and travel as HOST rows of {lr, beta1, beta2, weight_decay}, read during the call (`hyper`: one row;
+ * `group_hyper`: ngroups <= 8 rows; NULL: MUSE_ERR_BAD_ARG): each constant is computed in double from the Python floats and rounded
+ * ONCE to f32 -
+ *   decay = f32(1 - lr * wd)   b1 = f32(beta1)   omb1 = f32(1 - beta1)   b2 = f32(beta2)   omb2 = f32(1 - beta2)   nlr = f32(-lr)
+ * - and the update of one element is pinned at lion_update1 of csrc/optim.hip (contraction off, every operator rounds to f32, fma is
+ * one rounding, f32 denormals kept; s = grad_scale or *scale_dev):
+ *   gr = round(g * s)                       s == 1 leaves g's bits
+ *   p1 = round(p * decay)                   p.data.mul_(1 - lr * wd): the decayed parameter is rounded on its own
+ *   u  = round(round(m * b1) + round(gr * omb1))
+ *   p' = round(p1 + nlr * sign(u))          sign: +1, -1, 0 for u == +-0 (p' then has p1's bits, also for p1 == -0.0), NaN for NaN
+ *   m' = fma(omb2, gr, round(m * b2))       exp_avg.mul_(beta2).add_(grad, alpha=1 - beta2)
+ * u uses the OLD m; m' does not reuse round(m * b1).  On the CPU this is the reference class bit for bit (tests/golden/lion_steps.npz).
+ * A one-group grouped call is bit-identical to the single-set call.  A *_dev call is bit-identical to muse_grad_scale_* followed by the
+ * host-factor call with grad_scale 1. */
+int muse_lion_flat(float* p, const float* g, float* m, void* p_bf16, int64_t n, const double* hyper, float grad_scale,
+                   const int32_t* skip, void* stream);
+int muse_lion_flat_dev(float* p, const float* g, float* m, void* p_bf16, int64_t n, const double* hyper, const float* scale_dev,
+                       const int32_t* skip, void* stream);
+int muse_lion_flat_groups(float* p, const float* g, float* m, void* p_bf16, int64_t n, int64_t base, const int64_t* seg_end,
+                          const int32_t* seg_group, int32_t nseg, const double* group_hyper, int32_t ngroups, float grad_scale,
+                          const int32_t* skip, void* stream);
+int muse_lion_flat_groups_dev(float* p, const float* g, float* m, void* p_bf16, int64_t n, int64_t base, const int64_t* seg_end,
+                              const int32_t* seg_group, int32_t nseg, const double* group_hyper, int32_t ngroups,
+                              const float* scale_dev, const int32_t* skip, void* stream);
+int muse_lion_multi(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, const double* hyper,
+                    float grad_scale, const int32_t* skip, void* stream);
+int muse_lion_multi_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks, const double* hyper,
+                        const float* scale_dev, const int32_t* skip, void* stream);
+int muse_lion_multi_groups(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                           const double* group_hyper, int32_t ngroups, float grad_scale, const int32_t* skip, void* stream);
+int muse_lion_multi_groups_dev(const int64_t* table, const int32_t* chunk_first, int32_t num_tensors, int32_t num_chunks,
+                               const double* group_hyper, int32_t ngroups, const float* scale_dev, const int32_t* skip, void* stream);
 /* out[i] (+)= sum over s < nslices of ws[s*stride + i]: reduction of split-K partial results (n, stride % 4 == 0) */
 int muse_sum_slices(const float* ws, float* out, int32_t nslices, int64_t n, int64_t stride, int32_t accumulate, void* stream);
 /* njobs <= 16 reductions in ONE launch, each bit-identical to the single-job kernel it stands for: kind 0 = muse_sum_slices

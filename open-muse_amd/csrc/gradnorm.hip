@@ -11,7 +11,7 @@
 #include "../../include/muse_hip.h"
 #include <math.h>
 
-#define GN_CHUNK 4096   // the chunk of adamw_multi_kernel (OPT_CHUNK of optim.hip): FusedAdamW's chunk_first table serves both
+#define GN_CHUNK 4096   // the chunk of opt_multi_kernel (OPT_CHUNK of optim.hip): FusedAdamW's chunk_first table serves both
 
 // Sum of squares of g[0, cnt), cnt <= GN_CHUNK, by one workgroup of 256 -> *out.  Element i belongs to lane (i / 4) % 256, slot i % 4,
 // whether it is read by a 16-byte load or (unaligned start, ragged end) alone: the partial is a function of the values only.

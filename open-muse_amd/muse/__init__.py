@@ -26,8 +26,8 @@ from .pipeline_muse import PipelineMuse, PipelineMuseInpainting
 from .sampling import get_mask_chedule
 from .unbuilt import MOVQ, PaellaVQModel
 from . import lr_schedulers, training_utils
-from .training import (FusedAdamW, GradReducer, TrainStep, clip_grad_norm_, cond_dropout, grad_norms, grouped_parameters,
+from .training import (FusedAdamW, FusedLion, GradReducer, TrainStep, clip_grad_norm_, cond_dropout, grad_norms, grouped_parameters,
                        mask_or_random_replace_tokens, prepare_inputs_and_labels)
 
-__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "CLIPTextEncoder", "CLIPImageEncoder", "CLIPScorer", "clip_scores", "T5TextEncoder", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "GradReducer", "clip_grad_norm_", "grad_norms",
+__all__ = ["MOVQ", "PaellaVQModel", "EMAModel", "CLIPTextEncoder", "CLIPImageEncoder", "CLIPScorer", "clip_scores", "T5TextEncoder", "MaskGitVQGAN", "VQGANModel", "MaskGitTransformer", "MaskGiTUViT", "MaskGiTUViT_v2", "PipelineMuse", "PipelineMuseInpainting", "get_mask_chedule", "FusedAdamW", "FusedLion", "GradReducer", "clip_grad_norm_", "grad_norms",
            "TrainStep", "prepare_inputs_and_labels", "mask_or_random_replace_tokens", "cond_dropout", "grouped_parameters"]

@@ -127,6 +127,16 @@ SIGNATURES = {
     "muse_adamw_flat_groups_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_void_p, c_void_p],
     "muse_adamw_multi_groups_dev": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "muse_lion_flat": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_void_p, c_void_p],
+    "muse_lion_flat_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+    "muse_lion_flat_groups": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float,
+                              c_void_p, c_void_p],
+    "muse_lion_flat_groups_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p],
+    "muse_lion_multi": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p],
+    "muse_lion_multi_dev": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "muse_lion_multi_groups": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p],
+    "muse_lion_multi_groups_dev": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "muse_gemm_group_ok": [c_void_p, c_int, c_int],
     "muse_gemm_group": [c_void_p, c_int, c_int, c_void_p],
     "muse_sum_multi": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],

@@ -1615,12 +1615,14 @@ def soft_ce_bwd(logits, labels, soft, seq1, lse, psum, loss_out, grad_out, out_d
 # scale_dev (every adamw_*): None, or a device f32 (gradnorm_finalize's `scale`) the kernel multiplies the gradient by INSTEAD of
 # grad_scale (the muse_adamw_*_dev entry points: gradient clipping without a host round trip)
 def _adamw_call(name, args, grad_scale, skip, scale_dev, prof=None):
-    """muse_<name> (the host's grad_scale) or muse_<name>_dev (scale_dev); prof: the parameter tensor and its bf16 copy, to report to the profiler"""
+    """muse_<name> (the host's grad_scale) or muse_<name>_dev (scale_dev), AdamW and Lion alike; prof: the parameter tensor and its bf16
+    copy, to report to the profiler (28 B per element of state traffic for adamw_*, 20 B for lion_*)"""
+    what, per = ("lion", 20.0) if name.startswith("lion") else ("adamw", 28.0)
     name = "muse_" + name + ("_dev" if scale_dev is not None else "")
     e0 = _prof_begin() if prof else None
     check(getattr(lib(), name)(*args, float(grad_scale) if scale_dev is None else scale_dev.data_ptr(), ptr(skip), stream()), name)
     if prof:
-        _prof_end(e0, "adamw", 28.0 * prof[0].numel() + (2.0 * prof[0].numel() if prof[1] is not None else 0.0), "byte")
+        _prof_end(e0, what, per * prof[0].numel() + (2.0 * prof[0].numel() if prof[1] is not None else 0.0), "byte")
 
 
 def adamw_flat(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, skip=None, scale_dev=None):
@@ -1674,6 +1676,61 @@ def adamw_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, step
     hy = _group_hyper(groups)
     _adamw_call("adamw_multi_groups", (table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
                                        ctypes.cast(hy, ctypes.c_void_p), len(groups), int(step)), grad_scale, skip, scale_dev)
+
+
+# Lion (training/optimizer.py of the reference; muse_lion_*): the adamw_* forms without eps, step and v.  grad_scale, skip and scale_dev as
+# above.  The hyper-parameters go down as DOUBLE rows {lr, beta1, beta2, weight_decay}: the kernel's constants are rounded once, from the
+# Python floats (f32(1 - lr * wd) is not computable from an f32 lr).
+def _lion_hyper(groups):
+    """host array of {lr, beta1, beta2, weight_decay} double rows for muse_lion_* (kept alive by the caller for the call)"""
+    import ctypes
+    if not 1 <= len(groups) <= 8:
+        raise _hip.MuseHipError(f"FusedLion: 1..8 parameter groups are supported, got {len(groups)}")
+    flat = []
+    for g in groups:
+        flat += [float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["weight_decay"])]
+    return (ctypes.c_double * len(flat))(*flat)
+
+
+def _lion_row(lr, beta1, beta2, weight_decay):
+    return _lion_hyper([dict(lr=lr, betas=(beta1, beta2), weight_decay=weight_decay)])
+
+
+def lion_flat(p, g, m, p_bf16, lr, beta1, beta2, weight_decay, grad_scale=1.0, skip=None, scale_dev=None):
+    require_gpu(p, g, m, scale_dev)
+    import ctypes
+    hy = _lion_row(lr, beta1, beta2, weight_decay)
+    _adamw_call("lion_flat", (p.data_ptr(), g.data_ptr(), m.data_ptr(), ptr(p_bf16), p.numel(), ctypes.cast(hy, ctypes.c_void_p)),
+                grad_scale, skip, scale_dev, prof=(p, p_bf16))
+
+
+def lion_multi(table, chunk_first, num_tensors, num_chunks, lr, beta1, beta2, weight_decay, grad_scale=1.0, skip=None, scale_dev=None):
+    """one Lion launch over a device-side table of tensors (muse_lion_multi: adamw_multi's 6-column table, column 3 ignored)"""
+    require_gpu(table, chunk_first, scale_dev)
+    import ctypes
+    hy = _lion_row(lr, beta1, beta2, weight_decay)
+    _adamw_call("lion_multi", (table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks), ctypes.cast(hy, ctypes.c_void_p)),
+                grad_scale, skip, scale_dev)
+
+
+def lion_flat_groups(p, g, m, p_bf16, base, seg_end, seg_group, groups, grad_scale=1.0, skip=None, scale_dev=None):
+    """Lion on elements [base, base + p.numel()) of a flat buffer cut into parameter-group segments (muse_lion_flat_groups; arguments as for
+    adamw_flat_groups)"""
+    require_gpu(p, g, m, seg_end, seg_group, scale_dev)
+    import ctypes
+    hy = _lion_hyper(groups)
+    _adamw_call("lion_flat_groups", (p.data_ptr(), g.data_ptr(), m.data_ptr(), ptr(p_bf16), p.numel(), int(base), seg_end.data_ptr(),
+                                     seg_group.data_ptr(), int(seg_end.numel()), ctypes.cast(hy, ctypes.c_void_p), len(groups)),
+                grad_scale, skip, scale_dev, prof=(p, p_bf16))
+
+
+def lion_multi_groups(table, chunk_first, num_tensors, num_chunks, groups, grad_scale=1.0, skip=None, scale_dev=None):
+    """muse_lion_multi with a group column in the table (7 x int64 per tensor, as for adamw_multi_groups)"""
+    require_gpu(table, chunk_first, scale_dev)
+    import ctypes
+    hy = _lion_hyper(groups)
+    _adamw_call("lion_multi_groups", (table.data_ptr(), chunk_first.data_ptr(), int(num_tensors), int(num_chunks),
+                                      ctypes.cast(hy, ctypes.c_void_p), len(groups)), grad_scale, skip, scale_dev)
 
 
 # ---- gradient clipping by global L2 norm / per-parameter gradient norms (csrc/gradnorm.hip; training.GradNorm drives these) -------------

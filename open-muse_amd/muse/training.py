@@ -3,6 +3,8 @@
   * prepare_inputs_and_labels  — training/train_maskgit_imagenet.py:357-394 (VQ encode + cosine-schedule mask sampling)
   * FusedAdamW                 — the `fused_adamw` optimizer choice (:242-261, apex FusedAdam adam_w_mode), one HIP
                                  launch over the model's flat parameter buffer
+  * FusedLion                  — the `lion` optimizer choice (training/train_muse.py:405-424, training/optimizer.py): the same
+                                 machinery and kernels with Lion's update rule
   * GradReducer                — replaces accelerate/DDP (:152-158, :305, :433): bucketed all-reduce of the flat
                                  gradient buffer over RCCL (xGMI) on a side stream, overlapped with backward
   * TrainStep                  — the loop body (:405-452) strung together for benchmarks / smoke tests
@@ -166,7 +168,7 @@ def cond_dropout(encoder_hidden_states, clip_embeds, empty_embeds, empty_clip_em
     return enc.to(encoder_hidden_states.dtype), cond.to(clip_embeds.dtype)
 
 
-def _owner_of(params):
+def _owner_of(params, who="FusedAdamW"):
     """the muse.MaskGitTransformer that owns all `params` in its flat buffer, or None when the parameters are ordinary tensors
     (muse.MaskGiTUViT): those are stepped one launch per tensor with the same kernel"""
     owner = None
@@ -176,11 +178,11 @@ def _owner_of(params):
         ref = getattr(p, "_muse_owner", None)
         m = ref() if ref is not None else None
         if m is None:
-            raise MuseHipError("FusedAdamW: either all or none of the parameters may live in a flat parameter buffer")
+            raise MuseHipError(f"{who}: either all or none of the parameters may live in a flat parameter buffer")
         if owner is None:
             owner = m
         elif owner is not m:
-            raise MuseHipError("FusedAdamW: parameters of several models in one optimizer are not supported")
+            raise MuseHipError(f"{who}: parameters of several models in one optimizer are not supported")
     return owner
 
 
@@ -343,40 +345,31 @@ def named_grad_norms(model):
     return [names[id(p)] for p in params], out[3:]
 
 
-class FusedAdamW(torch.optim.Optimizer):
-    """AdamW (decoupled weight decay, torch.optim.AdamW numerics) as ONE kernel launch over the model's flat f32
-    parameter / gradient buffers; also refreshes the bf16 compute copy of the weights in the same pass.
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What muse.FusedAdamW and muse.FusedLion share - everything but the update rule: ownership of a model's flat buffers and its
+    parameter-group segments, the per-tensor pointer table, stepping inside backward / behind the reducer's buckets, clipping by the
+    global norm read on the device, the "f16" overflow guard and the refresh of the weights' operand images.  A rule supplies its
+    constructor (param_groups defaults, then `_init_fused`), `_who` (its name in messages), the state tensors (`_tensor_state`,
+    `_ensure_flat_state`), the launches (`_launch_flat`, `_launch_multi`) and `state_dict` / `load_state_dict`."""
+    _who = "FusedOptimizer"
+    _rule = "the update"
+    _subset_hint = "torch.optim.AdamW"     # what the "whole flat buffer" message recommends for a subset of the parameters
 
-    Drop-in for `optimizer_cls(model.parameters(), lr=..., betas=..., weight_decay=..., eps=...)`.  `state_dict()` /
-    `load_state_dict()` use torch.optim.AdamW's layout ({"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups"}),
-    so optimizer checkpoints written by the reference's `adamw` choice load here and vice versa.
-
-    `max_grad_norm` (also an attribute; None = off): clip the gradient by its global L2 norm inside the step - the semantics of
-    `accelerator.clip_grad_norm_(model.parameters(), max_grad_norm)` right before `optimizer.step()` (training/train_muse.py:758-761):
-    step() = norm kernels (for whatever begin_norm_in_backward / begin_norm_in_reducer have not already delivered) -> one finalize
-    launch -> ONE AdamW launch that reads `grad_scale * min(1, max_grad_norm / (norm + 1e-6))` from device memory.  No device-to-host
-    copy, no stream synchronisation.  `p.grad` is left UNSCALED (that write pass is what is saved): code that reads the gradients
-    after step() sees the unclipped ones - use muse.clip_grad_norm_ where the clipped gradient itself is needed.  After the step
-    `last_grad_norm` (the norm before clipping, of the gradient times `grad_scale`) and `last_clip_coef` are 0-dim device tensors.
-    It is not a param_groups default and does not enter state_dict(): checkpoints keep torch.optim.AdamW's layout."""
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
-        params = list(params)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def _init_fused(self, max_grad_norm):
         # Parameter groups: `params` may be the list of dicts training/train_muse.py:425-445 builds (weight decay on the matrices,
         # none on bias / LayerNorm / embedding weights) - torch.optim semantics, every group its own lr / betas / eps / weight_decay.
         # One group runs the single-set kernels (muse_adamw_flat / _multi); several run the *_groups kernels, still ONE launch.
         if len(self.param_groups) > 8:
-            raise MuseHipError(f"FusedAdamW: at most 8 parameter groups (got {len(self.param_groups)})")
+            raise MuseHipError(f"{self._who}: at most 8 parameter groups (got {len(self.param_groups)})")
         every = self._all_params()
-        owner = _owner_of(every)
+        owner = _owner_of(every, self._who)
         self._model = weakref.ref(owner) if owner is not None else None
         self._flat_gid = self._seg_dev = None
         if owner is not None:
             theirs = owner._param_order()
             if len(every) != len(theirs) or {id(q) for q in every} != {id(q) for q in theirs}:
-                raise MuseHipError("FusedAdamW steps the model's whole flat parameter buffer: pass model.parameters() "
-                                   "(all of them, as one list or split into groups); for a subset use torch.optim.AdamW")
+                raise MuseHipError(f"{self._who} steps the model's whole flat parameter buffer: pass model.parameters() "
+                                   f"(all of them, as one list or split into groups); for a subset use {self._subset_hint}")
             gid = {id(q): k for k, grp in enumerate(self.param_groups) for q in grp["params"]}
             self._flat_gid = [gid[id(q)] for q in theirs]           # group of each parameter, in the flat buffer's order
         self._m = self._v = None
@@ -420,17 +413,17 @@ class FusedAdamW(torch.optim.Optimizer):
             return self._step_per_tensor(loss)
         model = self._model()
         if model is None:
-            raise MuseHipError("FusedAdamW: the model that owned these parameters is gone")
+            raise MuseHipError(f"{self._who}: the model that owned these parameters is gone")
         if not model._flat_ok():
-            raise MuseHipError("FusedAdamW: the model's flat parameter buffer was rebuilt (model.to(...) / load after the "
+            raise MuseHipError(f"{self._who}: the model's flat parameter buffer was rebuilt (model.to(...) / load after the "
                                "optimizer was created is fine, replacing p.data is not)")
         flat = model.flat_params()
         order = model._param_order()
         if any(p.grad is None for p in order):
             if all(p.grad is None for p in order):
                 return loss  # nothing to do before the first backward (torch skips None grads)
-            raise MuseHipError("FusedAdamW: some parameters have no gradient; the flat step needs all of them")
-        g = _flat_grad_checked(model, order)
+            raise MuseHipError(f"{self._who}: some parameters have no gradient; the flat step needs all of them")
+        g = _flat_grad_checked(model, order, self._who)
         self._ensure_flat_state(flat)
         self._step += 1
         shadow = model._flat_c if model._flat_c is not None and model._flat_c.device == flat.device else None
@@ -464,22 +457,13 @@ class FusedAdamW(torch.optim.Optimizer):
         return loss
 
     def _apply(self, model, b, e, shadow, skip=None, scale_dev=None):
-        flat, g = model.flat_params(), model.flat_grads()
         # (the guard only when there is one: an unguarded update stays the call it always was, so a stand-in for ops.adamw_flat /
         #  adamw_flat_groups written without the keyword - a host-logic test, a CPU restatement of the kernel - keeps working; the
         #  same for the device-side gradient factor of a clipped step)
         guard = {} if skip is None else {"skip": skip}
         if scale_dev is not None:
             guard["scale_dev"] = scale_dev
-        if len(self.param_groups) > 1:
-            seg_end, seg_group = self._segments(model)
-            ops.adamw_flat_groups(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], b,
-                                  seg_end, seg_group, self.param_groups, self._step_for_apply, grad_scale=float(self.grad_scale), **guard)
-            return
-        grp = self.param_groups[0]
-        ops.adamw_flat(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], float(grp["lr"]),
-                       grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], self._step_for_apply,
-                       grad_scale=float(self.grad_scale), **guard)
+        self._launch_flat(model, b, e, shadow, guard)
 
     @property
     def _step_for_apply(self):
@@ -526,7 +510,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _check_not_partial(self):
         if getattr(self, "_partial_step", False):
-            raise MuseHipError("FusedAdamW: an earlier step failed inside backward after AdamW had already been applied to part of "
+            raise MuseHipError(f"{self._who}: an earlier step failed inside backward after {self._rule} had already been applied to part of "
                                "the parameters (in-backward / behind-the-all-reduce update); the optimizer state is inconsistent - "
                                "restore parameters and optimizer from a checkpoint (or set MUSE_OPT_IN_BACKWARD=0 / "
                                "MUSE_OPT_IN_REDUCER=0 to keep the update out of backward)")
@@ -643,15 +627,6 @@ class FusedAdamW(torch.optim.Optimizer):
         reducer.post_reduce = None
         self._norm_done, self._norm_live = (None if failed else self._norm_live), None
 
-    def _ensure_flat_state(self, flat):
-        if self._m is None:
-            self._m = torch.zeros_like(flat)
-            self._v = torch.zeros_like(flat)
-        elif self._m.device != flat.device:       # the model moved after the state was created / loaded: follow it
-            self._m, self._v = self._m.to(flat.device), self._v.to(flat.device)
-        if self._m.shape != flat.shape:
-            raise MuseHipError("FusedAdamW: optimizer state does not match the model's flat parameter buffer")
-
     def _step_per_tensor(self, loss):
         """parameters that are ordinary (contiguous f32) tensors: one muse_adamw_multi launch over all of them.  torch.optim.AdamW
         semantics: a parameter without a gradient is skipped and keeps its own state; the step count is shared (all
@@ -663,19 +638,12 @@ class FusedAdamW(torch.optim.Optimizer):
                                                   or getattr(getattr(p, "_muse_shadow", None), "dtype", None) == torch.float16 for p, _ in params)
         if not params:
             return loss
-        if self._m is None:
-            self._m, self._v = {}, {}
         self._step += 1
         rows = []
         for p, gk in params:
             if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
-                raise MuseHipError("FusedAdamW: parameters and gradients must be contiguous float32 tensors")
-            k = id(p)
-            if k not in self._m:
-                self._m[k] = torch.zeros_like(p)
-                self._v[k] = torch.zeros_like(p)
-            elif self._m[k].device != p.device:
-                self._m[k], self._v[k] = self._m[k].to(p.device), self._v[k].to(p.device)
+                raise MuseHipError(f"{self._who}: parameters and gradients must be contiguous float32 tensors")
+            state_ptrs = self._tensor_state(p)          # (m, v) pointers of the rule's state for p, created / moved to p's device
             shadow = getattr(p, "_muse_shadow", None)   # the model's cached bf16 compute copy of this weight (MaskGiTUViT bf16 mode)
             if shadow is not None and (shadow.numel() != p.numel() or shadow.device != p.device or not shadow.is_contiguous()):
                 shadow = None
@@ -686,8 +654,7 @@ class FusedAdamW(torch.optim.Optimizer):
             if planes is not None and shadow is None and planes[0].numel() == p.numel() and planes[0].device == p.device \
                     and planes[0].is_contiguous() and planes[1] > 0:
                 shadow, lo = planes[0], int(planes[1])
-            row = (p.data.data_ptr(), p.grad.data_ptr(), self._m[k].data_ptr(), self._v[k].data_ptr(),
-                   shadow.data_ptr() if shadow is not None else 0, p.numel())
+            row = (p.data.data_ptr(), p.grad.data_ptr()) + state_ptrs + (shadow.data_ptr() if shadow is not None else 0, p.numel())
             rows.append(row + (gk | (lo << 8),) if multi else row)
         # one launch for all tensors.  Gradients are fresh allocations every step, so the pointer table is rebuilt every step: ~500
         # rows staged through two alternating PINNED host buffers and copied asynchronously (a pageable copy would make the host
@@ -726,13 +693,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self.last_grad_norm, self.last_clip_coef = out[0], out[1]
             clip = {"scale_dev": out[2:3]}
         try:
-            if multi:
-                ops.adamw_multi_groups(self._table, self._chunk_first, len(rows), self._nchunks, self.param_groups, self._step,
-                                       grad_scale=float(self.grad_scale), skip=skip, **clip)
-            else:
-                grp = self.param_groups[0]
-                ops.adamw_multi(self._table, self._chunk_first, len(rows), self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
-                                grp["eps"], grp["weight_decay"], self._step, grad_scale=float(self.grad_scale), skip=skip, **clip)
+            self._launch_multi(multi, len(rows), dict(grad_scale=float(self.grad_scale), skip=skip, **clip))
         finally:
             self._f16_guard_off(guards)
         return loss
@@ -767,7 +728,40 @@ class FusedAdamW(torch.optim.Optimizer):
             images.after_optimizer_step()
             ops._F16_GUARDS.discard(images)
 
-    # ---- checkpointing in torch.optim.AdamW's layout ----------------------------------------------------------------
+    # ---- the rule's state: `_MOMENTS` names its tensors ((state-dict key, attribute), the first one `_m`), `_HAS_STEP` whether its
+    # checkpoints carry a step count.  Flat mode: one buffer per moment, shaped like the model's flat parameter buffer; per-tensor mode:
+    # one dict per moment, keyed by id(parameter)
+    _MOMENTS = ()
+    _HAS_STEP = True
+
+    def _ensure_flat_state(self, flat):
+        attrs = [a for _, a in self._MOMENTS]
+        if self._m is None:
+            for a in attrs:
+                setattr(self, a, torch.zeros_like(flat))
+        elif self._m.device != flat.device:       # the model moved after the state was created / loaded: follow it
+            for a in attrs:
+                setattr(self, a, getattr(self, a).to(flat.device))
+        if self._m.shape != flat.shape:
+            raise MuseHipError(f"{self._who}: optimizer state does not match the model's flat parameter buffer")
+
+    def _tensor_state(self, p):
+        """per-tensor mode: p's state tensors, created as zeros / moved to p's device -> the table's (m, v) pointer columns (0 where the
+        rule has no such moment)"""
+        if self._m is None:
+            for _, a in self._MOMENTS:
+                setattr(self, a, {})
+        k, ptrs = id(p), []
+        for _, a in self._MOMENTS:
+            store = getattr(self, a)
+            if k not in store:
+                store[k] = torch.zeros_like(p)
+            elif store[k].device != p.device:
+                store[k] = store[k].to(p.device)
+            ptrs.append(store[k].data_ptr())
+        return tuple(ptrs) + (0,) * (2 - len(ptrs))
+
+    # ---- checkpointing in the layout of the torch.optim class the rule stands in for ----------------------------------
     def _flat_offsets(self, model):
         return {id(q): o for q, o in zip(model._param_order(), model._offsets)}
 
@@ -780,23 +774,23 @@ class FusedAdamW(torch.optim.Optimizer):
             n0 += len(grp["params"])
             groups.append(g)
         state = {}
-        if self._step > 0 and self._m is not None:
+        if (self._step > 0 or not self._HAS_STEP) and self._m is not None:
             stepv = torch.tensor(float(self._step))
+            head = (lambda: {"step": stepv.clone()}) if self._HAS_STEP else dict
             if self._model is None:
                 for i, p in enumerate(ps):
                     if id(p) in self._m:
-                        state[i] = {"step": stepv.clone(), "exp_avg": self._m[id(p)], "exp_avg_sq": self._v[id(p)]}
+                        state[i] = dict(head(), **{name: getattr(self, a)[id(p)] for name, a in self._MOMENTS})
             else:
                 offs = self._flat_offsets(self._model())
                 for i, p in enumerate(ps):
                     o, n = offs[id(p)], p.numel()
-                    state[i] = {"step": stepv.clone(), "exp_avg": self._m[o:o + n].view(p.shape),
-                                "exp_avg_sq": self._v[o:o + n].view(p.shape)}
+                    state[i] = dict(head(), **{name: getattr(self, a)[o:o + n].view(p.shape) for name, a in self._MOMENTS})
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         if "state" not in sd or "param_groups" not in sd:
-            raise MuseHipError("FusedAdamW.load_state_dict expects torch.optim's layout {'state', 'param_groups'}")
+            raise MuseHipError(f"{self._who}.load_state_dict expects torch.optim's layout {{'state', 'param_groups'}}")
         ps = self._all_params()
         if len(sd["param_groups"]) != len(self.param_groups):
             raise ValueError("loaded state dict has a different number of parameter groups")
@@ -808,38 +802,139 @@ class FusedAdamW(torch.optim.Optimizer):
             ids += gi
             mine.update({k: v for k, v in grp.items() if k != "params"})
         state = {ids.index(k) if k in ids else k: v for k, v in sd["state"].items()}
-        steps = {int(float(v["step"])) for v in state.values()}
-        if len(steps) > 1:
-            raise MuseHipError("FusedAdamW keeps one step count for all parameters; the checkpoint has several")
-        self._step = steps.pop() if steps else 0
+        if self._HAS_STEP:
+            steps = {int(float(v["step"])) for v in state.values()}
+            if len(steps) > 1:
+                raise MuseHipError(f"{self._who} keeps one step count for all parameters; the checkpoint has several")
+            self._step = steps.pop() if steps else 0
+        attrs = [a for _, a in self._MOMENTS]
         if not state:
-            self._m = self._v = None
+            for a in attrs:
+                setattr(self, a, None)
             return
         model = self._model() if self._model is not None else None
         if model is None:
-            self._m, self._v = {}, {}
+            for a in attrs:
+                setattr(self, a, {})
             for i, st in state.items():
                 p = ps[i]
-                for name, store in (("exp_avg", self._m), ("exp_avg_sq", self._v)):
+                for name, a in self._MOMENTS:
                     t = st[name]
                     if tuple(t.shape) != tuple(p.shape):
-                        raise ValueError(f"FusedAdamW.load_state_dict: {name} of parameter {i} has shape {tuple(t.shape)}, "
+                        raise ValueError(f"{self._who}.load_state_dict: {name} of parameter {i} has shape {tuple(t.shape)}, "
                                          f"expected {tuple(p.shape)}")
-                    store[id(p)] = t.detach().to(device=p.device, dtype=torch.float32).contiguous().clone()
+                    getattr(self, a)[id(p)] = t.detach().to(device=p.device, dtype=torch.float32).contiguous().clone()
             return
         if len(state) != len(ps):
-            raise MuseHipError("FusedAdamW (flat): the checkpoint must carry state for every parameter")
+            raise MuseHipError(f"{self._who} (flat): the checkpoint must carry state for every parameter")
         flat = model.flat_params()
         offs = self._flat_offsets(model)
-        self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
+        for a in attrs:
+            setattr(self, a, torch.zeros_like(flat))
         for i, p in enumerate(ps):
             o, n = offs[id(p)], p.numel()
-            for name, buf in (("exp_avg", self._m), ("exp_avg_sq", self._v)):
+            for name, a in self._MOMENTS:
                 t = state[i][name]
                 if tuple(t.shape) != tuple(p.shape):
-                    raise ValueError(f"FusedAdamW.load_state_dict: {name} of parameter {i} has shape {tuple(t.shape)}, "
+                    raise ValueError(f"{self._who}.load_state_dict: {name} of parameter {i} has shape {tuple(t.shape)}, "
                                      f"expected {tuple(p.shape)}")
-                buf[o:o + n].view(p.shape).copy_(t.detach().to(device=flat.device, dtype=torch.float32))
+                getattr(self, a)[o:o + n].view(p.shape).copy_(t.detach().to(device=flat.device, dtype=torch.float32))
+
+
+class FusedAdamW(_FusedOptimizer):
+    """AdamW (decoupled weight decay, torch.optim.AdamW numerics) as ONE kernel launch over the model's flat f32
+    parameter / gradient buffers; also refreshes the bf16 compute copy of the weights in the same pass.
+
+    Drop-in for `optimizer_cls(model.parameters(), lr=..., betas=..., weight_decay=..., eps=...)`.  `state_dict()` /
+    `load_state_dict()` use torch.optim.AdamW's layout ({"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups"}),
+    so optimizer checkpoints written by the reference's `adamw` choice load here and vice versa.
+
+    `max_grad_norm` (also an attribute; None = off): clip the gradient by its global L2 norm inside the step - the semantics of
+    `accelerator.clip_grad_norm_(model.parameters(), max_grad_norm)` right before `optimizer.step()` (training/train_muse.py:758-761):
+    step() = norm kernels (for whatever begin_norm_in_backward / begin_norm_in_reducer have not already delivered) -> one finalize
+    launch -> ONE AdamW launch that reads `grad_scale * min(1, max_grad_norm / (norm + 1e-6))` from device memory.  No device-to-host
+    copy, no stream synchronisation.  `p.grad` is left UNSCALED (that write pass is what is saved): code that reads the gradients
+    after step() sees the unclipped ones - use muse.clip_grad_norm_ where the clipped gradient itself is needed.  After the step
+    `last_grad_norm` (the norm before clipping, of the gradient times `grad_scale`) and `last_clip_coef` are 0-dim device tensors.
+    It is not a param_groups default and does not enter state_dict(): checkpoints keep torch.optim.AdamW's layout."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+        params = list(params)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._init_fused(max_grad_norm)
+
+    _who = "FusedAdamW"
+    _rule = "AdamW"
+    _MOMENTS = (("exp_avg", "_m"), ("exp_avg_sq", "_v"))
+
+    def _launch_flat(self, model, b, e, shadow, guard):
+        flat, g = model.flat_params(), model.flat_grads()
+        if len(self.param_groups) > 1:
+            seg_end, seg_group = self._segments(model)
+            ops.adamw_flat_groups(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], b,
+                                  seg_end, seg_group, self.param_groups, self._step_for_apply, grad_scale=float(self.grad_scale), **guard)
+            return
+        grp = self.param_groups[0]
+        ops.adamw_flat(flat[b:e], g[b:e], self._m[b:e], self._v[b:e], None if shadow is None else shadow[b:e], float(grp["lr"]),
+                       grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], self._step_for_apply,
+                       grad_scale=float(self.grad_scale), **guard)
+
+    def _launch_multi(self, multi, nrows, kw):
+        if multi:
+            ops.adamw_multi_groups(self._table, self._chunk_first, nrows, self._nchunks, self.param_groups, self._step, **kw)
+        else:
+            grp = self.param_groups[0]
+            ops.adamw_multi(self._table, self._chunk_first, nrows, self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
+                            grp["eps"], grp["weight_decay"], self._step, **kw)
+
+
+class FusedLion(_FusedOptimizer):
+    """Lion (the reference's `lion` optimizer choice, training/optimizer.py) on muse.FusedAdamW's machinery with the update rule
+    swapped: ONE launch over the model's flat buffers (or over the pointer table of a model with ordinary parameters), the weights'
+    bf16 / bf16x3 / half images refreshed in the same pass, parameter groups, `max_grad_norm`, the "f16" overflow guard, stepping
+    inside backward and behind the reducer's buckets - see muse.FusedAdamW.  The arithmetic is the reference class's, rounding by
+    rounding (lion_update1 of csrc/optim.hip): p = p * (1 - lr * wd) - lr * sign(beta1 * m + (1 - beta1) * g), then
+    m = beta2 * m + (1 - beta2) * g.  The state is `exp_avg` alone: 4 bytes per parameter against AdamW's 8.
+
+    Drop-in for `Lion(params, lr=..., betas=..., weight_decay=...)` with the reference's defaults and argument checks; further keyword
+    arguments are accepted and ignored, as there.  `state_dict()` / `load_state_dict()` use the reference class's layout ({"state":
+    {i: {"exp_avg"}}, "param_groups": [{lr, betas, weight_decay, params}]}: no step count, no exp_avg_sq), so a checkpoint written
+    by the reference's `lion` choice loads here and vice versa."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0, max_grad_norm=None, **kwargs):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+        super().__init__(list(params), dict(lr=lr, betas=betas, weight_decay=weight_decay))
+        self._init_fused(max_grad_norm)
+
+    _who = "FusedLion"
+    _rule = "Lion"
+    _subset_hint = "the reference's Lion class"
+    _MOMENTS = (("exp_avg", "_m"),)
+    _HAS_STEP = False
+
+    def _launch_flat(self, model, b, e, shadow, guard):
+        flat, g = model.flat_params(), model.flat_grads()
+        if len(self.param_groups) > 1:
+            seg_end, seg_group = self._segments(model)
+            ops.lion_flat_groups(flat[b:e], g[b:e], self._m[b:e], None if shadow is None else shadow[b:e], b, seg_end, seg_group,
+                                 self.param_groups, grad_scale=float(self.grad_scale), **guard)
+            return
+        grp = self.param_groups[0]
+        ops.lion_flat(flat[b:e], g[b:e], self._m[b:e], None if shadow is None else shadow[b:e], float(grp["lr"]), grp["betas"][0],
+                      grp["betas"][1], grp["weight_decay"], grad_scale=float(self.grad_scale), **guard)
+
+    def _launch_multi(self, multi, nrows, kw):
+        if multi:
+            ops.lion_multi_groups(self._table, self._chunk_first, nrows, self._nchunks, self.param_groups, **kw)
+        else:
+            grp = self.param_groups[0]
+            ops.lion_multi(self._table, self._chunk_first, nrows, self._nchunks, float(grp["lr"]), grp["betas"][0], grp["betas"][1],
+                           grp["weight_decay"], **kw)
 
 
 def grouped_parameters(model, weight_decay, no_decay=("bias", "layer_norm.weight", "mlm_ln.weight", "embeddings.weight")):
@@ -1184,7 +1279,7 @@ class TrainStep:
     labels, soft_targets)`, backward, AdamW (class-conditional MaskGitTransformer only).  The prefetch then carries both.
 
     `max_grad_norm` (config.training.max_grad_norm, training/train_maskgit_imagenet.py:435-436): clip the gradient by its global L2
-    norm before the update (muse.FusedAdamW's `max_grad_norm`, which this sets).  The sums of squares are then accumulated where the
+    norm before the update (muse.FusedAdamW's / muse.FusedLion's `max_grad_norm`, which this sets).  The sums of squares are then accumulated where the
     update runs otherwise - inside backward, or behind each bucket's all-reduce - and step() finalizes and updates; the update itself
     cannot overlap backward any more (it needs the last gradient's norm)."""
 
@@ -1192,8 +1287,8 @@ class TrainStep:
                  min_masking_rate: float = 0.0, use_soft_code_target: bool = False, soft_code_temp: float = 1.0,
                  use_stochastic_code: bool = False, max_grad_norm: Optional[float] = None):
         if max_grad_norm is not None:
-            if not isinstance(optimizer, FusedAdamW):
-                raise MuseHipError("TrainStep(max_grad_norm=...) clips inside muse.FusedAdamW's step; with another optimizer call "
+            if not isinstance(optimizer, _FusedOptimizer):
+                raise MuseHipError("TrainStep(max_grad_norm=...) clips inside muse.FusedAdamW's / muse.FusedLion's step; with another optimizer call "
                                    "muse.clip_grad_norm_ between backward and step in a loop of your own")
             optimizer.max_grad_norm = float(max_grad_norm)
         self.vq_model, self.model, self.optimizer, self.reducer = vq_model, model, optimizer, reducer
@@ -1289,21 +1384,21 @@ class TrainStep:
             loss = soft_target_cross_entropy(logits, labels, soft)
         else:
             _, loss = self.model(input_ids=input_ids, labels=labels, label_smoothing=self.label_smoothing)
-        # clipping (FusedAdamW.max_grad_norm): the sums of squares are accumulated where the update would run - the update waits for step()
-        clip = isinstance(self.optimizer, FusedAdamW) and self.optimizer.max_grad_norm is not None
+        # clipping (FusedAdamW / FusedLion .max_grad_norm): the sums of squares are accumulated where the update would run - the update waits for step()
+        clip = isinstance(self.optimizer, _FusedOptimizer) and self.optimizer.max_grad_norm is not None
         flat_model = hasattr(self.model, "grad_ready_hook") and hasattr(self.model, "flat_grads")
         normed = (clip and self.optimizer_in_backward and self.reducer is None and flat_model
                   and self.optimizer.begin_norm_in_backward(self.model))
         normed_r = (clip and not normed and self.optimizer_in_reducer and self.reducer is not None
                     and getattr(self.reducer, "_flat_mode", False) and self.reducer.model is self.model
                     and self.optimizer.begin_norm_in_reducer(self.model, self.reducer))
-        # AdamW inside backward (FusedAdamW.begin_step_in_backward): only when nothing sits between the two - no reducer here
-        armed = (not clip and self.optimizer_in_backward and self.reducer is None and isinstance(self.optimizer, FusedAdamW)
+        # the update inside backward (FusedAdamW / FusedLion .begin_step_in_backward): only when nothing sits between the two - no reducer here
+        armed = (not clip and self.optimizer_in_backward and self.reducer is None and isinstance(self.optimizer, _FusedOptimizer)
                  and getattr(self.model, "wgrad_stream", False) and hasattr(self.model, "grad_ready_hook")
                  and self.model._resolve_cd() == torch.bfloat16 and self.optimizer.begin_step_in_backward(self.model))
-        # ... and with a reducer: AdamW on each bucket right behind its all-reduce, on the reducer's stream
+        # ... and with a reducer: the update on each bucket right behind its all-reduce, on the reducer's stream
         armed_r = (not clip and not armed and self.optimizer_in_reducer and self.reducer is not None and getattr(self.reducer, "_flat_mode", False)
-                   and self.reducer.model is self.model and isinstance(self.optimizer, FusedAdamW) and loss.is_cuda
+                   and self.reducer.model is self.model and isinstance(self.optimizer, _FusedOptimizer) and loss.is_cuda
                    and self.model._resolve_cd() == torch.bfloat16 and self.optimizer.begin_step_in_reducer(self.model, self.reducer))
         failed = True
         try:

@@ -3,6 +3,7 @@
     MUSE_HIP_LIB=/path/to/libmuse_hip.so python scripts/optim_parent_ab.py --dump FILE    # every case below -> FILE (raw bytes of every output)
     python scripts/optim_parent_ab.py --compare A B                                       # demands A == B byte for byte (exit 1 otherwise)
     MUSE_HIP_LIB=... python scripts/optim_parent_ab.py --time                             # HIP events: 5 warm-up + 20 timed launches, median per kernel
+    python scripts/optim_parent_ab.py --time-lion                                         # the same method, Lion against AdamW on the same tensors
 
 One process per library (the library is chosen when muse is imported).  Inputs come from a seeded CPU generator.  Every AdamW form runs
 steps 1, 2, 3 under: the host's grad_scale 0.5; grad_scale 1/3 (no power of two: the one case where a different contraction of g*s - m
@@ -204,7 +205,28 @@ def compare(a, b):
     sys.exit(1 if bad else 0)
 
 
-def time_kernels(warmup=5, launches=20):
+def median_us(fn, warmup=5, launches=20):
+    step = 0
+    for _ in range(warmup):
+        step += 1
+        fn(step)
+    torch.cuda.synchronize()
+    events = []
+    for _ in range(launches):
+        step += 1
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn(step)
+        e1.record()
+        events.append((e0, e1))
+    torch.cuda.synchronize()
+    return round(1000.0 * statistics.median(a.elapsed_time(b) for a, b in events), 2)
+
+
+def time_lion():
+    """lion_multi against adamw_multi over the parameter table of BASELINE config 4 (MaskGiTUViT, bf16 copies of every tensor), and
+    lion_flat against adamw_flat over the flat buffer of the configs/imagenet.yaml transformer with its bf16 shadow: each pair in this
+    one process, on the same p, g, m and images.  TB/s counts 30 (AdamW) / 22 (Lion) bytes per element."""
     import muse
     import weights as W
     dev_gen = torch.Generator(device="cuda").manual_seed(5)
@@ -212,22 +234,48 @@ def time_kernels(warmup=5, launches=20):
     def normal(n, scale):
         return torch.empty(n, dtype=torch.float32, device="cuda").normal_(generator=dev_gen).mul_(scale)
 
-    def median_us(fn):
-        step = 0
-        for _ in range(warmup):
-            step += 1
-            fn(step)
-        torch.cuda.synchronize()
-        events = []
-        for _ in range(launches):
-            step += 1
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn(step)
-            e1.record()
-            events.append((e0, e1))
-        torch.cuda.synchronize()
-        return round(1000.0 * statistics.median(a.elapsed_time(b) for a, b in events), 2)
+    def pair(res, name, n, adamw, lion):
+        # AdamW, Lion, AdamW, Lion: the two medians of each are reported so that the pair's own drift shows
+        a = [median_us(adamw), None]
+        li = [median_us(lion), None]
+        a[1], li[1] = median_us(adamw), median_us(lion)
+        res[name] = dict(elements=n, adamw_us=a, lion_us=li, adamw_tb_s=round(30.0 * n / min(a) / 1e6, 3), lion_tb_s=round(22.0 * n / min(li) / 1e6, 3),
+                         lion_over_adamw=round(statistics.median(li) / statistics.median(a), 4))
+    res = {"library": os.environ.get("MUSE_HIP_LIB", "in-tree")}
+    with torch.device("meta"):
+        sizes = [q.numel() for q in muse.MaskGiTUViT(**W.UVIT_CC12M).parameters()]
+    rows, keep = [], []
+    for sz in sizes:
+        p, g, m, v = normal(sz, 0.02), normal(sz, 0.01), torch.zeros(sz, device="cuda"), torch.zeros(sz, device="cuda")
+        sh = torch.zeros(sz, dtype=torch.bfloat16, device="cuda")
+        keep.append((p, g, m, v, sh))
+        rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), sh.data_ptr(), sz))
+    first, nch = ops.chunk_first(sizes)
+    first, table = torch.tensor(first, dtype=torch.int32).cuda(), torch.tensor(rows, dtype=torch.int64).cuda()
+    res["multi_tensors"] = len(sizes)
+    pair(res, "multi", sum(sizes),
+         lambda step: ops.adamw_multi(table, first, len(sizes), nch, 1e-4, 0.9, 0.999, 1e-8, 0.01, step),
+         lambda step: ops.lion_multi(table, first, len(sizes), nch, 1e-4, 0.9, 0.99, 0.01))
+    del keep, rows, table
+    model = muse.MaskGitTransformer(**W.TRANSFORMER_B).to("cuda")
+    n = model.flat_params().numel()
+    del model
+    p, g, m, v = normal(n, 0.02), normal(n, 0.01), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    sh = torch.zeros(n, dtype=torch.bfloat16, device="cuda")
+    pair(res, "flat", n,
+         lambda step: ops.adamw_flat(p, g, m, v, sh, 1e-4, 0.9, 0.999, 1e-8, 0.01, step),
+         lambda step: ops.lion_flat(p, g, m, sh, 1e-4, 0.9, 0.99, 0.01))
+    print(json.dumps(res))
+
+
+def time_kernels():
+    import muse
+    import weights as W
+    dev_gen = torch.Generator(device="cuda").manual_seed(5)
+
+    def normal(n, scale):
+        return torch.empty(n, dtype=torch.float32, device="cuda").normal_(generator=dev_gen).mul_(scale)
+
     res = {"library": os.environ.get("MUSE_HIP_LIB", "in-tree")}
     # the flat buffer of the configs/imagenet.yaml transformer, with its bf16 shadow; segments = its parameters, matrices decayed
     model = muse.MaskGitTransformer(**W.TRANSFORMER_B).to("cuda")
@@ -273,6 +321,7 @@ def main():
     ap.add_argument("--dump", metavar="FILE")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--time-lion", action="store_true")
     ap.add_argument("--limit", type=float, default=240.0, help="seconds the run may take before the process is ended")
     args = ap.parse_args()
     faulthandler.dump_traceback_later(args.limit, exit=True)
@@ -282,8 +331,10 @@ def main():
         dump(args.dump)
     elif args.time:
         time_kernels()
+    elif args.time_lion:
+        time_lion()
     else:
-        ap.error("one of --dump, --compare, --time")
+        ap.error("one of --dump, --compare, --time, --time-lion")
 
 
 if __name__ == "__main__":
