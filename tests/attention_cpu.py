@@ -1,7 +1,7 @@
 """Plain torch restatement of the fused attention kernels' operation (csrc/attention.hip, attention2.hip, attention3.hip and the causal
 policy of attention_enc.hip), for tests/test_gpu_attention_edges.py and tests/test_attention_cpu.py.  Imports without a GPU.
 
-Four layers:
+Five layers:
   * `reference`: ctx, lse, dq, dk, dv of softmax(alpha q k^T) v in float64 on the rounded inputs, full visibility or causal, and the
     per-element "terms" normalisers: a result is judged against the sum of the magnitudes it adds up, not against the tensor's largest
     entry.  With p = softmax(alpha q k^T), dp = dO v^T and dsum = rowsum(dO * O):
@@ -11,6 +11,9 @@ Four layers:
     of the five products, P and dS rounded to bf16 once, the row sum taken over the rounded P, f32 accumulation, everything else f32.
     It fixes where bf16 rounding is allowed; it is neither a copy of the kernels nor the code under test.  Its error against float64 is
     E_ref.  It also takes the three classic defects (`defect=`) that tests/test_attention_cpu.py seeds to prove that the checks can fail;
+  * `core3_model` (`model_h16`, `model_x3`): the same for the two TF32-class cores of attention3.hip, f32 in and out - every product one
+    IEEE-half product (gradient operands times the power-of-two scale S) or three bf16 products of hi / lo planes; with the defects of
+    tests/test_gpu_attention_x3_edges.py (a missing 1 / S, an unscaled dsum, a skipped middle key block) besides the dropped / leaked key;
   * probe builders, every value exact in bf16 (asserted):
       - `address_probe`: key j carries its base-16 digits (a, b, c), their squares and three ones in nine feature columns, the query
         aimed at key t carries c' (2 a_t, 2 b_t, 2 c_t, -1, -1, -1, -a_t^2, -b_t^2, -c_t^2) with c' a power of two and alpha c' >= 32.
@@ -36,7 +39,10 @@ BF16_ULP = 2.0 ** -8        # one bf16 rounding, relative (the spacing just belo
 PROBE_LSE_TOL = 1e-5        # |lse| (address) and |lse - log Skv| (uniform); the smallest defect shift is log(1026 / 1025) = 9.7e-4
 X3_TOL = 2.0 ** -14         # bf16x3 results of the uniform probe: 2^-16 per product (the documented class), two chained products, x 2
 KINDS = ("ctx", "lse", "dq", "dk", "dv")
-DEFECTS = ("drop_last", "leak_pad", "causal_plus", "causal_minus")
+DEFECTS = ("drop_last", "leak_pad", "causal_plus", "causal_minus", "no_unscale", "dsum_unscaled", "skip_middle")
+HALF = torch.float16
+HALF_ULP = 2.0 ** -11       # one rounding to IEEE half, relative (normal range)
+HALF_SUB_HALF = 2.0 ** -25  # half the spacing of half's subnormals: a magnitude at or below it rounds to 0, rounding into them is off by this much
 
 
 def bf(t):
@@ -44,9 +50,19 @@ def bf(t):
     return t.to(BF).to(F32)
 
 
+def hf(t):
+    """round to IEEE half (nearest even, overflow to inf), keep float32"""
+    return t.to(HALF).to(F32)
+
+
 def assert_bf16_exact(**tensors):
     for name, t in tensors.items():
         assert torch.equal(t.to(BF).to(t.dtype), t), f"{name}: not exact in bf16"
+
+
+def assert_half_exact(**tensors):
+    for name, t in tensors.items():
+        assert torch.equal(t.to(HALF).to(t.dtype), t), f"{name}: not exact in IEEE half"
 
 
 def to_heads(t, B, S, nh, hd):
@@ -70,12 +86,22 @@ def make_case(B, Sq, Skv, nh, hd, q, k, v, do, alpha=None, causal=False, **extra
     return c
 
 
-def random_case(B, Sq, Skv, nh, hd, seed, causal=False):
-    """seeded N(0, 1) operands, rounded to bf16"""
+def bf_half(t):
+    """round to bf16, then to half (a bf16 value below 2^-14 loses bits there); the result is exact in both formats (asserted)"""
+    t = hf(bf(t))
+    assert_bf16_exact(t=t)
+    assert_half_exact(t=t)
+    return t
+
+
+def random_case(B, Sq, Skv, nh, hd, seed, causal=False, rnd=bf):
+    """seeded N(0, 1) operands, rounded to bf16 (rnd = bf_half: exact in bf16 and half, the H16 cases; rnd = None: plain f32, both planes
+    of the bf16x3 kernels in use)"""
     g = torch.Generator().manual_seed(seed)
     H = nh * hd
-    q, do = (bf(torch.randn((B * Sq, H), generator=g)) for _ in range(2))
-    k, v = (bf(torch.randn((B * Skv, H), generator=g)) for _ in range(2))
+    rnd = rnd or (lambda t: t)
+    q, do = (rnd(torch.randn((B * Sq, H), generator=g)) for _ in range(2))
+    k, v = (rnd(torch.randn((B * Skv, H), generator=g)) for _ in range(2))
     return make_case(B, Sq, Skv, nh, hd, q, k, v, do, causal=causal)
 
 
@@ -162,6 +188,83 @@ def rounded_outputs(out, dtype=BF):
     return {n: (t if n == "lse" else t.to(dtype)) for n, t in out.items()}
 
 
+# ---- the two TF32-class cores of csrc/attention3.hip (f32 tensors in and out) ------------------------------------------------------------
+def prod_h16(a, b):
+    """one half product: both operands rounded to IEEE half, exact products, f32 accumulation (half8 / split_raw<true> / fill_two<.., true>
+    convert, mma_rows3 / mma_seq3 issue one v_mfma_f32_32x32x16_f16 per K step)"""
+    return hf(a) @ hf(b)
+
+
+def split_bf16(t):
+    hi = bf(t)
+    return hi, bf(t - hi)
+
+
+def prod_x3(a, b):
+    """bf16x3: hi = bf16(x), lo = bf16(x - hi); lo*hi + hi*lo + hi*hi in f32 (split8 / pack8x3; the dropped lo*lo term and the 16 bits an
+    operand keeps are 2^-16 per product, X3_TOL's class)"""
+    ah, al = split_bf16(a)
+    bh, bl = split_bf16(b)
+    return al @ bh + ah @ bl + ah @ bh
+
+
+def core3_model(c, prod, S=1.0, defect=None, ctx_bwd=None):
+    """float32 at the precision class of attention3.hip's kernels, `prod` = prod_h16 (the H16 instantiations) or prod_x3:
+      forward   s = prod(q, k^T); m = rowmax(s); p = exp(alpha (s - m)) in f32; l = rowsum(p) over the UNROUNDED p (the kernels add the f32
+                p before mma_seq3 converts it); ctx = prod(p, v) / l; lse = alpha m + log l
+      backward  dsum = S (dO . O) in f32 from the f32 tensors (O: the f32 context, or ctx_bwd); p = exp(alpha s - lse);
+                dS = p (prod(S dO, v^T) - dsum) in f32; dq = prod(dS, k) alpha / S, dk = prod(dS^T, q) alpha / S, dv = prod(p^T, S dO) / S
+    S (a power of two) is the H16 backward's gradient scale (the bf16x3 kernels have none: S = 1).  Operands of an H16 case must be exact in
+    bf16 and half (asserted; dO times S in half).  defect: "drop_last" / "leak_pad" as contract_model; "skip_middle" hides keys 256 .. 511 (the
+    middle block of a 768-key stream); "no_unscale" leaves the 1 / S off dq, dk, dv; "dsum_unscaled" applies S to dO but not to dsum."""
+    assert defect is None or defect in DEFECTS
+    q, k, v, do = _operands(c, F32)
+    if prod is prod_h16:
+        assert_bf16_exact(q=q, k=k, v=v)
+        assert_half_exact(q=q, k=k, v=v, do_scaled=do * S)
+    B, Sq, Skv, nh, hd = c["B"], c["Sq"], c["Skv"], c["nh"], c["hd"]
+    a = float(c["alpha"])
+    vis = None
+    if defect == "drop_last":
+        vis = torch.ones((Sq, Skv), dtype=torch.bool)
+        vis[:, Skv - 1] = False
+    if defect == "skip_middle":
+        assert Skv == 768
+        vis = torch.ones((Sq, Skv), dtype=torch.bool)
+        vis[:, 256:512] = False
+    if defect == "leak_pad":
+        pad = torch.zeros_like(k[..., :1, :])
+        k, v = torch.cat([k, pad], -2), torch.cat([v, pad], -2)
+    s = prod(q, k.transpose(-1, -2))
+    if vis is not None:
+        s = s.masked_fill(~vis, -math.inf)
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp((s - m) * a)
+    l = p.sum(-1, keepdim=True)
+    ctx = prod(p, v) / l
+    lse = m * a + torch.log(l)
+    o = ctx if ctx_bwd is None else to_heads(ctx_bwd.to(F32), B, Sq, nh, hd)
+    dos = do * S
+    dsum = (do * o).sum(-1, keepdim=True) * (1.0 if defect == "dsum_unscaled" else S)
+    pb = torch.exp(s * a - lse)
+    ds = pb * (prod(dos, v.transpose(-1, -2)) - dsum)
+    un = 1.0 if defect == "no_unscale" else 1.0 / S
+    dq, dk, dv = prod(ds, k) * (a * un), prod(ds.transpose(-1, -2), q) * (a * un), prod(pb.transpose(-1, -2), dos) * un
+    if defect == "leak_pad":
+        dk, dv = dk[..., :Skv, :], dv[..., :Skv, :]
+    out = {n: to_rows(t) for n, t in dict(ctx=ctx, dq=dq, dk=dk, dv=dv).items()}
+    out["lse"] = lse.reshape(B * nh, Sq)
+    return out
+
+
+def model_h16(c, S=1.0, defect=None, ctx_bwd=None):
+    return core3_model(c, prod_h16, S, defect, ctx_bwd)
+
+
+def model_x3(c, defect=None, ctx_bwd=None):
+    return core3_model(c, prod_x3, 1.0, defect, ctx_bwd)
+
+
 # =====================================================================================================================================
 # probe values
 # =====================================================================================================================================
@@ -243,10 +346,21 @@ def address_leak_bounds(c):
     return dict(ctx=e * c["Skv"] * V_MAX, dv=e * c["Sq"] * DO_MAX, dq=a * c["Skv"] * e * d * 225.0, dk=a * c["Sq"] * e * d * 225.0 * cp)
 
 
-def uniform_probe(B, Sq, Skv, nh, hd, seed, alpha=None):
+def address_leak_bounds_h16(c, S):
+    """address_leak_bounds for the H16 core.  Every key beside the target has p <= e^-32 (f32, one rounding of exp2's argument and result:
+    1 + 2^-20), which is 0 as a half: NOTHING leaks into P V or into dV.  dS is rounded to half AFTER the product with dP - dsum, in
+    the scaled domain: |S dS| <= x = e^-32 S 2 hd max|dO| max|v| becomes 0 when x <= 2^-25 and at most x (1 + 2^-11) + 2^-25 otherwise (a
+    half subnormal is off by up to half its spacing); the results are divided by S again.  The target's own dS is exactly 0."""
+    a, cp = float(c["alpha"]), address_scale(c["alpha"])
+    x = math.exp(-a * cp) * (1 + 2.0 ** -20) * 2 * c["hd"] * V_MAX * DO_MAX * S
+    ds = 0.0 if x <= HALF_SUB_HALF else (x * (1 + HALF_ULP) + HALF_SUB_HALF) / S
+    return dict(ctx=0.0, dv=0.0, dq=a * c["Skv"] * ds * 225.0, dk=a * c["Sq"] * ds * 225.0 * cp)
+
+
+def uniform_probe(B, Sq, Skv, nh, hd, seed, alpha=None, rnd=bf):
     g = torch.Generator().manual_seed(seed)
     H = nh * hd
-    q, k = torch.zeros((B * Sq, H)), bf(torch.randn((B * Skv, H), generator=g))
+    q, k = torch.zeros((B * Sq, H)), rnd(torch.randn((B * Skv, H), generator=g))
     v, do = probe_v(B, Skv, nh, hd), probe_do(B, Sq, nh, hd)
     assert_bf16_exact(q=q, k=k, v=v, do=do)
     return make_case(B, Sq, Skv, nh, hd, q, k, v, do, alpha=alpha, probe="uniform")
@@ -314,14 +428,21 @@ def mfma_slack(n, mag):
     return (3 * math.ceil(n / 16) + 8) * 2.0 ** -23 * mag
 
 
-def check_address(c, out, tag="address", bf16_out=True):
+def check_address(c, out, tag="address", bf16_out=True, h16=None, ctx_slack=False):
     """out: dict of CPU row tensors, any subset of ctx, lse, dq, dk, dv.  Targets every query sees: ctx == v[target] bit for bit (an f32
     context: within mfma_slack), |lse| < 1e-5, dv within the leakage (+ mfma_slack) of the exact scatter-sum, dq / dk within the
     leakage of 0.  A map with hidden targets (causal, `masked`): ctx within one bf16 rounding (+ the leakage) of the float64 masked
-    reference."""
+    reference.
+    h16 = the gradient scale S of a run of the H16 core: the other keys' P is 0 as a half, so ctx == v[target] AND dv == the scatter-sum
+    bit for bit, dq / dk within address_leak_bounds_h16.  ctx_slack (the streamed H16 forward): the key blocks before the target's were
+    added at the running maximum of their time - the nearest key of each with P = 1 - and scaled down by e^-32 or less when the target
+    arrived, so the MFMA that adds v[target] finds that remainder in its C operand: ctx within mfma_slack, as an f32 bf16x3 context."""
     ctx_e, dv_e = address_expected(c)
-    lk = address_leak_bounds(c)
-    lk["dv"] += mfma_slack(c["Sq"], float(_scatter_to_keys(c, c["do"].abs()).max()))       # (the largest per-key sum of |dO|)
+    if h16 is None:
+        lk = address_leak_bounds(c)
+        lk["dv"] += mfma_slack(c["Sq"], float(_scatter_to_keys(c, c["do"].abs()).max()))   # (the largest per-key sum of |dO|)
+    else:
+        lk = address_leak_bounds_h16(c, h16)
     vis = visible(c["Sq"], c["Skv"], c["causal"])
     hidden = vis is not None and not bool(torch.gather(vis.expand(c["B"], c["nh"], -1, -1), 3, c["targets"][..., None]).all())
     for n in out:
@@ -333,7 +454,7 @@ def check_address(c, out, tag="address", bf16_out=True):
             d = (got.double() - ref).abs()
             w = _worst(d, bf16_ulp(ref) + lk["ctx"])
             assert w <= 1.0, f"{tag} ctx: {w:.3g} x (one bf16 rounding + leakage) from the float64 masked reference"
-        elif not bf16_out:
+        elif not bf16_out and (h16 is None or ctx_slack):
             e = float((got.double() - ctx_e).abs().max())
             assert e <= mfma_slack(c["Skv"], V_MAX), f"{tag} ctx: max |ctx - v[target]| = {e:.3e}, allowed {mfma_slack(c['Skv'], V_MAX):.1e}"
         else:
@@ -362,12 +483,14 @@ def _rows_identical(t, B, S, nh, hd):
     return bool((h == h[:, :, :1]).all())
 
 
-def check_uniform(c, out, ref, e_ref_dq, bf16_out=True, tag="uniform"):
+def check_uniform(c, out, ref, e_ref_dq, bf16_out=True, tag="uniform", h16=False):
     """q = 0: |lse - log Skv| < 1e-5; ctx the column mean of v (one rounding to the output type; P = 1 and the integer sums are exact in any
     order, so with a bf16 kernel every query's row is the same bit pattern); dk exactly 0; dv the same for every key (bit for bit for a bf16
     kernel: p is one bf16 number, its products with small integers and their sums are exact) and within one rounding of p and one of the
     output of colsum(dO) / Skv; dq per element over its terms: 4 E_ref (the contract model on the uniform cases) + one bf16 rounding.
-    The bf16x3 kernels (f32 results): X3_TOL of the terms instead."""
+    The bf16x3 kernels (f32 results): X3_TOL of the terms instead.  h16 (the H16 core, f32 results): the forward's P = 1 is exact in
+    half (ctx as for bf16), the backward's p = 1 / Skv is rounded to half once (2^-11 of every term of dv; v and S dO are integers, exact),
+    dk exactly 0, dq 4 E_ref of the H16 model (e_ref_dq)."""
     B, Sq, Skv, nh, hd = c["B"], c["Sq"], c["Skv"], c["nh"], c["hd"]
     for n in out:
         _finite(f"{tag} {n}", out[n])
@@ -381,27 +504,28 @@ def check_uniform(c, out, ref, e_ref_dq, bf16_out=True, tag="uniform"):
         w = _worst(d, bound)
         assert w <= 1.0, f"{tag} {n}: {w:.3g} x its bound"
     if "ctx" in out:
-        judge("ctx", 1e-6 if bf16_out else X3_TOL)                  # (bf16: P = 1 exactly, integer sums, an f32 reciprocal and product)
+        judge("ctx", 1e-6 if bf16_out or h16 else X3_TOL)                  # (bf16: P = 1 exactly, integer sums, an f32 reciprocal and product)
         if bf16_out:
             assert _rows_identical(out["ctx"], B, Sq, nh, hd), f"{tag} ctx: the queries of a head do not all hold the same row"
     if "dk" in out:
         assert not bool((out["dk"] != 0).any()), f"{tag} dk: not exactly 0 with q = 0"
     if "dv" in out:
-        judge("dv", BF16_ULP + 1e-6 if bf16_out else X3_TOL)        # (bf16: one rounding of p; 1e-6: exp and the f32 lse it reads)
+        judge("dv", BF16_ULP + 1e-6 if bf16_out else HALF_ULP + 1e-6 if h16 else X3_TOL)        # (bf16: one rounding of p; 1e-6: exp and the f32 lse it reads)
         if bf16_out:
             assert _rows_identical(out["dv"], B, Skv, nh, hd), f"{tag} dv: the keys of a head do not all hold the same row"
     if "dq" in out:
-        judge("dq", 4.0 * e_ref_dq if bf16_out else X3_TOL)
+        judge("dq", 4.0 * e_ref_dq if bf16_out or h16 else X3_TOL)
 
 
 def measure(got, ref, scale):
     return float(((got.double() - ref).abs() / scale).max()) if ref.numel() else 0.0
 
 
-def model_errors(c, ref=None, kinds=KINDS):
-    """E_ref of one case: the contract model (before its output rounding) against float64, per output kind, over the terms"""
+def model_errors(c, ref=None, kinds=KINDS, model=contract_model):
+    """E_ref of one case: the contract model (before its output rounding; model_h16 / model_x3: the f32 results) against float64, per
+    output kind, over the terms"""
     ref = reference(c) if ref is None else ref
-    m = contract_model(c)
+    m = model(c)
     return {n: measure(m[n], ref[n], 1.0 if n == "lse" else ref["t_" + n]) for n in kinds}
 
 

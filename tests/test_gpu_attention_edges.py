@@ -33,8 +33,9 @@ Which case meets which branch (Sq x Skv; "self" = the SELF_LENS at all four head
     128-row chunks (both sides long)         self 289 .. 1025
   attention2.hip shape_ok (head dim 48, self, 225 <= S <= 260): ATTN2_LENS 224 | 225, 256 | 257 (8 | 9 key blocks), 260 | 261, each with
     MUSE_ATTN2=1 and =0 (at 224 and 261 both settings must reach the general kernels)
-  attention3.hip: 3 | 8 key blocks (Skv 65, 77, 96 | 225, 240, 256), one | several 256-query blocks (Sq 256 | 512), several key blocks
-    (Skv 512) streamed (X3_STREAM) or as block pairs + merge
+  attention3.hip: 3 | 8 key blocks (Skv 65, 77, 96 | 225, 240, 256), one | several 256-query blocks (Sq 256 | 512, 768), several key blocks
+    (Skv 512; 768: a middle block, neither first nor last) streamed (X3_STREAM) or as block pairs + merge.  Here: the probes on the bf16x3
+    instantiations; tests/test_gpu_attention_x3_edges.py has their seeded cases and planes and everything on the H16 ("f16" mode) ones
   attention_enc.hip, causal policy: S 1, 15, 16, 17, 32, 33, 77, 127, 128 (1 .. 8 waves; an odd number of key tiles; the S = 128 limit)
 """
 import ctypes as C
@@ -88,7 +89,7 @@ CROSS = [(256, 77), (384, 77), (385, 77), (512, 77), (129, 77), (17, 289), (1, 2
 ATTN2_LENS = [224, 225, 256, 257, 260, 261]
 CAUSAL_LENS = [1, 15, 16, 17, 32, 33, 77, 127, 128]
 CAUSAL_HDS = (32, 64)
-X3_SQ, X3_SKV = (256, 512), (65, 77, 96, 225, 240, 256, 512)
+X3_SQ, X3_SKV = (256, 512, 768), (65, 77, 96, 225, 240, 256, 512, 768)
 POISON = [(17, 64, None), (77, 64, None), (257, 64, None), (257, 48, "1"), (257, 48, "0"), (289, 64, None), (513, 64, None)]
 
 BF16_SHAPES = ([(s, s, hd) for hd in HDS for s in SELF_LENS] + [(sq, skv, hd) for hd in CROSS_HDS for sq, skv in CROSS]
