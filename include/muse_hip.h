@@ -846,6 +846,36 @@ int muse_clip_vision_embed_ln(const float* patch, const float* class_embedding, 
 int muse_l2_normalize_rows(const float* x, float* y, int64_t rows, int32_t cols, float mult, int32_t has_mult, const float* log_mult,
                            void* stream);
 
+/* ---- masked-token logging diagnostics (diag.hip): muse/training_utils.py:299-397 of the reference, called by training/train_muse.py
+ * :812-847 on the step's own logits.  Both read logits [rows, ld] (f32 or bf16, first `vocab` columns valid, any element-aligned base
+ * and any ld >= vocab: rows off 16-byte alignment are read through a peeled head and tail, never past column `vocab`), accumulate in
+ * f32, use no atomics and allocate nothing.  A row's results are a function of the row's values alone - not of its address, `ld` or
+ * the other rows - and the same bits on every run.  vocab > ld, a NULL required pointer or another dtype: MUSE_ERR_BAD_ARG.
+ * muse_token_stats: per row, lse[r] = logsumexp(x[r]) and entropy[r] = -sum_v p log p with p = softmax(x[r]), from ONE read of the row:
+ *   an online (max m, s = sum e^(x - m), t = sum e^(x - m) (x - m)) gives lse = m + log s and entropy = log s - t / s (which is
+ *   lse - sum(e x) / sum(e) with m taken out of both terms).  row_mask (NULL = every row) holds one byte per row: a row whose byte is 0
+ *   is not loaded, its entropy is written as 0 and its lse is unspecified.  row_max, sum_exp (both or neither; NULL = not wanted)
+ *   receive m and s themselves, for muse_masked_mean_probs.  Replaces the softmax, log_softmax and their product of
+ *   pixel_entropy_per_percent_masked_bucket (:304-307).
+ * muse_masked_mean_probs: per image b, mean_probs[b, v] = (sum over s with input_ids[b, s] == mask_id, ascending, of
+ *   exp(x[b, s, v] - lse[b S + s])) / n_masked[b], logits seen as [batch * seq, ld]; rows that are not masked are not loaded.  The
+ *   row's lse comes in as the pair (row_max, sum_exp) of muse_token_stats, valid for at least the masked rows, and the term is
+ *   evaluated as exp(x - max) * (1 / sum): a rounded lse near 10 would put a common relative error of 5e-7 on a row's probabilities.
+ *   mean_probs f32 [batch, vocab] contiguous.  entropy (NULL = skip) f32 [batch]: -sum_v mean_probs log(mean_probs) by a second small
+ *   launch over mean_probs (one block per image, fixed summation order).  The reference's expression as it stands (:329-336): an image
+ *   with no masked token gives NaN (0 / 0), a code whose mean probability is exactly 0 gives NaN (0 * -inf).  batch <= 65535, else
+ *   MUSE_ERR_UNSUPPORTED.
+ * muse_masked_row_mean: out[b] = (sum_s values[b, s]) / #{s : input_ids[b, s] == mask_id} for values f32 [batch, seq] contiguous -
+ *   entropy_per_pixel.sum(-1) / num_masked_pixels (:312-313) on muse_token_stats' entropies (exact zeros where not masked).  One block
+ *   per image, a fixed summation order: an image's mean is the same bits in any batch.  No masked token: NaN (0 / 0). */
+int muse_masked_row_mean(const float* values, const int64_t* input_ids, float* out, int32_t batch, int32_t seq, int64_t mask_id,
+                         void* stream);
+int muse_token_stats(const void* logits, int32_t dtype, const uint8_t* row_mask, float* lse, float* entropy, float* row_max, float* sum_exp,
+                     int64_t rows, int32_t vocab, int64_t ld, void* stream);
+int muse_masked_mean_probs(const void* logits, int32_t dtype, const int64_t* input_ids, const float* row_max, const float* sum_exp,
+                           float* mean_probs, float* entropy, int32_t batch, int32_t seq, int32_t vocab, int64_t ld, int64_t mask_id,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

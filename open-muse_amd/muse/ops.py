@@ -1556,6 +1556,78 @@ def cross_entropy_fwd(logits, labels, label_smoothing, vocab=None, want_rows=Fal
     return loss_out, lse
 
 
+def _logit_rows(what, logits, vocab):
+    """(rows, V, ld) of a [rows, cols] logits tensor the diagnostics kernels read in place: unit last stride, V <= cols, V <= ld"""
+    require_gpu(logits)
+    dt(logits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise _hip.MuseHipError(f"{what}: logits must be [rows, cols] with rows, cols >= 1, got {tuple(logits.shape)}")
+    if logits.stride(1) != 1:
+        raise _hip.MuseHipError(f"{what}: the last stride of logits must be 1, got {logits.stride(1)}")
+    rows, cols = logits.shape
+    V = cols if vocab is None else int(vocab)
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), cols)
+    if not 1 <= V <= cols or V > ld:
+        raise _hip.MuseHipError(f"{what}: vocab {V} does not fit rows of {cols} columns with row stride {ld}")
+    return rows, V, ld
+
+
+def token_stats(logits, vocab=None, row_mask=None, want_max_sum=False):
+    """logits [rows, cols] (f32 / bf16, last stride 1, any row stride: a sliced view goes in as it is), first `vocab` columns valid ->
+    (lse [rows], entropy [rows]) f32 from one read of each row, and with want_max_sum also (row_max [rows], sum_exp [rows]) - the row
+    maximum m and sum of exp(x - m) that lse = m + log(sum) is made of, which masked_mean_probs takes.  row_mask (bool / uint8
+    [rows]): rows whose entry is 0 are not loaded, their entropy is 0 and their other results unspecified.  Nothing is written but
+    the results."""
+    rows, V, ld = _logit_rows("token_stats", logits, vocab)
+    if row_mask is not None:
+        require_gpu(row_mask)
+        if row_mask.dtype not in (torch.bool, torch.uint8) or row_mask.numel() != rows or not row_mask.is_contiguous():
+            raise _hip.MuseHipError("token_stats: row_mask must be a contiguous bool / uint8 tensor with one entry per row")
+    out = torch.empty((4 if want_max_sum else 2, rows), dtype=torch.float32, device=logits.device)
+    e0 = _prof_begin()
+    check(lib().muse_token_stats(logits.data_ptr(), dt(logits), ptr(row_mask), out[0].data_ptr(), out[1].data_ptr(),
+                                 out[2].data_ptr() if want_max_sum else None, out[3].data_ptr() if want_max_sum else None, rows, V, ld,
+                                 stream()), "muse_token_stats")
+    _prof_end(e0, "token_stats", float(rows) * V * _esz(logits) + _nbytes(out), "byte")   # an upper bound under a row_mask
+    return tuple(out.unbind(0))
+
+
+def masked_row_mean(values, input_ids, mask_id):
+    """values f32 [B, S] contiguous (token_stats' entropies: exact zeros where not masked), input_ids int64 [B, S] -> f32 [B]: the row
+    sums over the images' masked counts, in a fixed order per image (the same bits in any batch); NaN for an image without a masked token"""
+    require_gpu(values, input_ids)
+    if (values.dtype != torch.float32 or input_ids.dtype != torch.long or input_ids.dim() != 2 or values.shape != input_ids.shape
+            or not values.is_contiguous() or not input_ids.is_contiguous()):
+        raise _hip.MuseHipError("masked_row_mean: values f32 and input_ids int64 must be contiguous [B, S] tensors of one shape")
+    B, S = input_ids.shape
+    out = torch.empty(B, dtype=torch.float32, device=values.device)
+    check(lib().muse_masked_row_mean(values.data_ptr(), input_ids.data_ptr(), out.data_ptr(), B, S, int(mask_id), stream()),
+          "muse_masked_row_mean")
+    return out
+
+
+def masked_mean_probs(logits, input_ids, row_max, sum_exp, mask_id, vocab=None, want_entropy=True):
+    """logits [B * S, cols] as for token_stats, input_ids int64 [B, S], (row_max, sum_exp) f32 [B * S] from token_stats(...,
+    want_max_sum=True), valid for at least the masked rows -> (mean_probs f32 [B, vocab], entropy f32 [B] or None): per image the mean
+    of softmax(logits) over its masked tokens (rows added in ascending order, unmasked rows not loaded) and -sum(mean_probs *
+    log(mean_probs)); NaN for an image with no masked token and for a mean probability of exactly 0, as the reference's expression"""
+    rows, V, ld = _logit_rows("masked_mean_probs", logits, vocab)
+    require_gpu(input_ids, row_max, sum_exp)
+    if input_ids.dim() != 2 or input_ids.dtype != torch.long or not input_ids.is_contiguous() or input_ids.numel() != rows:
+        raise _hip.MuseHipError("masked_mean_probs: input_ids must be a contiguous int64 [B, S] with B * S = the logits' rows")
+    for t in (row_max, sum_exp):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
+            raise _hip.MuseHipError("masked_mean_probs: row_max and sum_exp must be contiguous f32 tensors with one entry per row")
+    B, S = input_ids.shape
+    mean = torch.empty((B, V), dtype=torch.float32, device=logits.device)
+    ent = torch.empty(B, dtype=torch.float32, device=logits.device) if want_entropy else None
+    e0 = _prof_begin()
+    check(lib().muse_masked_mean_probs(logits.data_ptr(), dt(logits), input_ids.data_ptr(), row_max.data_ptr(), sum_exp.data_ptr(),
+                                       mean.data_ptr(), ptr(ent), B, S, V, ld, int(mask_id), stream()), "muse_masked_mean_probs")
+    _prof_end(e0, "masked_mean_probs", float(rows) * V * _esz(logits) + 8.0 * B * V, "byte")   # an upper bound: masked rows only
+    return mean, ent
+
+
 def cross_entropy_bwd(logits, labels, lse, loss_out, grad_out, label_smoothing, out_dtype, vocab=None):
     """dlogits has the same (padded) row stride as logits; pad columns are written as zeros."""
     require_gpu(logits, labels, grad_out)
