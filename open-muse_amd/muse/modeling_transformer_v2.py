@@ -665,7 +665,7 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
                 dgl = ops.linear_dgrad(dtb, wo2)
             else:
                 dgl = self._lin_bwd(dt, sv["gl"], lyr.ffn.wo, nm + ".ffn.wo", G)
-            dab = ops.glu_bwd(sv["ab"], dgl, planes_only=isinstance(sv["gl"], ops.Planes) and ops.planes_only_ok(*sv["ab"].shape))
+            dab = ops.glu_bwd(sv["ab"], dgl, planes_only=isinstance(sv["gl"], ops.OperandOnly) and ops.planes_only_ok(*sv["ab"].shape))
             gw01 = self._mm_dw(dab, sv["m3"], sv["w01"].shape)
             I = gw01.shape[0] // 2
             G[nm + ".ffn.wi_0.weight"], G[nm + ".ffn.wi_1.weight"] = gw01[:I], gw01[I:]

@@ -98,21 +98,32 @@ def gemm(A, B, C_, M, N, K, *, la=0, lb=0, lda, ldb, ldc, a_off=0, b_off=0, c_of
     la/lb = 0: operand(r,k) at base + r*ld + k;  1: at base + k*ld + r (see include/muse_hip.h).
     x3_lo = (a_lo, b_lo): A / B are the bf16 hi planes of a bf16x3 product, their lo planes that many elements behind them
     (muse_gemm_x3); returns None when that kernel does not take the product.
+
+    Here: the mode prologue - an f32 product of a running "f16" / "bf16x3" pass (GemmPass) goes to that mode's route; the rest is _gemm_plain.
     """
     require_gpu(A, B, C_)
-    if (_F32_AS_F16[0] and C_.dtype == torch.float32 and (A.dtype, B.dtype) in _F16_MODE_PAIRS and act == 0 and split_k == 1 and batch == 1
+    kind = _PASS.kind
+    if (kind == "f16" and C_.dtype == torch.float32 and (A.dtype, B.dtype) in _F16_MODE_PAIRS and act == 0 and split_k == 1 and batch == 1
             and _gemm_f16(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, c_off, alpha, bias, rowvec, residual, ldr, accumulate, a_off, b_off)):
         return C_
     if A.dtype != B.dtype:
         raise _hip.MuseHipError("gemm operands must share a dtype")
-    if _F32_AS_BF16X3[0] and A.dtype == torch.float32 and C_.dtype == torch.float32 and act == 0 and split_k == 1:
-        done = _gemm_bf16x3(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, a_off, b_off, c_off, alpha, bias, rowvec, residual, ldr, batch,
-                            zdiv, sA, sB, sC, accumulate)
-        if done:
-            return C_
-    if isinstance(A, Planes) or isinstance(B, Planes):
-        # a planes-only operand has no f32 bytes behind data_ptr(): every path below would read its bf16 planes as something else
+    if (kind == "bf16x3" and A.dtype == torch.float32 and C_.dtype == torch.float32 and act == 0 and split_k == 1
+            and _gemm_bf16x3(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, a_off, b_off, c_off, alpha, bias, rowvec, residual, ldr, batch, zdiv,
+                             sA, sB, sC, accumulate)):
+        return C_
+    if isinstance(A, OperandOnly) or isinstance(B, OperandOnly):
+        # an operand-only object has no f32 bytes behind data_ptr(): every path below would read its image as something else
         raise _hip.MuseHipError("a planes-only operand reached a product the four-plane kernel does not take")
+    return _gemm_plain(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, a_off, b_off, c_off, alpha, bias, rowvec, residual, ldr, batch, zdiv, sA, sB, sC,
+                       accumulate, act, split_k, split_stride, x3_lo)      # (positional: this hop is on every product's host path)
+
+
+def _gemm_plain(A, B, C_, M, N, K, la=0, lb=0, lda=None, ldb=None, ldc=None, a_off=0, b_off=0, c_off=0, alpha=1.0, bias=None, rowvec=None,
+                residual=None, ldr=0, batch=1, zdiv=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), accumulate=False, act=0, split_k=1,
+                split_stride=0, x3_lo=None):
+    """gemm() on the operands as they are, whatever pass is running: the skinny split-K of a captured forward, the bring-up transpose
+    route, or one muse_gemm / muse_gemm_x3 launch"""
     if (SKINNY and x3_lo is None and A.dtype == torch.bfloat16 and batch == 1 and la == 0 and lb == 0 and act == 0 and rowvec is None and not accumulate
             and split_k == 1 and M <= 2048 and K >= 512 and N % 4 == 0 and ldc % 4 == 0 and (residual is None or ldr % 4 == 0)
             and (SKINNY == 2 or torch.cuda.is_current_stream_capturing())):
@@ -134,7 +145,7 @@ def gemm(A, B, C_, M, N, K, *, la=0, lb=0, lda, ldb, ldc, a_off=0, b_off=0, c_of
             sk = (nk + per - 1) // per
         if sk >= 2:
             ws = torch.empty((sk, M, N), dtype=torch.float32, device=A.device)
-            gemm(A, B, ws, M, N, K, la=0, lb=0, lda=lda, ldb=ldb, ldc=N, a_off=a_off, b_off=b_off, alpha=alpha, split_k=sk, split_stride=M * N)
+            _gemm_plain(A, B, ws, M, N, K, la=0, lb=0, lda=lda, ldb=ldb, ldc=N, a_off=a_off, b_off=b_off, alpha=alpha, split_k=sk, split_stride=M * N)
             check(lib().muse_sum_slices_epilogue(ws.data_ptr(), sk, M * N, ptr(bias), ptr(residual), ldr, C_.data_ptr() + c_off * _esz(C_),
                                                  dt(C_), ldc, M, N, stream()), "muse_sum_slices_epilogue")
             return _touched(C_)
@@ -181,6 +192,168 @@ def gemm(A, B, C_, M, N, K, *, la=0, lb=0, lda, ldb, ldc, a_off=0, b_off=0, c_of
     return _touched(C_)
 
 
+# ---- the compute pass: how the f32 products of the forward / backward pass that is running are computed --------------------------------
+# Exact f32 (no pass), "bf16x3" or "f16" (the two sections below).  _PASS is the ONE place that knows: gemm() / linear_wgrad() ask it for
+# the route, the producer kernels' wrappers for the operand-image format, scale and cache, split_planes / split_cat3 for the split cache.
+class GemmPass:
+    """kind: None | "bf16x3" | "f16"; images: the operand-image cache of the step - an X3Images or None ("bf16x3": None = route, do not
+    cache), an F16Images ("f16": always one)"""
+
+    def __init__(self, kind=None, images=None):
+        self.kind, self.images = kind, images
+        self.x3 = None if kind == "f16" else images        # the split cache split_planes / split_cat3 go through
+        # the operand-image tensor a producer kernel writes (planes_alloc): ONE IEEE-half image [1, r, c], or (hi, lo) bf16 planes [2, r, c]
+        self.image_planes, self.image_dtype = (1, torch.float16) if kind == "f16" else (2, torch.bfloat16)
+
+    def scale(self, gradient):
+        """the power of two a producer kernel applies to its image: the pass's gradient scale for a backward result of an "f16" pass"""
+        return self.images.grad_scale if (gradient and self.kind == "f16") else 1.0
+
+    def producing(self):
+        """the cache a producer kernel's operand image goes to, None when it should write none"""
+        return self.images if (F16_PRODUCERS if self.kind == "f16" else X3_NATIVE and X3_PRODUCERS) else None
+
+
+_PASS = GemmPass()
+
+
+class _PassScope:
+    """makes a GemmPass the running one for a `with` body; the previous pass is back on exit (also when the body raises).  There is one
+    slot: an inner scope wins, so an on=True scope of one mode inside a pass of the other REPLACES that pass for its body (no caller
+    nests them).  on=False switches this mode's routing off - a bf16x3 step's split cache stays readable - and leaves a pass of the
+    other mode alone."""
+
+    def __init__(self, kind, on, images):
+        self.kind, self.on, self.images = kind, bool(on), images
+
+    def __enter__(self):
+        global _PASS
+        self.prev = _PASS
+        if self.on:
+            _PASS = GemmPass(self.kind, self.images)
+        elif _PASS.kind == self.kind:
+            _PASS = GemmPass(None, _PASS.x3)
+        return self
+
+    def __exit__(self, *exc):
+        global _PASS
+        _PASS = self.prev
+        if self.on and self.kind == "f16" and self.images.backward:
+            _F16_GUARDS.add(self.images)         # (the owner's optimizer step that follows skips its update if this pass overflowed)
+        return False
+
+
+def f32_gemms_as_bf16x3(on=True, images=None):
+    """`images`: an X3Images to share operand images between the products of a step (None: every product splits its operands)"""
+    return _PassScope("bf16x3", on, images)
+
+
+def f32_gemms_as_f16(on=True, images=None):
+    """`images`: the F16Images of the step (None: a private one - every product converts its operands)"""
+    return _PassScope("f16", on, images if images is not None else (F16Images() if on else None))
+
+
+class _ImageCache:
+    """What the two modes' operand-image caches share: entries keyed by (storage address, shape, strides, autograd version, form) that
+    hold their source tensor - so an address cannot come back with other contents while the entry exists, and the wrappers of kernels
+    that rewrite a tensor in place bump its version (`_touched`) - in `persist` until the owner's clear(), or in a short LRU of `recent`
+    entries: the images a backward pass makes are dead two products later, and so are those of a forward nobody keeps (`keep`)."""
+    keep = True
+
+    def __init__(self, recent=12):
+        self.persist, self.lru, self.recent, self.backward = {}, {}, int(recent), False
+        self.hits = self.misses = self.produced = 0
+
+    def clear(self):
+        self.persist.clear()
+        self.lru.clear()
+
+    @staticmethod
+    def _key(t, *form):
+        return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version) + form
+
+    def _find(self, key):
+        hit = self.persist.get(key)
+        if hit is None:
+            hit = self.lru.get(key)
+        if hit is None:
+            self.misses += 1
+        else:
+            self.hits += 1
+        return hit
+
+    def _store(self, key, entry, short=False):
+        if short or self.backward or not self.keep:
+            self.lru[key] = entry
+            while len(self.lru) > self.recent:
+                self.lru.pop(next(iter(self.lru)))
+        else:
+            self.persist[key] = entry
+
+
+class OperandOnly:
+    """An f32-class GEMM operand that exists ONLY as the operand image a producer kernel wrote - the result of a kernel that nothing but
+    weight GEMMs reads (the GLU output and its input gradient inside an MLP, planes_only=True): the f32 tensor is never written.
+    Quacks like the contiguous f32 [rows, cols] tensor it stands for as far as the GEMM entry points look (shape, dtype, strides); the
+    products that take it are its mode's (Planes: muse_gemm_x3, HalfImage: the half kernels) - anything else raises instead of reading
+    bytes that are not there."""
+    dtype = torch.float32
+    is_cuda = True
+    _version = 0
+
+    def __init__(self, planes):
+        if planes.dtype != self.image_dtype:
+            raise _hip.MuseHipError(f"{type(self).__name__} holds {self.image_dtype} images, got {planes.dtype}")
+        self.planes = planes
+        self.shape = torch.Size(planes.shape[1:])
+        self.device = planes.device
+
+    def dim(self):
+        return 2
+
+    def numel(self):
+        return self.shape[0] * self.shape[1]
+
+    def stride(self, i=None):
+        st = (self.shape[1], 1)
+        return st if i is None else st[i]
+
+    def is_contiguous(self):
+        return True
+
+    def data_ptr(self):
+        return self.planes.data_ptr()      # (only ever probed for alignment)
+
+    def record_stream(self, s):
+        self.planes.record_stream(s)
+
+
+class Planes(OperandOnly):
+    """"bf16x3" mode: the (hi, lo) bf16 planes [2, rows, cols]"""
+    image_dtype = torch.bfloat16
+
+
+class HalfImage(OperandOnly):
+    """"f16" mode: ONE IEEE-half image [1, rows, cols] = half(x * scale), `scale` the power of two the producer kernel was GIVEN
+    (_image_args: the pass's gradient scale for a backward result, 1 for a forward one) - handed in by whoever launched it"""
+    image_dtype = torch.float16
+
+    def __init__(self, planes, scale):
+        super().__init__(planes)
+        self.scale = float(scale)
+
+    def half_image(self):
+        t = self.planes[0]
+        t._muse_scale = self.scale
+        return t
+
+
+def operand_only(planes, gradient):
+    """the operand-only result of a producer kernel of the running pass: `planes` is the tensor it has just written (planes_alloc) with
+    the (half, scale) of _image_args(gradient, planes)"""
+    return HalfImage(planes, _PASS.scale(gradient)) if _PASS.kind == "f16" else Planes(planes)
+
+
 # ---- "f16": every f32 weight GEMM as ONE product of IEEE-half operand images ----------------------------------------------------------
 # configs/cc12m_uvit_clip.yaml:102-103 trains f32 tensors with `enable_tf32`: the products round their operands to TF32 (10-bit mantissa,
 # 8-bit exponent) and accumulate in f32.  gfx950 has no xf32 MFMA; IEEE half has the SAME 10-bit mantissa, and its MFMA
@@ -193,8 +366,7 @@ def gemm(A, B, C_, M, N, K, *, la=0, lb=0, lda, ldb, ldc, a_off=0, b_off=0, c_of
 # one included), the producer kernels (common.h store_image4) every 4-element GROUP that holds one; the cast kernel also counts the
 # finite non-zero elements it rounds to +-0 ([1]).  The fp16-training recipe applies on top: TapeOps.f16_update_grad_scale() halves the
 # scale and has the caller skip the step, or muse.FusedAdamW skips it on the device.  Products the 256^2 half kernels refuse stay in exact f32.
-_F32_AS_F16 = [False]
-_F16_IMAGES = [None]
+# Scoped by f32_gemms_as_f16 (a GemmPass of kind "f16" whose images are the step's F16Images).
 # the F16Images of f16 BACKWARD passes whose overflow counter no optimizer step has consumed yet: muse.FusedAdamW guards its update
 # with the counter of a pass of the model whose parameters it steps (F16Images.owner) - never with another model's
 _F16_GUARDS = weakref.WeakSet()
@@ -203,24 +375,18 @@ _F16_GUARDS = weakref.WeakSet()
 _F16_MODE_PAIRS = {(torch.float32, torch.float32), (torch.float32, torch.float16), (torch.float16, torch.float32)}
 
 
-class F16Images:
-    """The half operand images of ONE training step (the role X3Images plays for the bf16x3 mode): a tensor is converted once per step,
-    whichever products read it - keyed by (storage, shape, strides, version, scale); images made during the backward live in a short LRU.
-    `backward`: the pass running is a backward pass - the A operand of its products and the dy of its weight gradients are gradients and
-    take `grad_scale`.  `keep` (forward passes): images stay until clear() because the backward pass reads them again; a forward that
-    records no tape (inference) sets it False and its images share the short LRU, so no activation outlives its consumers."""
+class F16Images(_ImageCache):
+    """The half operand images of ONE training step (the role X3Images plays for the bf16x3 mode): a tensor is converted once per step and
+    scale, whichever products read it (the key's form is the scale).  `backward`: the pass running is a backward pass - the A operand of
+    its products and the dy of its weight gradients are gradients and take `grad_scale`.  `keep` (forward passes): the backward pass reads
+    the images again; a forward that records no tape (inference) sets it False, so no activation outlives its consumers."""
 
     def __init__(self, grad_scale=1.0, recent=12):
-        self.persist, self.lru, self.recent, self.backward, self.keep = {}, {}, int(recent), False, True
+        super().__init__(recent)
         self.grad_scale = float(grad_scale)
-        self.hits = self.misses = self.produced = 0
         self._stats = None
         self._snaps, self._free, self.totals = [], [], [0, 0]      # counter copies in flight (pinned buffer, event), free ones, running totals
         self.owner = None      # weakref to the model whose passes these are (the optimizer steps that honour its overflow guard)
-
-    def clear(self):
-        self.persist.clear()
-        self.lru.clear()
 
     def set_grad_scale(self, s):
         if s <= 0 or math.frexp(float(s))[0] != 0.5:
@@ -278,27 +444,18 @@ class F16Images:
         return out
 
     def image(self, t, scale):
-        if isinstance(t, Planes):          # a producer's result that exists as its half image only
-            if not t.half:
+        if isinstance(t, OperandOnly):     # a producer's result that exists as its half image only
+            if not isinstance(t, HalfImage):
                 raise _hip.MuseHipError("a bf16x3 planes-only operand reached a half product")
             return t.half_image()
         if t.dtype == torch.float16:       # already an image (a weight's half copy): its own scale rides on it
             return t
-        key = (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version, float(scale))
-        hit = self.persist.get(key)
-        if hit is None:
-            hit = self.lru.get(key)
+        key = self._key(t, float(scale))
+        hit = self._find(key)
         if hit is not None:
-            self.hits += 1
             return hit[1]
-        self.misses += 1
         out = cast_to_f16(t, scale, self._ensure_stats(t.device))
-        if self.backward or not self.keep:
-            self.lru[key] = (t, out)
-            while len(self.lru) > self.recent:
-                self.lru.pop(next(iter(self.lru)))
-        else:
-            self.persist[key] = (t, out)
+        self._store(key, (t, out))
         return out
 
     def put_planes(self, t, planes):
@@ -307,48 +464,19 @@ class F16Images:
         scale = self.grad_scale if self.backward else 1.0
         img = planes[0]
         img._muse_scale = scale
-        key = (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version, float(scale))
         self.produced += 1
-        if self.backward or not self.keep:
-            self.lru[key] = (t, img)
-            while len(self.lru) > self.recent:
-                self.lru.pop(next(iter(self.lru)))
-        else:
-            self.persist[key] = (t, img)
-
-
-class f32_gemms_as_f16:
-    """`images`: the F16Images of the step (None: a private one - every product converts its operands)"""
-    def __init__(self, on=True, images=None):
-        self.on = bool(on)
-        self.images = images if images is not None else (F16Images() if on else None)
-
-    def __enter__(self):
-        self.prev = (_F32_AS_F16[0], _F16_IMAGES[0])
-        _F32_AS_F16[0] = self.on
-        if self.on:
-            _F16_IMAGES[0] = self.images
-        return self
-
-    def __exit__(self, *exc):
-        _F32_AS_F16[0], _F16_IMAGES[0] = self.prev
-        if self.on and self.images is not None and self.images.backward:
-            _F16_GUARDS.add(self.images)         # (the owner's optimizer step that follows skips its update if this pass overflowed)
-        return False
+        self._store(self._key(t, float(scale)), (t, img))
 
 
 def _image_args(gradient, *planes):
     """(half, scale, stats) of a producer entry point (*_x3) in the running pass: half = 1 in an "f16" pass (the kernel writes ONE IEEE-half
     image, and the x3 attention kernels compute in half), scale = the pass's gradient scale for a backward result (`gradient`), 1 for a
     forward one, stats = the pass's overflow counter.  A plane tensor given must have the mode's dtype (half: float16, else bfloat16)."""
-    half = _F32_AS_F16[0]
+    half = _PASS.kind == "f16"
     for p in planes:
-        if p is not None and p.dtype != (torch.float16 if half else torch.bfloat16):
+        if p is not None and p.dtype != _PASS.image_dtype:
             raise _hip.MuseHipError(f"operand image of dtype {p.dtype} in a{'n f16' if half else ' bf16x3'} pass")
-    if not half:
-        return 0, 1.0, None
-    im = _F16_IMAGES[0]
-    return 1, im.grad_scale if gradient else 1.0, im._ensure_stats().data_ptr()
+    return (1, _PASS.scale(gradient), _PASS.images._ensure_stats().data_ptr()) if half else (0, 1.0, None)
 
 
 def cast_to_f16(t, scale=1.0, stats=None):
@@ -388,25 +516,25 @@ def _gemm_f16(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, c_off, alpha, bias, rowv
         return False
     if not _f16_kernel_takes(A, B, C_.data_ptr() + c_off * 4, M, N, K, la, lb, lda, ldb, ldc, residual, ldr):
         return False
-    im = _F16_IMAGES[0]
+    im = _PASS.images
     a16 = im.image(A, im.grad_scale if im.backward else 1.0)
     b16 = im.image(B, 1.0)
-    gemm(a16, b16, C_, M, N, K, la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
-         residual=residual, ldr=ldr, accumulate=accumulate)
+    _gemm_plain(a16, b16, C_, M, N, K, la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
+                residual=residual, ldr=ldr, accumulate=accumulate)
     return True
 
 
 def f16_wgrad_operands(dy, x, M=None, lda=None):
     """the half images (dy with the pass's gradient scale, x unscaled) of a weight-gradient product dy^T x the half kernels take, through
     the running step's image cache - or None (no f16 step running / a shape they refuse: the caller keeps the f32 tensors)"""
-    if not (_F32_AS_F16[0] and dy.dtype == torch.float32 and x.dtype == torch.float32 and dy.dim() == 2 and x.dim() == 2
+    if not (_PASS.kind == "f16" and dy.dtype == torch.float32 and x.dtype == torch.float32 and dy.dim() == 2 and x.dim() == 2
             and (lda is None or lda == dy.stride(0)) and dy.shape[0] == x.shape[0]):
         return None
     N = M if M is not None else dy.shape[1]
     if not (_f16_operands_ok(dy, x, N, x.shape[1], dy.shape[0], 1, 1, dy.stride(0), x.stride(0))
             and _f16_kernel_takes(dy, x, dy.data_ptr(), N, x.shape[1], dy.shape[0], 1, 1, dy.stride(0), x.stride(0), x.shape[1])):
         return None
-    im = _F16_IMAGES[0]
+    im = _PASS.images
     return im.image(dy, im.grad_scale), im.image(x, 1.0)
 
 
@@ -415,13 +543,10 @@ def f16_wgrad_operands(dy, x, M=None, lda=None):
 # (157 TFLOP/s peak).  configs/cc12m_uvit_clip.yaml:102-103 trains in f32 tensors with TF32 products (10-bit mantissa); gfx950 has no
 # xf32 MFMA, the CDNA4 counterpart at or above that precision is the three-product scheme the tokenizer already uses: operands split
 # into hi = bf16(x), lo = bf16(x - hi), C = hi*hi + hi*lo + lo*hi with f32 accumulation (the dropped lo*lo term is 2^-16 relative) on
-# the bf16 kernels at 1/3 of their rate.  Scoped by a context manager the models enter for "bf16x3" compute; a product the bf16 kernels
-# cannot take (operand rows that are not whole 16-byte chunks in bf16) silently stays on the exact-f32 kernel.
-_F32_AS_BF16X3 = [False]
-_X3_IMAGES = [None]      # the operand-image cache of the pass that is running (X3Images), or None
-
-
-class X3Images:
+# the bf16 kernels at 1/3 of their rate.  Scoped by f32_gemms_as_bf16x3, which the models enter for "bf16x3" compute (a GemmPass of that
+# kind; its images are the step's X3Images, or None); a product the bf16 kernels cannot take (operand rows that are not whole 16-byte
+# chunks in bf16) silently stays on the exact-f32 kernel.
+class X3Images(_ImageCache):
     """The bf16x3 operand images of ONE training step, so that a tensor is split once per step instead of once per product.  An
     activation x is the A operand of its Linear's forward product and the B operand of the weight-gradient product; a gradient dY is
     the A operand of the dX product and the A operand of dW; a weight is the B operand of the forward and of the dX product.
@@ -431,134 +556,35 @@ class X3Images:
       * K-concatenated images for the plain kernel (shapes muse_gemm_x3 refuses): with the patterns chosen in `_gemm_bf16x3` /
         `linear_wgrad` the row-concatenated image [T, 3K] of the forward / dX product, viewed as [3T, K], IS the token-stacked image of
         the dW product (token t's three thirds are rows 3t .. 3t+2 - a contraction does not care about the order of its slots).
-    Keyed by (storage address, shape, strides, autograd version, form); an entry keeps its source tensor alive, so an address cannot
-    come back with other contents while the entry exists, and the wrappers of kernels that rewrite a tensor in place bump its version
-    (`_touched`).  The owner clears the cache at the start of a forward and at the end of a backward.  Images made during the backward
-    (dY) are dead two products later: they live in a short LRU."""
-
-    def __init__(self, recent=12):
-        self.persist, self.lru, self.recent, self.backward = {}, {}, int(recent), False
-        self.hits = self.misses = self.produced = 0
-
-    def clear(self):
-        self.persist.clear()
-        self.lru.clear()
-
-    @staticmethod
-    def _key(t, layout, lo_pos):
-        return (t.data_ptr(), tuple(t.shape), tuple(t.stride()), t._version, layout, lo_pos)
+    The form is (layout, lo position), or (9, 0) for the planes.  The owner clears the cache at the start of a forward and at the end of
+    a backward."""
 
     def get(self, t, layout, K, lo_pos, last_use=False):
         key = self._key(t, layout, lo_pos)
-        hit = self.persist.pop(key, None) if last_use else self.persist.get(key)
-        if hit is not None and last_use:      # (the weight-gradient product is an activation's last reader - bar siblings that share it, q / k / v)
-            self._recent(key, hit)
-        if hit is None:
-            hit = self.lru.get(key)
+        hit = self._find(key)
         if hit is not None:
-            self.hits += 1
+            if last_use and self.persist.pop(key, None) is not None:
+                self._store(key, hit, short=True)      # (dW is an activation's last reader - bar siblings that share it, q / k / v)
             return hit[1], hit[2]
-        self.misses += 1
         out, ld = _split_cat3_now(t, layout, K, lo_pos)
-        if self.backward or last_use:
-            self._recent(key, (t, out, ld))
-        else:
-            self.persist[key] = (t, out, ld)
+        self._store(key, (t, out, ld), short=last_use)
         return out, ld
 
     def planes(self, t):
         """(hi, lo) planes [2, *t.shape] of a contiguous f32 tensor (the operand form of muse_gemm_x3): ONE image per tensor whatever
         the product reads it as (forward A, dX A, dW A / B, a weight in the forward and in dX)"""
         key = self._key(t, 9, 0)
-        hit = self.persist.get(key)
-        if hit is None:
-            hit = self.lru.get(key)
+        hit = self._find(key)
         if hit is not None:
-            self.hits += 1
             return hit[1]
-        self.misses += 1
         out = _split_planes_now(t)
-        if self.backward:
-            self._recent(key, (t, out, 0))
-        else:
-            self.persist[key] = (t, out, 0)
+        self._store(key, (t, out, 0))
         return out
 
     def put_planes(self, t, planes):
         """a producer kernel wrote t's planes itself (same bits as the split of t): no split pass when a product reads t"""
-        key = self._key(t, 9, 0)
         self.produced += 1
-        if self.backward:
-            self._recent(key, (t, planes, 0))
-        else:
-            self.persist[key] = (t, planes, 0)
-
-    def _recent(self, key, entry):
-        self.lru[key] = entry
-        while len(self.lru) > self.recent:
-            self.lru.pop(next(iter(self.lru)))
-
-
-class Planes:
-    """An f32-class GEMM operand that exists ONLY as its (hi, lo) bf16 planes [2, rows, cols] - the result of a producer kernel that nothing
-    but weight GEMMs reads (the GLU output and its input gradient inside an MLP, planes_only=True): the f32 tensor is never written.
-    Quacks like the contiguous f32 [rows, cols] tensor it stands for as far as the GEMM entry points look (shape, dtype, strides); the
-    products that take it are the four-plane ones (muse_gemm_x3) - anything else raises instead of reading bytes that are not there."""
-    dtype = torch.float32
-    is_cuda = True
-    _version = 0
-
-    def __init__(self, planes):
-        self.planes = planes
-        self.shape = torch.Size(planes.shape[1:])
-        self.device = planes.device
-        # "f16" mode: ONE IEEE-half image [1, rows, cols] = half(x * scale); the scale is the one the producer kernel applied - the
-        # running pass's gradient scale for a backward result, 1 for a forward one (_image_args)
-        self.half = planes.dtype == torch.float16
-        im = _F16_IMAGES[0]
-        self.scale = (im.grad_scale if (im is not None and im.backward) else 1.0) if self.half else 1.0
-
-    def half_image(self):
-        t = self.planes[0]
-        t._muse_scale = self.scale
-        return t
-
-    def dim(self):
-        return 2
-
-    def numel(self):
-        return self.shape[0] * self.shape[1]
-
-    def stride(self, i=None):
-        st = (self.shape[1], 1)
-        return st if i is None else st[i]
-
-    def is_contiguous(self):
-        return True
-
-    def data_ptr(self):
-        return self.planes.data_ptr()      # (only ever probed for alignment)
-
-    def record_stream(self, s):
-        self.planes.record_stream(s)
-
-
-class f32_gemms_as_bf16x3:
-    """`images`: an X3Images to share operand images between the products of a step (None: every product splits its operands)"""
-    def __init__(self, on=True, images=None):
-        self.on = bool(on)
-        self.images = images
-
-    def __enter__(self):
-        self.prev = (_F32_AS_BF16X3[0], _X3_IMAGES[0])
-        _F32_AS_BF16X3[0] = self.on
-        if self.on:
-            _X3_IMAGES[0] = self.images
-        return self
-
-    def __exit__(self, *exc):
-        _F32_AS_BF16X3[0], _X3_IMAGES[0] = self.prev
-        return False
+        self._store(self._key(t, 9, 0), (t, planes, 0))
 
 
 def split_f32(t):
@@ -589,16 +615,18 @@ def _split_planes_now(t):
 
 def split_planes(t):
     """[2, *t.shape] bf16: hi = bf16(t), lo = bf16(t - hi), through the running step's image cache when there is one"""
-    if isinstance(t, Planes):
+    if isinstance(t, OperandOnly):
+        if not isinstance(t, Planes):
+            raise _hip.MuseHipError("a half image reached a bf16x3 product")
         return t.planes
     require_gpu(t)
-    im = _X3_IMAGES[0]
+    im = _PASS.x3
     return _split_planes_now(t) if im is None else im.planes(t)
 
 
 def split_cat3(t, layout, K, lo_pos, last_use=False):
     """_split_cat3_now through the running step's image cache (X3Images), when there is one"""
-    im = _X3_IMAGES[0]
+    im = _PASS.x3
     if im is None:
         return _split_cat3_now(t, layout, K, lo_pos)
     return im.get(t, layout, K, lo_pos, last_use)
@@ -646,36 +674,30 @@ def _gemm_bf16x3(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, a_off, b_off, c_off, 
     if X3_NATIVE and full2d and lda % 8 == 0 and ldb % 8 == 0 and A.numel() % 8 == 0 and B.numel() % 8 == 0:
         # ONE kernel on the four planes (hi, lo of each operand; csrc/gemm256.h PipeX3): every plane goes through the LDS-DMA path once
         # per K-tile and feeds three MFMA products; one image per tensor serves every product that reads it
-        with f32_gemms_as_bf16x3(False):
-            a2, b2 = split_planes(A), split_planes(B)
-            if gemm(a2[0], b2[0], C_, M, N, K, la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
-                    residual=residual, ldr=ldr, accumulate=accumulate, x3_lo=(A.numel(), B.numel())) is not None:
-                return True
-    if isinstance(A, Planes) or isinstance(B, Planes):
+        a2, b2 = split_planes(A), split_planes(B)
+        if _gemm_plain(a2[0], b2[0], C_, M, N, K, la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
+                       residual=residual, ldr=ldr, accumulate=accumulate, x3_lo=(A.numel(), B.numel())) is not None:
+            return True
+    if isinstance(A, OperandOnly) or isinstance(B, OperandOnly):
         raise _hip.MuseHipError("a planes-only operand reached a product the four-plane kernel does not take")
-    if (X3_CAT and a_off == 0 and b_off == 0 and A.dim() == 2 and B.dim() == 2 and A.is_contiguous() and B.is_contiguous() and K % 8 == 0
-            and A.stride(0) == lda and B.stride(0) == ldb and A.shape[1 if la == 0 else 0] == K and B.shape[1 if lb == 0 else 0] == K
-            and A.shape[0 if la == 0 else 1] >= M and B.shape[0 if lb == 0 else 1] >= N and 3 * A.numel() * 2 < (1 << 31)
-            and 3 * B.numel() * 2 < (1 << 31)):
+    if X3_CAT and full2d and 3 * A.numel() * 2 < (1 << 31) and 3 * B.numel() * 2 < (1 << 31):
         # ONE launch: A' = (hi | hi | lo), B' = (hi | lo | hi) along a three times longer K (muse_split_f32_to_bf16_cat3) - one epilogue,
         # no read-modify-write of C between the terms, the persistent kernel where the plain product would take it
         # which operand carries (hi | hi | lo) and which (hi | lo | hi) is free as long as the two differ; chosen so that the images of
         # a Linear's forward (x W^T: lb = 0) and dX (dY W: lb = 1) products are the ones its dW product wants (X3Images)
         pa, pb = (2, 1) if lb == 0 else (1, 2)
-        with f32_gemms_as_bf16x3(False):
-            a3, lda3 = split_cat3(A, la, K, pa)
-            b3, ldb3 = split_cat3(B, lb, K, pb)
-            gemm(a3, b3, C_, M, N, 3 * K, la=la, lb=lb, lda=lda3, ldb=ldb3, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
-                 residual=residual, ldr=ldr, accumulate=accumulate)
+        a3, lda3 = split_cat3(A, la, K, pa)
+        b3, ldb3 = split_cat3(B, lb, K, pb)
+        _gemm_plain(a3, b3, C_, M, N, 3 * K, la=la, lb=lb, lda=lda3, ldb=ldb3, ldc=ldc, c_off=c_off, alpha=alpha, bias=bias, rowvec=rowvec,
+                    residual=residual, ldr=ldr, accumulate=accumulate)
         return True
-    with f32_gemms_as_bf16x3(False):
-        ah, al = split_f32(A)
-        bh, bl = split_f32(B)
-        kw = dict(la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, a_off=a_off, b_off=b_off, c_off=c_off, alpha=alpha, batch=batch, zdiv=zdiv,
-                  sA=sA, sB=sB, sC=sC)
-        gemm(ah, bh, C_, M, N, K, bias=bias, rowvec=rowvec, residual=residual, ldr=ldr, accumulate=accumulate, **kw)
-        gemm(ah, bl, C_, M, N, K, accumulate=True, **kw)
-        gemm(al, bh, C_, M, N, K, accumulate=True, **kw)
+    ah, al = split_f32(A)
+    bh, bl = split_f32(B)
+    kw = dict(la=la, lb=lb, lda=lda, ldb=ldb, ldc=ldc, a_off=a_off, b_off=b_off, c_off=c_off, alpha=alpha, batch=batch, zdiv=zdiv,
+              sA=sA, sB=sB, sC=sC)
+    _gemm_plain(ah, bh, C_, M, N, K, bias=bias, rowvec=rowvec, residual=residual, ldr=ldr, accumulate=accumulate, **kw)
+    _gemm_plain(ah, bl, C_, M, N, K, accumulate=True, **kw)
+    _gemm_plain(al, bh, C_, M, N, K, accumulate=True, **kw)
     return True
 
 
@@ -697,9 +719,9 @@ def _gemm_via_transpose(A, B, C_, M, N, K, la, lb, lda, ldb, ldc, a_off, b_off, 
 
     A2, lda2, a_off2, sA2 = fix(A, la, M, lda, a_off, sA)
     B2, ldb2, b_off2, sB2 = fix(B, lb, N, ldb, b_off, sB)
-    return gemm(A2, B2, C_, M, N, K, la=0, lb=0, lda=lda2, ldb=ldb2, ldc=ldc, a_off=a_off2, b_off=b_off2, c_off=c_off,
-                alpha=alpha, bias=bias, rowvec=rowvec, residual=residual, ldr=ldr, batch=batch, zdiv=zdiv, sA=sA2,
-                sB=sB2, sC=sC, accumulate=accumulate, act=act)
+    return _gemm_plain(A2, B2, C_, M, N, K, la=0, lb=0, lda=lda2, ldb=ldb2, ldc=ldc, a_off=a_off2, b_off=b_off2, c_off=c_off,
+                       alpha=alpha, bias=bias, rowvec=rowvec, residual=residual, ldr=ldr, batch=batch, zdiv=zdiv, sA=sA2,
+                       sB=sB2, sC=sC, accumulate=accumulate, act=act)
 
 
 def linear(x, w, out=None, *, out_dtype=None, residual=None, act=0, bias=None):
@@ -796,56 +818,59 @@ def _wgrad_x3_native(dy, x, dw, accumulate, M):
         if sk is None:      # a 64-wide K-tile of this kernel is three products: ~2.6 x the plain kernel's time per tile
             sk = _WGRAD_X3_PLAN[(N, K, T_)] = wgrad_splits(N, K, T_, torch.bfloat16, slots=256, tile=256, ktile_us=X3_WGRAD_KTILE_US)
     if sk <= 1:
-        return gemm(dy2[0], x2[0], dw, N, K, T_, la=1, lb=1, lda=ncols, ldb=K, ldc=dw.stride(0), accumulate=accumulate, x3_lo=lo) is not None
+        return _gemm_plain(dy2[0], x2[0], dw, N, K, T_, la=1, lb=1, lda=ncols, ldb=K, ldc=dw.stride(0), accumulate=accumulate, x3_lo=lo) is not None
     ws = torch.empty((sk, N, K), dtype=torch.float32, device=dw.device)
-    if gemm(dy2[0], x2[0], ws, N, K, T_, la=1, lb=1, lda=ncols, ldb=K, ldc=K, split_k=sk, split_stride=N * K, x3_lo=lo) is None:
+    if _gemm_plain(dy2[0], x2[0], ws, N, K, T_, la=1, lb=1, lda=ncols, ldb=K, ldc=K, split_k=sk, split_stride=N * K, x3_lo=lo) is None:
         return False
     check(lib().muse_sum_slices(ws.data_ptr(), dw.data_ptr(), sk, N * K, N * K, 1 if accumulate else 0, stream()), "muse_sum_slices")
     return True
 
 
 def planes_only_ok(rows, cols):
-    """may a producer hand its [rows, cols] result to the weight GEMMs as planes only?  (a bf16x3 step is running, the four-plane kernel
-    is on and takes products with this operand: >= 128 rows / columns, whole 16-byte rows)"""
-    on = ((_X3_IMAGES[0] is not None and _F32_AS_BF16X3[0] and X3_NATIVE and X3_PRODUCERS)
-          or (_F16_IMAGES[0] is not None and _F32_AS_F16[0] and F16_PRODUCERS))       # ("f16" mode: the result as its half image only)
-    return (on and X3_PLANES_ONLY and rows >= 128 and cols >= 128 and rows % 8 == 0 and cols % 8 == 0 and rows * cols * 2 < (1 << 31))
+    """may a producer hand its [rows, cols] result to the weight GEMMs as its operand image only?  (a step of either mode is running, its
+    producers are on and its kernels take products with this operand: >= 128 rows / columns, whole 16-byte rows)"""
+    return (X3_PLANES_ONLY and _PASS.kind is not None and _PASS.producing() is not None and rows >= 128 and cols >= 128
+            and rows % 8 == 0 and cols % 8 == 0 and rows * cols * 2 < (1 << 31))
 
 
 def linear_wgrad(dy, x, dw, accumulate, M=None, lda=None):
     """dw[N,K] (+)= dy[T,N]^T @ x[T,K]   (both operands k-major, f32 output into the flat grad buffer).
     Split-K slices write partial tiles to a workspace that muse_sum_slices folds into dw in a fixed order."""
-    if _F32_AS_F16[0] and dw.dtype == torch.float32 and dw.is_contiguous() and dw.data_ptr() % 16 == 0:
+    kind = _PASS.kind
+    if kind == "f16" and dw.dtype == torch.float32 and dw.is_contiguous() and dw.data_ptr() % 16 == 0:
         pair = f16_wgrad_operands(dy, x, M, lda)      # half operand images: dy is a gradient (the pass's scale), x a saved activation
         if pair is not None:
-            return linear_wgrad(pair[0], pair[1], dw, accumulate, M=M, lda=lda)
-    x3 = _F32_AS_BF16X3[0] and dy.dtype == torch.float32 and x.dtype == torch.float32 and dw.dtype == torch.float32 \
+            return _linear_wgrad_plain(pair[0], pair[1], dw, accumulate, M, lda)
+    x3 = kind == "bf16x3" and dy.dtype == torch.float32 and x.dtype == torch.float32 and dw.dtype == torch.float32 \
         and dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and x.shape[1] % 8 == 0 and (M if M is not None else dy.shape[1]) % 8 == 0
-    if not x3 and (isinstance(dy, Planes) or isinstance(x, Planes)):
-        raise _hip.MuseHipError("a planes-only operand reached a weight-gradient product outside the bf16x3 mode's preconditions")
-    if x3:
-        with f32_gemms_as_bf16x3(False):
-            if (X3_NATIVE and dy.dim() == 2 and x.dim() == 2 and dy.is_contiguous() and x.is_contiguous() and (lda is None or lda == dy.stride(0))
-                    and dy.shape[0] == x.shape[0] and _wgrad_x3_native(dy, x, dw, accumulate, M)):
-                return dw
-            if isinstance(dy, Planes) or isinstance(x, Planes):
-                raise _hip.MuseHipError("a planes-only operand reached a weight-gradient product the four-plane kernel does not take")
-            if (X3_CAT and dy.dim() == 2 and x.dim() == 2 and dy.is_contiguous() and x.is_contiguous() and (lda is None or lda == dy.stride(0))
-                    and dy.shape[0] == x.shape[0] and 3 * dy.numel() * 2 < (1 << 32) - 64 and 3 * x.numel() * 2 < (1 << 32) - 64):
-                # one product over 3 T slots: the ROW-concatenated images dY' [T, 3N] = (hi | lo | hi), X' [T, 3K] = (hi | hi | lo) - the ones
-                # the dX product of dY and the forward product of x made (X3Images) - read as [3T, N] / [3T, K]: slot 3t + s holds third s
-                # of token t in both, so the contraction over slots is sum_t hi hi + lo hi + hi lo
-                T_ = dy.shape[0]
-                dy3, _ = split_cat3(dy, 0, dy.shape[1], 1)
-                x3, _ = split_cat3(x, 0, x.shape[1], 2, last_use=True)
-                linear_wgrad(dy3.view(3 * T_, dy.shape[1]), x3.view(3 * T_, x.shape[1]), dw, accumulate, M=M, lda=lda)
-            else:                             # three bf16 products through the bf16 split-K machinery, accumulated in a fixed order
-                dyh, dyl = split_f32(dy)
-                xh, xl = split_f32(x)
-                linear_wgrad(dyh, xh, dw, accumulate, M=M, lda=lda)
-                linear_wgrad(dyh, xl, dw, True, M=M, lda=lda)
-                linear_wgrad(dyl, xh, dw, True, M=M, lda=lda)
+    if not x3:
+        if isinstance(dy, OperandOnly) or isinstance(x, OperandOnly):
+            raise _hip.MuseHipError("a planes-only operand reached a weight-gradient product outside the bf16x3 mode's preconditions")
+        return _linear_wgrad_plain(dy, x, dw, accumulate, M, lda)
+    whole = dy.dim() == x.dim() == 2 and dy.is_contiguous() and x.is_contiguous() and (lda is None or lda == dy.stride(0)) and dy.shape[0] == x.shape[0]
+    if X3_NATIVE and whole and _wgrad_x3_native(dy, x, dw, accumulate, M):
         return dw
+    if isinstance(dy, OperandOnly) or isinstance(x, OperandOnly):
+        raise _hip.MuseHipError("a planes-only operand reached a weight-gradient product the four-plane kernel does not take")
+    if X3_CAT and whole and 3 * dy.numel() * 2 < (1 << 32) - 64 and 3 * x.numel() * 2 < (1 << 32) - 64:
+        # one product over 3 T slots: the ROW-concatenated images dY' [T, 3N] = (hi | lo | hi), X' [T, 3K] = (hi | hi | lo) - the ones
+        # the dX product of dY and the forward product of x made (X3Images) - read as [3T, N] / [3T, K]: slot 3t + s holds third s
+        # of token t in both, so the contraction over slots is sum_t hi hi + lo hi + hi lo
+        T_ = dy.shape[0]
+        dy3, _ = split_cat3(dy, 0, dy.shape[1], 1)
+        xc3, _ = split_cat3(x, 0, x.shape[1], 2, last_use=True)
+        _linear_wgrad_plain(dy3.view(3 * T_, dy.shape[1]), xc3.view(3 * T_, x.shape[1]), dw, accumulate, M, lda)
+    else:                             # three bf16 products through the bf16 split-K machinery, accumulated in a fixed order
+        dyh, dyl = split_f32(dy)
+        xh, xl = split_f32(x)
+        _linear_wgrad_plain(dyh, xh, dw, accumulate, M, lda)
+        _linear_wgrad_plain(dyh, xl, dw, True, M, lda)
+        _linear_wgrad_plain(dyl, xh, dw, True, M, lda)
+    return dw
+
+
+def _linear_wgrad_plain(dy, x, dw, accumulate, M, lda):
+    """linear_wgrad on the operands as they are: one product, or split-K slices and their fixed-order sum"""
     T_, N = dy.shape
     if M is not None:
         N = M
@@ -853,10 +878,12 @@ def linear_wgrad(dy, x, dw, accumulate, M=None, lda=None):
     lda = lda or dy.stride(0)
     splittable = dw.dtype == torch.float32 and dw.is_contiguous() and (N * K) % 4 == 0
     sk = _wgrad_plan(dy, x, N, K, T_, lda, x.stride(0)) if splittable else 1
+    # (a bf16 / half pair: nothing for the mode prologue to route; anything else - f32, a mixed pair it routes or refuses - goes through it)
+    mm = _gemm_plain if dy.dtype == x.dtype != torch.float32 else gemm
     if sk <= 1:
-        return gemm(dy, x, dw, N, K, T_, la=1, lb=1, lda=lda, ldb=x.stride(0), ldc=dw.stride(0), accumulate=accumulate)
+        return mm(dy, x, dw, N, K, T_, la=1, lb=1, lda=lda, ldb=x.stride(0), ldc=dw.stride(0), accumulate=accumulate)
     ws = torch.empty((sk, N, K), dtype=torch.float32, device=dw.device)
-    gemm(dy, x, ws, N, K, T_, la=1, lb=1, lda=lda, ldb=x.stride(0), ldc=K, split_k=sk, split_stride=N * K)
+    mm(dy, x, ws, N, K, T_, la=1, lb=1, lda=lda, ldb=x.stride(0), ldc=K, split_k=sk, split_stride=N * K)
     check(lib().muse_sum_slices(ws.data_ptr(), dw.data_ptr(), sk, N * K, N * K, 1 if accumulate else 0, stream()),
           "muse_sum_slices")
     return dw
@@ -1302,7 +1329,7 @@ def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None
     """-> (dq [B*Sq, H], dk, dv [B*Skv, H]) f32; dq / dk / dv may be views (the column blocks of a packed gradient).
     planes = ((dq_hi, dq_lo_off), (dk_hi, ..), (dv_hi, ..)): hi-plane views shaped / strided like dq / dk / dv and the element distance
     to their lo planes (entries may be None) - the gradients also come out as operand planes (x3_new_planes of the packed tensor).
-    planes_only: no f32 gradients at all (dq / dk / dv stay None; the caller wraps the plane tensors in ops.Planes)"""
+    planes_only: no f32 gradients at all (dq / dk / dv stay None; the caller wraps the plane tensors: operand_only)"""
     require_gpu(q, k, v, ctx, dctx, lse)
     H = nh * hd
     planes = planes or (None, None, None)
@@ -1376,18 +1403,14 @@ def attention_bwd(qkv, ctx, dctx, lse, B, S, nh, hd, alpha):
     return dqkv
 
 
-X3_PLANES_ONLY = os.environ.get("MUSE_X3_PLANES_ONLY", "1") != "0"   # ... and skip the f32 result where only weight GEMMs read it (ops.Planes)
+X3_PLANES_ONLY = os.environ.get("MUSE_X3_PLANES_ONLY", "1") != "0"   # ... and skip the f32 result where only weight GEMMs read it (ops.OperandOnly)
 X3_PRODUCERS = os.environ.get("MUSE_X3_PRODUCERS", "1") != "0"   # bf16x3 mode: kernels whose f32 result feeds a product write its operand planes too
 F16_PRODUCERS = os.environ.get("MUSE_F16_PRODUCERS", "1") != "0"  # f16 mode: ... write its half image too (0: every operand through muse_cast_f32_to_f16)
 
 
 def _x3_producing(t):
     """the running step's image cache when a producer of `t`-like f32 results should write operand planes next to them"""
-    if _F32_AS_F16[0]:
-        im = _F16_IMAGES[0]
-        return im if (im is not None and F16_PRODUCERS and t.dtype == torch.float32 and t.is_contiguous()) else None
-    im = _X3_IMAGES[0]
-    return im if (im is not None and X3_NATIVE and X3_PRODUCERS and t.dtype == torch.float32 and t.is_contiguous()) else None
+    return _PASS.producing() if (t.dtype == torch.float32 and t.is_contiguous()) else None
 
 
 def x3_new_planes(t):
@@ -1402,18 +1425,16 @@ def x3_new_planes(t):
 def planes_alloc(shape, device):
     """the operand-image tensor a producer kernel of the running step writes for a [rows, cols] result: [2, rows, cols] bf16 (hi, lo
     planes, "bf16x3" mode) or [1, rows, cols] IEEE half ("f16" mode: _image_args tells the kernels which)"""
-    if _F32_AS_F16[0]:
-        return torch.empty((1,) + tuple(shape), dtype=torch.float16, device=device)
-    return torch.empty((2,) + tuple(shape), dtype=torch.bfloat16, device=device)
+    return torch.empty((_PASS.image_planes,) + tuple(shape), dtype=_PASS.image_dtype, device=device)
 
 
 def x3_put_planes(t, planes):
     if planes is not None:
-        (_F16_IMAGES[0] if _F32_AS_F16[0] else _X3_IMAGES[0]).put_planes(t, planes)
+        _PASS.images.put_planes(t, planes)
 
 
 def glu_fwd(ab, planes_only=False):
-    """planes_only (a bf16x3 step, see planes_only_ok): -> ops.Planes, the result as GEMM operand planes without its f32 tensor"""
+    """planes_only (see planes_only_ok): -> OperandOnly, the result as the running pass's GEMM operand image without its f32 tensor"""
     require_gpu(ab)
     rows, two_i = ab.shape
     if planes_only:
@@ -1421,7 +1442,7 @@ def glu_fwd(ab, planes_only=False):
             raise _hip.MuseHipError("glu_fwd(planes_only=True) outside planes_only_ok")
         planes = planes_alloc((rows, two_i // 2), ab.device)
         check(lib().muse_glu_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(False, planes), stream()), "muse_glu_fwd_x3")
-        return Planes(planes)
+        return operand_only(planes, False)
     h = torch.empty((rows, two_i // 2), dtype=ab.dtype, device=ab.device)
     im = _x3_producing(ab)
     if im is not None and (two_i // 2) % 8 == 0:
@@ -1443,7 +1464,7 @@ def glu_bwd(ab, dh, planes_only=False):
         planes = planes_alloc((rows, two_i), ab.device)
         check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(True, planes), stream()),
               "muse_glu_bwd_x3")
-        return Planes(planes)
+        return operand_only(planes, True)
     dab = torch.empty_like(ab)
     im = _x3_producing(ab)
     if im is not None and dh.dtype == torch.float32 and dh.is_contiguous() and two_i % 16 == 0:
@@ -2461,7 +2482,7 @@ def norm_adaln_ok(rows, cols, batch):
 
 def norm_adaln_fwd(x, w, ss, batch, eps, mode, residual=None, out_dtype=torch.float32, planes_only=False):
     """v = x (+ residual); m = Norm(v) * w * (1 + scale) + shift with (scale | shift) = ss [batch, 2C]  ->  (m in out_dtype, v).
-    planes_only (a bf16x3 step, planes_only_ok): m comes back as ops.Planes - operand planes without the f32 tensor"""
+    planes_only (planes_only_ok): m comes back as OperandOnly - the running pass's operand image without the f32 tensor"""
     require_gpu(x, ss)
     rows, cols = x.shape
     pre = torch.empty_like(x)
@@ -2471,7 +2492,7 @@ def norm_adaln_fwd(x, w, ss, batch, eps, mode, residual=None, out_dtype=torch.fl
         planes = planes_alloc((rows, cols), x.device)
         check(lib().muse_norm_adaln_fwd_x3(x.data_ptr(), ptr(residual), ptr(w), ss.data_ptr(), pre.data_ptr(), None, planes.data_ptr(),
                                            batch, rows // batch, cols, eps, mode, *_image_args(False, planes), stream()), "muse_norm_adaln_fwd_x3")
-        return Planes(planes), pre
+        return operand_only(planes, False), pre
     m = torch.empty((rows, cols), dtype=out_dtype, device=x.device)
     f32 = out_dtype == torch.float32
     im = _x3_producing(x) if f32 else None

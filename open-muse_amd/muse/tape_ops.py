@@ -521,7 +521,7 @@ class TapeOps:
                 pl = ops.planes_alloc(tuple(qkv.shape), qkv.device)
                 ops.attention_x3_bwd(q, qkv[:, Cq:2 * Cq], qkv[:, 2 * Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, planes_only=True,
                                      planes=((pl[0][:, :Cq], lo), (pl[0][:, Cq:2 * Cq], lo), (pl[0][:, 2 * Cq:], lo)))
-                dqkv = ops.Planes(pl)
+                dqkv = ops.operand_only(pl, True)
             else:
                 dqkv = torch.empty_like(qkv)
                 pl = None if blocked else ops.x3_new_planes(dqkv)       # ... or as f32 and planes, both out of the kernel
@@ -542,7 +542,7 @@ class TapeOps:
             plkv = ops.planes_alloc(tuple(qkv.shape), q.device)
             ops.attention_x3_bwd(q, qkv[:, :Cq], qkv[:, Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, planes_only=True,
                                  planes=((plq[0], q.numel()), (plkv[0][:, :Cq], qkv.numel()), (plkv[0][:, Cq:], qkv.numel())))
-            dq, dkv = ops.Planes(plq), ops.Planes(plkv)
+            dq, dkv = ops.operand_only(plq, True), ops.operand_only(plkv, True)
         else:
             dq = torch.empty_like(q)
             dkv = torch.empty_like(qkv)

@@ -1706,7 +1706,7 @@ def test_f16_mode_producers_write_half_images():
     muse_cast_f32_to_f16 makes of that result - unscaled in a forward pass, times the pass's gradient scale in a backward pass -
     registered under the result tensor so the product that reads it launches no cast; the f32 results are the plain kernels' bits
     (the attention core's, which computes in half itself inside the mode, to that precision).
-    A result only weight GEMMs read exists as its image alone (ops.Planes) and gives the same products."""
+    A result only weight GEMMs read exists as its image alone (ops.HalfImage) and gives the same products."""
     ops = _ops()
     rows, inter, C_, B = 512, 256, 512, 2
     ab, dh = rnd((rows, 2 * inter), 740).to(DEV), rnd((rows, inter), 741, 1e-5).to(DEV)
@@ -1756,11 +1756,11 @@ def test_f16_mode_producers_write_half_images():
             assert ops.planes_only_ok(rows, inter)
             if not bwd:
                 hp = ops.glu_fwd(ab, planes_only=True)
-                assert isinstance(hp, ops.Planes) and hp.half and torch.equal(hp.planes[0], ops.cast_to_f16(fused["h"]))
+                assert isinstance(hp, ops.HalfImage) and torch.equal(hp.planes[0], ops.cast_to_f16(fused["h"]))
                 assert torch.equal(ops.linear(hp, wl), ops.linear(fused["h"], wl))
             else:
                 dp = ops.glu_bwd(ab, dh, planes_only=True)
-                assert dp.half and dp.scale == S and torch.equal(dp.planes[0], ops.cast_to_f16(fused["dab"], S))
+                assert isinstance(dp, ops.HalfImage) and dp.scale == S and torch.equal(dp.planes[0], ops.cast_to_f16(fused["dab"], S))
                 w2 = rnd((2 * inter, 384), 749).to(DEV)
                 assert torch.equal(ops.linear_dgrad(dp, w2), ops.linear_dgrad(fused["dab"], w2))
                 g0, g1 = torch.empty((2 * inter, 384), device=DEV), torch.empty((2 * inter, 384), device=DEV)
@@ -1772,6 +1772,39 @@ def test_f16_mode_producers_write_half_images():
     with ops.f32_gemms_as_bf16x3(True, ops.X3Images()):
         h = ops.glu_fwd(ab)
         assert torch.equal(ops.split_planes(h), ops._split_planes_now(h))
+
+
+def test_f16_half_image_wrapped_after_its_pass_keeps_the_scale_it_was_given():
+    """An operand-only gradient carries the scale its producer kernel was GIVEN, not the state of whatever pass runs when it is wrapped:
+    in an f16 backward pass with gradient scale 2^19, glu_bwd(planes_only=True) writes the half image of a [136, 264] result (just above
+    the mode's floor: M, N >= 128, K >= 64, the 256^2 tile; planes-only needs >= 128 rows and columns in multiples of 8); the image is
+    wrapped as ops.HalfImage AFTER the scope has exited and consumed by linear_dgrad (K = 264 -> 200 columns) and linear_wgrad inside a
+    re-entered scope with the same images: the same bits as the f32 tensor's route through F16Images.image."""
+    import unittest.mock as um
+    ops = _ops()
+    M, N, K, S = 136, 264, 200, 2.0 ** 19
+    ab, dh = rnd((M, N), 760).to(DEV), rnd((M, N // 2), 761, 1e-5).to(DEV)
+    w, xx = rnd((N, K), 762).to(DEV), rnd((M, K), 763).to(DEV)
+    im = ops.F16Images(grad_scale=S)
+    im.backward = True
+    with ops.f32_gemms_as_f16(True, im):
+        assert ops.planes_only_ok(M, N)
+        dab = ops.glu_bwd(ab, dh)
+        planes = ops.glu_bwd(ab, dh, planes_only=True).planes
+    assert ops._PASS.kind is None
+    dp = ops.HalfImage(planes, S)                            # wrapped outside the pass: the scale is handed in
+    assert dp.scale == S and torch.equal(planes[0], ops.cast_to_f16(dab, S))
+    with ops.f32_gemms_as_f16(True, im):
+        calls = []
+        real = ops._gemm_plain
+        with um.patch.object(ops, "_gemm_plain", lambda A, *a, **k: (calls.append(A.dtype), real(A, *a, **k))[1]):
+            dx0, dx1 = ops.linear_dgrad(dab, w), ops.linear_dgrad(dp, w)
+            g0, g1 = torch.empty((N, K), device=DEV), torch.empty((N, K), device=DEV)
+            ops.linear_wgrad(dab, xx, g0, False)
+            ops.linear_wgrad(dp, xx, g1, False)
+        assert calls and all(d == torch.float16 for d in calls)      # all four products ran on half images
+    ops._F16_GUARDS.discard(im)
+    assert torch.equal(dx0, dx1) and torch.equal(g0, g1) and bool(torch.isfinite(g1).all()) and float(g1.abs().max()) > 0
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

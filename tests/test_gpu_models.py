@@ -254,13 +254,13 @@ def test_transformer_config_b_f16_mode_vs_reference_golden(golden_dir, gold):
     m, _ = _build_transformer(cfg, seed, "f16")
     from muse import ops
     halves = []
-    inner = ops.gemm
-    ops.gemm = lambda *a, **k: (halves.append(1) if a[0].dtype == torch.float16 else None, inner(*a, **k))[1]
+    inner = ops._gemm_plain                                # (where the mode's routes launch their half products)
+    ops._gemm_plain = lambda *a, **k: (halves.append(1) if a[0].dtype == torch.float16 else None, inner(*a, **k))[1]
     try:
         logits, loss = m(input_ids=ids.to(DEV), labels=labels.to(DEV))
         loss.backward()
     finally:
-        ops.gemm = inner
+        ops._gemm_plain = inner
     torch.cuda.synchronize()
     assert len(halves) >= 12 * 4 * 3                       # four Linears per layer: forward, dX, dW
     overflowed, flushed = m.f16_stats()
@@ -1319,8 +1319,8 @@ def test_flat_engine_f16_overflow_guard(grouped):
     opt = muse.FusedAdamW(params, lr=1e-3, betas=(0.9, 0.99), weight_decay=0.05, eps=1e-8)
     assert len(opt.param_groups) == (2 if grouped else 1)
     halves, launches = [], []
-    inner_gemm, inner_flat, inner_groups = ops.gemm, ops.adamw_flat, ops.adamw_flat_groups
-    ops.gemm = lambda *a, **k: (halves.append(1) if a[0].dtype == torch.float16 else None, inner_gemm(*a, **k))[1]
+    inner_gemm, inner_flat, inner_groups = ops._gemm_plain, ops.adamw_flat, ops.adamw_flat_groups
+    ops._gemm_plain = lambda *a, **k: (halves.append(1) if a[0].dtype == torch.float16 else None, inner_gemm(*a, **k))[1]
     ops.adamw_flat = lambda *a, **k: (launches.append("flat"), inner_flat(*a, **k))[1]
     ops.adamw_flat_groups = lambda *a, **k: (launches.append("groups"), inner_groups(*a, **k))[1]
     overflowed_steps, applied = 0, False
@@ -1362,7 +1362,7 @@ def test_flat_engine_f16_overflow_guard(grouped):
                 break
             scale_prev, skipped_prev = scale, skipped
     finally:
-        ops.gemm, ops.adamw_flat, ops.adamw_flat_groups = inner_gemm, inner_flat, inner_groups
+        ops._gemm_plain, ops.adamw_flat, ops.adamw_flat_groups = inner_gemm, inner_flat, inner_groups
     print("flat f16 guard: overflowed steps", overflowed_steps, "-> scale", m.f16_grad_scale, "; half products", len(halves))
     assert applied and overflowed_steps >= 1 and len(halves) > 0
 

@@ -736,7 +736,7 @@ def test_uvit_config4_vs_reference_golden(golden_dir):
         model.zero_grad(set_to_none=True)
         from muse import ops
         counts = {"attn": 0, "gemm_x3": 0, "gemm_f16": 0}
-        inner_a, inner_g = ops.attention_x3_fwd, ops.gemm
+        inner_a, inner_g = ops.attention_x3_fwd, ops._gemm_plain      # (_gemm_plain: where the modes' routes launch their products)
 
         def count_a(*a, **k):
             counts["attn"] += 1
@@ -747,12 +747,12 @@ def test_uvit_config4_vs_reference_golden(golden_dir):
             counts["gemm_x3"] += 1 if (k.get("x3_lo") is not None and r is not None) else 0
             counts["gemm_f16"] += 1 if a[0].dtype == torch.float16 else 0
             return r
-        ops.attention_x3_fwd, ops.gemm = count_a, count_g
+        ops.attention_x3_fwd, ops._gemm_plain = count_a, count_g
         try:
             logits, loss = model(ids, enc, cond, micro, labels=labels)
             loss.backward()
         finally:
-            ops.attention_x3_fwd, ops.gemm = inner_a, inner_g
+            ops.attention_x3_fwd, ops._gemm_plain = inner_a, inner_g
         if cd == "bf16x3":     # the mode's own kernels ran (no silent fallback to the materialised core / the K-concatenated product)
             print("bf16x3 step:", counts["attn"], "fused attention forwards,", counts["gemm_x3"], "four-plane products")
             assert counts["attn"] >= 2 * 22 and counts["gemm_x3"] >= 3 * 6 * 22

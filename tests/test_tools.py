@@ -98,7 +98,7 @@ def test_bf16x3_operand_image_cache_host_logic(monkeypatch):
         assert ops.split_planes(c) is made                        # forward images stay until the step ends
         im.clear()
         assert not im.persist and not im.lru
-    assert ops._X3_IMAGES[0] is None and not ops.planes_only_ok(512, 512)
+    assert ops._PASS.kind is None and ops._PASS.images is None and not ops.planes_only_ok(512, 512)      # no pass is running
     pl = ops.Planes(torch.zeros((2, 256, 128), dtype=torch.bfloat16))
     assert tuple(pl.shape) == (256, 128) and pl.dtype == torch.float32 and pl.stride() == (128, 1) and pl.stride(0) == 128
     assert pl.dim() == 2 and pl.numel() == 256 * 128 and pl.is_contiguous() and ops.split_planes(pl) is pl.planes and len(calls) == 9
@@ -152,17 +152,17 @@ def test_f16_mode_host_logic(monkeypatch):
     im.backward, im.keep = False, False                                   # inference forward: nothing persists
     im.image(a, 1.0)
     assert not im.persist and len(im.lru) == 1
-    # a planes-only half operand knows its scale
-    ops._F16_IMAGES[0] = im
-    try:
-        im.backward = True
-        pl = ops.Planes(torch.zeros((1, 256, 128), dtype=torch.float16))
-        assert pl.half and pl.scale == 2.0 ** 19 and tuple(pl.shape) == (256, 128) and pl.half_image()._muse_scale == 2.0 ** 19
+    # a planes-only half operand is given its scale: the one the running pass hands its producer kernels
+    im.backward = True
+    with ops.f32_gemms_as_f16(True, im):
+        pl = ops.operand_only(torch.zeros((1, 256, 128), dtype=torch.float16), True)
+        assert isinstance(pl, ops.HalfImage) and ops.operand_only(pl.planes, False).scale == 1.0
+        assert pl.scale == 2.0 ** 19 and tuple(pl.shape) == (256, 128) and pl.half_image()._muse_scale == 2.0 ** 19
         assert im.image(pl, 1.0).data_ptr() == pl.planes.data_ptr()
         with pytest.raises(MuseHipError):
             im.image(ops.Planes(torch.zeros((2, 256, 128), dtype=torch.bfloat16)), 1.0)
-    finally:
-        ops._F16_IMAGES[0] = None
+    assert ops._PASS.kind is None and im in ops._F16_GUARDS                # (a backward pass leaves its overflow guard behind)
+    ops._F16_GUARDS.discard(im)
 
     class Host(tape_ops.TapeOps):
         pass
@@ -175,6 +175,144 @@ def test_f16_mode_host_logic(monkeypatch):
     assert h.f16_update_grad_scale(growth_interval=2) is True and h.f16_grad_scale == 2.0 ** 18
     assert h.f16_update_grad_scale(growth_interval=2) is True and h.f16_grad_scale == 2.0 ** 19       # two good steps: double
     assert h.f16_update_grad_scale(growth_interval=2) is True and h.f16_grad_scale == 2.0 ** 19
+
+
+def _ops():
+    import sys
+    if os.path.join(ROOT, "open-muse_amd") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "open-muse_amd"))
+    from muse import ops
+    return ops
+
+
+def test_gemm_prologue_and_plain_body_stay_in_step(monkeypatch):
+    """CPU: ops.gemm forwards to ops._gemm_plain positionally, so the two parameter lists must be the same names in the same order with
+    the same defaults (the leading dimensions, which gemm requires, aside); and a weight gradient of a mixed-dtype pair still goes through
+    gemm's prologue, which refuses it - only a bf16 / half pair may skip it."""
+    import inspect
+    import torch
+    ops = _ops()
+    from muse._hip import MuseHipError
+    pg, pp = inspect.signature(ops.gemm).parameters, inspect.signature(ops._gemm_plain).parameters
+    assert list(pg) == list(pp)
+    for name in pg:
+        if name not in ("lda", "ldb", "ldc"):
+            assert pg[name].default == pp[name].default, name
+    monkeypatch.setattr(ops, "require_gpu", lambda *a: None)
+    monkeypatch.setattr(ops, "_gemm_plain", lambda *a, **k: (_ for _ in ()).throw(AssertionError("a mixed pair reached the launch")))
+    dw = torch.zeros(9, 7)                                   # (9 * 7 is no multiple of 4: one product, no split-K plan)
+    for dy_dt, x_dt in ((torch.bfloat16, torch.float32), (torch.float32, torch.bfloat16), (torch.float16, torch.bfloat16)):
+        with pytest.raises(MuseHipError, match="share a dtype"):
+            ops.linear_wgrad(torch.zeros(16, 9, dtype=dy_dt), torch.zeros(16, 7, dtype=x_dt), dw, False)
+    with ops.f32_gemms_as_f16(True):                         # (half, f32) in an f16 pass is the prologue's to route or refuse, too
+        with pytest.raises(MuseHipError, match="share a dtype"):
+            ops.linear_wgrad(torch.zeros(16, 9, dtype=torch.float16), torch.zeros(16, 7), dw, False)
+
+
+def test_compute_pass_scopes_restore_the_previous_pass():
+    """CPU: ops.f32_gemms_as_bf16x3 / f32_gemms_as_f16 set the ONE running pass (ops._PASS) and put the previous one back - also when the
+    body raises; on=False of the running mode stops the routing (the step's split cache stays readable), on=False of the other mode
+    leaves the running pass alone."""
+    ops = _ops()
+
+    def state():
+        return ops._PASS.kind, ops._PASS.images
+    assert state() == (None, None)
+    im = ops.X3Images()
+    with ops.f32_gemms_as_bf16x3(True, im):
+        assert state() == ("bf16x3", im) and ops._PASS.x3 is im
+        with ops.f32_gemms_as_bf16x3(False):
+            assert state() == (None, im) and ops._PASS.x3 is im
+        assert state() == ("bf16x3", im)
+        with ops.f32_gemms_as_f16(False):                      # the other mode's "off" does not touch a running pass
+            assert state() == ("bf16x3", im)
+        with ops.f32_gemms_as_bf16x3(True):                    # route, do not cache
+            assert state() == ("bf16x3", None)
+        assert state() == ("bf16x3", im)
+    assert state() == (None, None)
+    with pytest.raises(KeyError):
+        with ops.f32_gemms_as_bf16x3(True, im):
+            raise KeyError("inside")
+    assert state() == (None, None)
+    f16 = ops.F16Images()
+    with ops.f32_gemms_as_f16(True, f16):
+        assert state() == ("f16", f16) and ops._PASS.x3 is None
+        with ops.f32_gemms_as_bf16x3(False):
+            assert state() == ("f16", f16)
+        with ops.f32_gemms_as_f16(False):
+            assert state() == (None, None)
+        assert state() == ("f16", f16)
+    assert state() == (None, None) and f16 not in ops._F16_GUARDS          # (a forward pass leaves no overflow guard)
+    with ops.f32_gemms_as_f16() as scope:                                  # no images given: a private F16Images
+        assert isinstance(scope.images, ops.F16Images) and ops._PASS.images is scope.images
+    assert state() == (None, None)
+
+
+def test_operand_only_classes_refuse_the_other_format_and_keep_their_scale():
+    """CPU: ops.Planes holds bf16 (hi, lo) planes only, ops.HalfImage one half image and the scale it was GIVEN - also when it is built
+    after the pass that wrote it has exited; split_planes refuses a half image."""
+    import torch
+    ops = _ops()
+    from muse._hip import MuseHipError
+    half, planes = torch.zeros((1, 256, 128), dtype=torch.float16), torch.zeros((2, 256, 128), dtype=torch.bfloat16)
+    with pytest.raises(MuseHipError):
+        ops.HalfImage(planes, 1.0)
+    with pytest.raises(MuseHipError):
+        ops.Planes(half)
+    with pytest.raises(MuseHipError):
+        ops.split_planes(ops.HalfImage(half, 1.0))
+    im = ops.F16Images(grad_scale=2.0 ** 19)
+    im.backward = True
+    with ops.f32_gemms_as_f16(True, im):
+        scale = ops._PASS.scale(True)                          # what _image_args hands the producer kernel
+    ops._F16_GUARDS.discard(im)
+    hi = ops.HalfImage(half, scale)                            # wrapped after the pass: the scale is the one passed in, not ambient state
+    assert ops._PASS.kind is None and hi.scale == 2.0 ** 19 and hi.half_image()._muse_scale == 2.0 ** 19
+    assert isinstance(hi, ops.OperandOnly) and isinstance(ops.Planes(planes), ops.OperandOnly) and hi.dtype == torch.float32
+    assert tuple(hi.shape) == (256, 128) and hi.stride() == (128, 1) and hi.dim() == 2 and hi.numel() == 256 * 128 and hi.is_contiguous()
+    assert isinstance(ops.operand_only(planes, True), ops.Planes)          # no f16 pass running: bf16 planes
+
+
+def test_image_caches_share_one_store_policy(monkeypatch):
+    """CPU: X3Images and F16Images over the same scripted sequence (recent = 2): forward images are kept for the step, backward images -
+    a producer's included - go to the short LRU and the oldest is evicted at `recent`, a forward image nobody keeps (F16Images.keep =
+    False) goes to the LRU too.  The (persist, lru) sizes and the hit / miss / produced counts are what the two separate classes gave
+    before they shared a base."""
+    import torch
+    ops = _ops()
+    monkeypatch.setattr(ops, "_split_planes_now", lambda t: torch.zeros((2,) + tuple(t.shape), dtype=torch.bfloat16))
+
+    def fake_cast(t, scale=1.0, stats=None):
+        out = torch.zeros(t.shape, dtype=torch.float16)
+        out._muse_scale = float(scale)
+        return out
+    monkeypatch.setattr(ops, "cast_to_f16", fake_cast)
+    monkeypatch.setattr(ops.F16Images, "_ensure_stats", lambda self, device=None: None)
+
+    def script(im, make, made):
+        ts = [torch.zeros(8, 16) for _ in range(8)]
+        sizes = []
+        for t in ts[:3]:
+            make(im, t)
+        sizes.append((len(im.persist), len(im.lru)))
+        im.backward = True
+        for t in ts[3:6]:
+            make(im, t)
+        sizes.append((len(im.persist), len(im.lru)))
+        im.put_planes(ts[6], made)
+        sizes.append((len(im.persist), len(im.lru)))
+        make(im, ts[0])
+        make(im, ts[6])
+        im.backward = False
+        if isinstance(im, ops.F16Images):
+            im.keep = False
+            make(im, ts[7])
+            sizes.append((len(im.persist), len(im.lru)))
+        return sizes, (im.hits, im.misses, im.produced)
+    assert script(ops.X3Images(recent=2), lambda im, t: im.planes(t), torch.zeros((2, 8, 16), dtype=torch.bfloat16)) \
+        == ([(3, 0), (3, 2), (3, 2)], (2, 6, 1))
+    assert script(ops.F16Images(recent=2), lambda im, t: im.image(t, im.grad_scale if im.backward else 1.0),
+                  torch.zeros((1, 8, 16), dtype=torch.float16)) == ([(3, 0), (3, 2), (3, 2), (3, 2)], (2, 7, 1))
 
 
 def test_bf16x3_attention_shape_logic_and_step_timeline_on_cpu(tmp_path):
