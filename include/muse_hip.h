@@ -192,6 +192,21 @@ int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo
  * (*_planes, optional: the result ALSO as the bf16 operand planes of the products that read it - muse_gemm_x3 - so that no split pass
  *  runs over it: the hi plane is addressed exactly like the f32 tensor (same strides, in elements), the lo plane sits *_lo elements
  *  behind it; NULL = f32 only) */
+/* muse_attention_x3_fwd / _bwd with nn.Dropout(p) on the probabilities applied inside the kernels (the bf16x3 / f16 modes' counterpart of
+ * muse_attention_drop_fwd_ex / _bwd_ex; the same mask contract): the keep bit of (bh, query q, key k) of this launch is the bit
+ * muse_dropout(seed, offset) produces for flat element (bh * sq_total + q0 + q) * ld_mask + k0 + k of the FULL-sequence
+ * [batch * heads, sq_total, ld_mask] mask - q0 / k0 are the global indices of the launch's first query / key, so the block-by-block routes of
+ * the longer sequences (256-query blocks against <= 96 text states; block pairs merged by their log-sum-exps) draw the full-sequence mask.
+ * Row maximum, row sum and lse use the undropped P; P keep / (1 - p) is formed in f32, then split into planes / converted to half;
+ * backward: dsum = dO . O of the (dropped) final context, dP_eff = keep / (1 - p) dP in f32, dS = P (dP_eff - dsum), dV from the dropped P.
+ * ld_mask % 4 == 0, k0 % 4 == 0, k0 + seq_kv <= ld_mask, q0 + seq_q <= sq_total, 0 <= p < 1: else MUSE_ERR_BAD_ARG. */
+int muse_attention_x3_drop_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, float p, uint64_t seed, uint64_t offset,
+                               int64_t ld_mask, int64_t q0, int64_t k0, int64_t sq_total, int32_t half, float scale, int32_t* stats, void* stream);
+int muse_attention_x3_drop_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq, int64_t lddq,
+                               int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv, void* dq_planes,
+                               int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo, float p, uint64_t seed,
+                               uint64_t offset, int64_t ld_mask, int64_t q0, int64_t k0, int64_t sq_total, int32_t half, float scale,
+                               int32_t* stats, void* stream);
 /* Streaming forms for sequences of whole 256-row blocks on BOTH sides (round 6: the self-attention of BASELINE config 4's 1024 tokens;
  * reference modeling_transformer_v2.py:881-915).  d describes the FULL sequences (seq_q, seq_kv multiples of 256, head_dim 64; batch
  * strides of the whole tensors).  _fwd_stream: a workgroup keeps 256 queries and streams the key blocks through LDS with an online
@@ -231,6 +246,21 @@ int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32
                     void* stream);
 int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, int32_t half, float scale,
                     int32_t* stats, void* stream);
+/* GLU followed by nn.Dropout (MaskGiTUViT's `hidden_dropout`, reference muse/modeling_transformer_v2.py:933,947) in ONE pass: the keep
+ * bit of element r * inter + c of the [rows, inter] result is the bit muse_dropout(seed, offset) produces for that flat element (Philox
+ * block offset + (e >> 2), word e & 3, kept iff u >= p; scale 1 / (1 - p) in f32).  forward: h = keep * s * (gelu_erf(a) * b), one f32
+ * product before the output rounding / the plane split / the half image;  backward: keep * s * dh in f32, then muse_glu_bwd's
+ * expressions.  The _x3 forms write the operand image like muse_glu_fwd_x3 / _bwd_x3 (h / dab may be NULL: image only).  p = 0 keeps
+ * every element (the caller uses the plain entry points).  inter % 4 != 0: MUSE_ERR_UNSUPPORTED (a thread's four columns are one Philox
+ * block; the caller then applies muse_dropout to the plain result);  p < 0 or p >= 1: MUSE_ERR_BAD_ARG. */
+int muse_glu_drop_fwd(const void* ab, void* h, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
+                      void* stream);
+int muse_glu_drop_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed,
+                      uint64_t offset, void* stream);
+int muse_glu_drop_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
+                         int32_t half, float scale, int32_t* stats, void* stream);
+int muse_glu_drop_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed,
+                         uint64_t offset, int32_t half, float scale, int32_t* stats, void* stream);
 /* Fused middle of the NormFormer GLU MLP (muse/modeling_transformer.py:789-797), one pass over ab = [rows, 2*inter]:
  *   fwd: h = gelu_erf(a) * b, hm = LayerNorm(h) * w (mean/rstd saved);
  *   bwd: dh = LN'(dhm) never leaves the CU, dab = (dh*b*gelu'(a), dh*gelu(a)); dw_partial [ceil(rows/R), inter] f32 with
@@ -640,6 +670,15 @@ int muse_grn_fwd(const float* x, const float* gamma, const float* beta, float* y
 /* ... with the f32 result and / or its bf16 copy (the next GEMM's operand in the bf16 compute mode); either pointer may be null */
 int muse_grn_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch, int32_t batch,
                     int64_t S, int32_t C, void* stream);
+/* muse_grn_fwd_ex followed by nn.Dropout (ResBlock.channelwise[3], reference :607) in the same pass: the statistics see the undropped
+ * input, the result is multiplied by muse_dropout(seed, offset)'s keep bit of flat element (b * S + s) * C + c, scale 1 / (1 - p).
+ * muse_grn_drop_bwd: muse_grn_bwd with that mask, redrawn, applied to dy before everything else (the dgamma / dbeta sums included).
+ * C % 4 != 0 (or a shape the four-channel kernels do not index): MUSE_ERR_UNSUPPORTED, nothing launched - the caller runs the plain
+ * entry point and muse_dropout.  Pointers 16-byte aligned (y_bf16: 8), else MUSE_ERR_ALIGN. */
+int muse_grn_drop_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch, int32_t batch,
+                         int64_t S, int32_t C, float p, uint64_t seed, uint64_t offset, void* stream);
+int muse_grn_drop_bwd(const float* dy, const float* x, const float* gamma, const float* stats, float* dx, float* work, int32_t batch,
+                      int64_t S, int32_t C, float p, uint64_t seed, uint64_t offset, void* stream);
 int muse_sinusoidal_encode(const float* f, float* out, int64_t n, int32_t dim, float max_positions, void* stream);
 int muse_weighted_mean(const float* v, const float* w, float* out, int64_t n, void* stream);
 /* backward of the above (f32).  v = the forward's pre-norm sum x (+ res); dv = dx = dres; dw_partial [nblk, cols] is folded

@@ -25,6 +25,7 @@
 // two workgroups share a CU and overlap each other's phases.  Gradient operands (dO, dS) are converted times the pass's power-of-two
 // gradient scale S and the results handed back divided by it: dO S, -dsum S -> S (dP - dsum) -> S dS -> S dQ, S dK; P^T (dO S) = S dV.
 #include "attention_blocks.h"
+#include "philox.h"   // DROP instantiations: muse_dropout's keep bits, drawn in the kernel
 #include "../../include/muse_hip.h"
 
 namespace attn3 {
@@ -56,7 +57,81 @@ struct Params {
   // streaming forms (longer sequences: whole multiples of 256 queries / keys; q, k, v, o, dO, dq, dk, dv are the FULL-sequence tensors):
   int nqb, nkj;        // query blocks (= gridDim.y of the forward / dQ kernels) and key blocks (= gridDim.y of the dK / dV kernel)
   float* dsum;         // [nqb][B * nh][256]: dO . O per query, written by the dQ kernel, read by the dK / dV kernel
+  // DROP instantiations: nn.Dropout on the probabilities.  The keep bit of (bh, query q, key k) is muse_dropout(seed, offset)'s bit of flat
+  // element (bh * sq_total + q0 + q) * ld_mask + k0 + k of the FULL-sequence [B * nh, sq_total, ld_mask] mask: q0 / k0 = global index of
+  // this launch's first query / key (block-by-block routes), ld_mask % 4 == 0, k0 % 4 == 0.  drop_s = 1 / (1 - p) in f32.
+  float drop_p, drop_s;
+  uint64_t drop_seed, drop_offset;
+  int ld_mask, q0, k0, sq_total;
 };
+
+// DROP: the four keep bits of Philox block `blk` of muse_dropout's stream (bit w: word w kept)
+__device__ __forceinline__ unsigned keep_bits4(const Params& P, uint64_t blk) {
+  const uint64_t c = P.drop_offset + blk;
+  const u4 r = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), MUSE_DROPOUT_TAG, 0u, (uint32_t)P.drop_seed, (uint32_t)(P.drop_seed >> 32));
+  return (u01_open_high(r.x) >= P.drop_p ? 1u : 0u) | (u01_open_high(r.y) >= P.drop_p ? 2u : 0u) | (u01_open_high(r.z) >= P.drop_p ? 4u : 0u) |
+         (u01_open_high(r.w) >= P.drop_p ? 8u : 0u);
+}
+// DROP, queries stationary (forward, backward phase 1): the lane's query row `erow` = flat index of (bh, q, key 32 kb) in the mask.  By
+// row_of_reg the lane of half h holds, per 4-aligned key group 16 Tp + 4 j, keys + h (register 4 (2 Tp) + j) and + 2 + h (register
+// 4 (2 Tp + 1) + j): words h and 2 + h of ONE Philox block, the other two words belonging to lane + 32 (the same query).  The halves
+// share the draws through one cross-half exchange: half h draws the four blocks of Tp = h, packs their 16 keep bits, and reads the
+// other half's.  x[r] = mult * x[r] + add for each of the 16 registers (add = 0: the dropped P; add = -dsum: dP_eff - dsum).
+__device__ __forceinline__ void drop_keys16(const Params& P, uint64_t erow, int h, f32x16& x, float add) {
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    mine |= keep_bits4(P, (erow + (uint64_t)(16 * h + 4 * j)) >> 2) << (4 * j);
+    __builtin_amdgcn_sched_barrier(0);      // one draw in flight at a time: interleaved, the blocks' words cost registers these kernels lack
+  }
+  const unsigned other = (unsigned)__shfl_xor((int)mine, 32, 64);
+  const unsigned b0 = h ? other : mine, b1 = h ? mine : other;      // the keep bits of the blocks of Tp = 0 / Tp = 1
+#pragma unroll
+  for (int Tp = 0; Tp < 2; ++Tp)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned b = (Tp ? b1 : b0) >> (4 * j + h);
+      x[4 * (2 * Tp) + j] = fmaf((b & 1u) ? P.drop_s : 0.f, x[4 * (2 * Tp) + j], add);
+      x[4 * (2 * Tp + 1) + j] = fmaf((b & 4u) ? P.drop_s : 0.f, x[4 * (2 * Tp + 1) + j], add);
+    }
+}
+// DROP, keys stationary (backward phase 2): the lane owns key column `ecol` = k0 + key, register r is query q0 + 32 qb + row_of_reg(r, h).
+// The four lanes of a key quad (keys 4 g .. 4 g + 3, the same queries) share the draws as in csrc/attention.hip: quad lane i draws the
+// blocks of registers 4 T + i and packs their keep bits; every lane then reads quad lane j's bits through DPP quad_perm and takes bit
+// (its own key & 3) of register 4 T + j.  p_and_ds<true> with the mask in the same pass over the registers:
+// s <- P keep s (the operand of dV), dp <- P (keep s dP - dsum) = dS; dp arrives as the raw dP.  l2p / dsp: the block's lse log2(e) and
+// -dsum in LDS at this half's offset.  (All 64 lanes are active here: `own` is wave-uniform.)
+template <int J>
+__device__ __forceinline__ unsigned quad_bits(unsigned bits) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)bits, J * 0x55, 0xf, 0xf, true);   // quad_perm:[J,J,J,J]
+}
+__device__ __forceinline__ void drop_p_and_ds_queries16(const Params& P, uint64_t bh_row0, uint64_t ecol, int h, f32x16& s, f32x16& dp, float c,
+                                                        const float* l2p, const float* dsp) {
+  const int i = (int)(ecol & 3);
+  const uint64_t col4 = ecol - (uint64_t)i;
+  unsigned mine = 0;
+#pragma unroll
+  for (int T = 0; T < 4; ++T) {
+    // (row_of_reg(4 T + i, h) with a run-time i: 16 (T >> 1) + 4 i + 2 (T & 1) + h)
+    const uint64_t e = (bh_row0 + (uint64_t)(16 * (T >> 1) + 4 * i + 2 * (T & 1) + h)) * (uint64_t)P.ld_mask + col4;
+    mine |= keep_bits4(P, e >> 2) << (4 * T);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  const unsigned q0b = quad_bits<0>(mine) >> i, q1b = quad_bits<1>(mine) >> i, q2b = quad_bits<2>(mine) >> i, q3b = quad_bits<3>(mine) >> i;
+#pragma unroll
+  for (int T = 0; T < 4; ++T) {
+    const f32x4 l2 = *(const f32x4*)(l2p + 8 * T), ds = *(const f32x4*)(dsp + 8 * T);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * T + j;
+      const unsigned b = (j == 0 ? q0b : j == 1 ? q1b : j == 2 ? q2b : q3b) >> (4 * T);
+      const float mu = (b & 1u) ? P.drop_s : 0.f;
+      const float pv = __builtin_amdgcn_exp2f(fmaf(s[r], c, -l2[j]));
+      dp[r] = pv * fmaf(mu, dp[r], ds[j]);
+      s[r] = pv * mu;
+    }
+  }
+}
 
 typedef _Float16 f16x8_ __attribute__((ext_vector_type(8)));
 // eight f32 values (times s) as one half fragment
@@ -219,7 +294,21 @@ __device__ __forceinline__ void store_rows3(float* rowp, const f32x16 (&acc)[C::
 // =================================================================================================================
 // forward: wave w owns queries 32 w .. 32 w + 31
 // =================================================================================================================
-template <int NKB, bool H16 = false>
+// DROP forward, key blocks KB .. NKB - 1: exp, row sum, mask, P V.  A compile-time recursion instead of the unrolled loop of the p = 0
+// form: with eight Philox draws per block in its body the loop is no longer unrolled, and a run-time kb puts s[] into scratch.
+template <int KB, int NKB, bool H16>
+__device__ __forceinline__ void fwd_pv_drop(const Params& P, f32x16 (&s)[NKB], f32x16 (&o)[C::NDB], float& l, float c, float mc, uint64_t erow0,
+                                            const unsigned char* Vh, const unsigned char* Vl, const LaneGeom& g) {
+  if constexpr (KB < NKB) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[KB][r] = __builtin_amdgcn_exp2f(fmaf(s[KB][r], c, -mc)); l += s[KB][r]; }
+    drop_keys16(P, erow0 + 32 * KB, g.h, s[KB], 0.f);      // (row maximum, row sum and lse are those of the undropped P)
+    mma_seq3<H16>(Vh, Vl, g, KB, s[KB], o);
+    fwd_pv_drop<KB + 1, NKB, H16>(P, s, o, l, c, mc, erow0, Vh, Vl, g);
+  }
+}
+
+template <int NKB, bool H16 = false, bool DROP = false>
 __global__ __launch_bounds__(NT, 2) void fwd_kernel(const Params P) {
   constexpr int PL = NKB * 32 * C::STR;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -250,11 +339,16 @@ __global__ __launch_bounds__(NT, 2) void fwd_kernel(const Params P) {
   f32x16 o[C::NDB];
 #pragma unroll
   for (int db = 0; db < C::NDB; ++db) o[db] = zero16();
+  if constexpr (DROP) {      // P keep s in f32, then the split / half conversion inside mma_seq3
+    const uint64_t erow0 = ((uint64_t)head * (uint64_t)P.sq_total + (uint64_t)(P.q0 + q)) * (uint64_t)P.ld_mask + (uint64_t)P.k0;
+    fwd_pv_drop<0, NKB, H16>(P, s, o, l, c, mc, erow0, Vh, Vl, g);
+  } else {
 #pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) {
+    for (int kb = 0; kb < NKB; ++kb) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { s[kb][r] = __builtin_amdgcn_exp2f(fmaf(s[kb][r], c, -mc)); l += s[kb][r]; }
-    mma_seq3<H16>(Vh, Vl, g, kb, s[kb], o);
+      for (int r = 0; r < 16; ++r) { s[kb][r] = __builtin_amdgcn_exp2f(fmaf(s[kb][r], c, -mc)); l += s[kb][r]; }
+      mma_seq3<H16>(Vh, Vl, g, kb, s[kb], o);
+    }
   }
   l += xhalf(l);
   const long oo = b * P.bo + (long)q * P.ldo + hh * HD;
@@ -275,7 +369,7 @@ __device__ __forceinline__ void p_and_ds(f32x16& s, f32x16& dp, float c, const f
   }
 }
 
-template <int NKB, bool H16 = false>
+template <int NKB, bool H16 = false, bool DROP = false>
 __global__ __launch_bounds__(NT, 2) void bwd_kernel(const Params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char *Ah = smem, *Al = smem + PLANE, *Bh = smem + (H16 ? 1 : 2) * PLANE, *Bl = smem + 3 * PLANE;   // phase 1: K, V   phase 2: Q, dO
@@ -321,7 +415,11 @@ __global__ __launch_bounds__(NT, 2) void bwd_kernel(const Params P) {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
       f32x16 s = mma_rows3<H16>(Ah, Al, g, kb, qf, kb == NKB - 1 ? mask16(last_valid, g.h) : zero16());
-      f32x16 dp = mma_rows3<H16>(Bh, Bl, g, kb, dof, dsv);
+      f32x16 dp = mma_rows3<H16>(Bh, Bl, g, kb, dof, DROP ? zero16() : dsv);
+      if constexpr (DROP) {    // dP_eff = keep s dP in f32, then dS = P (dP_eff - dsum)
+        const uint64_t erow = ((uint64_t)head * (uint64_t)P.sq_total + (uint64_t)(P.q0 + q)) * (uint64_t)P.ld_mask + (uint64_t)(P.k0 + 32 * kb);
+        drop_keys16(P, erow, g.h, dp, -d);
+      }
       p_and_ds<false>(s, dp, c, l2v);
       mma_seq3<H16>(Ah, Al, g, kb, dp, dq);
     }
@@ -339,23 +437,31 @@ __global__ __launch_bounds__(NT, 2) void bwd_kernel(const Params P) {
     fill_two<SQ, H16>(Ah, Al, qh, P.ldq, Bh, Bl, doh, P.lddo, SQ, S);
     const FragB3 kf = split_raw<H16>(kr), vf = split_raw<H16>(vr);
     lds_barrier();
+    constexpr int QB_UNROLL = DROP ? 1 : SQ / 32;     // DROP: rolled - across unrolled blocks the draws' temporaries spill; p = 0: unrolled as before
     if (own) {
       f32x16 dk[C::NDB], dv[C::NDB];
 #pragma unroll
       for (int db = 0; db < C::NDB; ++db) { dk[db] = zero16(); dv[db] = zero16(); }
-#pragma unroll
+#pragma unroll QB_UNROLL
       for (int qb = 0; qb < SQ / 32; ++qb) {
         f32x16 l2v, dsv;
+        if constexpr (!DROP) {
 #pragma unroll
-        for (int T = 0; T < 4; ++T) {
-          const f32x4 a = *(const f32x4*)(L2 + qb * 32 + 8 * T + 4 * g.h);
-          const f32x4 dd = *(const f32x4*)(DS + qb * 32 + 8 * T + 4 * g.h);
+          for (int T = 0; T < 4; ++T) {
+            const f32x4 a = *(const f32x4*)(L2 + qb * 32 + 8 * T + 4 * g.h);
+            const f32x4 dd = *(const f32x4*)(DS + qb * 32 + 8 * T + 4 * g.h);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { l2v[4 * T + j] = a[j]; dsv[4 * T + j] = dd[j]; }
+            for (int j = 0; j < 4; ++j) { l2v[4 * T + j] = a[j]; dsv[4 * T + j] = dd[j]; }
+          }
         }
         f32x16 s = mma_rows3<H16>(Ah, Al, g, qb, kf, zero16());
-        f32x16 dp = mma_rows3<H16>(Bh, Bl, g, qb, vf, dsv);
-        p_and_ds<true>(s, dp, c, l2v);
+        f32x16 dp = mma_rows3<H16>(Bh, Bl, g, qb, vf, DROP ? zero16() : dsv);
+        if constexpr (DROP) {    // (dV from the dropped P, dK from dS = P (keep s dP - dsum))
+          const uint64_t row0 = (uint64_t)head * (uint64_t)P.sq_total + (uint64_t)(P.q0 + 32 * qb);
+          drop_p_and_ds_queries16(P, row0, (uint64_t)(P.k0 + key), g.h, s, dp, c, L2 + qb * 32 + 4 * g.h, DS + qb * 32 + 4 * g.h);
+        } else {
+          p_and_ds<true>(s, dp, c, l2v);
+        }
         mma_seq3<H16>(Bh, Bl, g, qb, s, dv);
         mma_seq3<H16>(Ah, Al, g, qb, dp, dk);
       }
@@ -573,10 +679,33 @@ static int check_stream(const muse_attn_desc* d) {
   return 0;
 }
 
+// the dropout arguments of the *_drop_* entry points (null: the p = 0 kernels)
+struct DropArgs { float p; uint64_t seed, offset; int64_t ld_mask, q0, k0, sq_total; };
+static int set_drop(Params& P, const muse_attn_desc* d, const DropArgs& a) {
+  if (!(a.p >= 0.0f && a.p < 1.0f) || a.ld_mask <= 0 || (a.ld_mask & 3) || a.q0 < 0 || a.k0 < 0 || (a.k0 & 3) || a.k0 + d->seq_kv > a.ld_mask ||
+      a.q0 + d->seq_q > a.sq_total || a.ld_mask > (1L << 30) || a.sq_total > (1L << 30))
+    return MUSE_ERR_BAD_ARG;
+  P.drop_p = a.p; P.drop_s = 1.0f / (1.0f - a.p); P.drop_seed = a.seed; P.drop_offset = a.offset;
+  P.ld_mask = (int)a.ld_mask; P.q0 = (int)a.q0; P.k0 = (int)a.k0; P.sq_total = (int)a.sq_total;
+  return 0;
+}
+
 }  // namespace attn3
 
+static int x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale, int32_t* stats, void* stream,
+                  const attn3::DropArgs* drop);
 extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale, int32_t* stats,
                                      void* stream) {
+  return x3_fwd(d, lse, o_planes, o_lo, half, scale, stats, stream, nullptr);
+}
+extern "C" int muse_attention_x3_drop_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, float p, uint64_t seed, uint64_t offset,
+                                          int64_t ld_mask, int64_t q0, int64_t k0, int64_t sq_total, int32_t half, float scale, int32_t* stats,
+                                          void* stream) {
+  const attn3::DropArgs a{p, seed, offset, ld_mask, q0, k0, sq_total};
+  return x3_fwd(d, lse, o_planes, o_lo, half, scale, stats, stream, &a);
+}
+static int x3_fwd(const muse_attn_desc* d, float* lse, void* o_planes, int64_t o_lo, int32_t half, float scale, int32_t* stats, void* stream,
+                  const attn3::DropArgs* drop) {
   using namespace attn3;
   const int rc = check(d);
   if (rc) return rc;
@@ -588,6 +717,14 @@ extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* 
   P.out = (float*)d->o; P.lse = lse;
   P.outp = (bf16_t*)o_planes; P.lo_out = f.lo_sign < 0 ? -1 : o_lo; P.img_scale = f.scale; P.img_stats = f.stats;
   const int nkb = nkb_of(d->seq_kv);
+  if (drop) {
+    if (const int e = set_drop(P, d, *drop)) return e;
+    const size_t lds = (f.lo_sign < 0 ? 2 : 4) * (size_t)nkb * 32 * C::STR;
+    const int nb = d->batch * d->heads;
+    hipStream_t st = (hipStream_t)stream;
+    if (f.lo_sign < 0) return nkb == 8 ? launch(fwd_kernel<8, true, true>, P, nb, lds, st) : launch(fwd_kernel<3, true, true>, P, nb, lds, st);
+    return nkb == 8 ? launch(fwd_kernel<8, false, true>, P, nb, lds, st) : launch(fwd_kernel<3, false, true>, P, nb, lds, st);
+  }
   if (f.lo_sign < 0) {      // the "f16" compute mode is on: the core's products are single half products like the mode's GEMMs
     const size_t lds = 2 * (size_t)nkb * 32 * C::STR;
     return nkb == 8 ? launch(fwd_kernel<8, true>, P, d->batch * d->heads, lds, (hipStream_t)stream)
@@ -598,10 +735,30 @@ extern "C" int muse_attention_x3_fwd(const muse_attn_desc* d, float* lse, void* 
                   : launch(fwd_kernel<3>, P, d->batch * d->heads, lds, (hipStream_t)stream);
 }
 
+static int x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
+                  int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
+                  void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
+                  int32_t half, float scale, int32_t* stats, void* stream, const attn3::DropArgs* drop);
 extern "C" int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
                                      int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
                                      void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
                                      int32_t half, float scale, int32_t* stats, void* stream) {
+  return x3_bwd(d, d_o, lddo, bsdo, lse, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv, dq_planes, dq_lo, dk_planes, dk_lo, dv_planes, dv_lo,
+                half, scale, stats, stream, nullptr);
+}
+extern "C" int muse_attention_x3_drop_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
+                                          int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
+                                          void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
+                                          float p, uint64_t seed, uint64_t offset, int64_t ld_mask, int64_t q0, int64_t k0, int64_t sq_total,
+                                          int32_t half, float scale, int32_t* stats, void* stream) {
+  const attn3::DropArgs a{p, seed, offset, ld_mask, q0, k0, sq_total};
+  return x3_bwd(d, d_o, lddo, bsdo, lse, dq, lddq, bsdq, dk, lddk, bsdk, dv, lddv, bsdv, dq_planes, dq_lo, dk_planes, dk_lo, dv_planes, dv_lo,
+                half, scale, stats, stream, &a);
+}
+static int x3_bwd(const muse_attn_desc* d, const void* d_o, int64_t lddo, int64_t bsdo, const float* lse, void* dq,
+                  int64_t lddq, int64_t bsdq, void* dk, int64_t lddk, int64_t bsdk, void* dv, int64_t lddv, int64_t bsdv,
+                  void* dq_planes, int64_t dq_lo, void* dk_planes, int64_t dk_lo, void* dv_planes, int64_t dv_lo,
+                  int32_t half, float scale, int32_t* stats, void* stream, const attn3::DropArgs* drop) {
   using namespace attn3;
   ImgFormat f;
   if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
@@ -621,6 +778,14 @@ extern "C" int muse_attention_x3_bwd(const muse_attn_desc* d, const void* d_o, i
   P.dqp = (bf16_t*)dq_planes; P.dkp = (bf16_t*)dk_planes; P.dvp = (bf16_t*)dv_planes; P.img_scale = f.scale; P.img_stats = f.stats;
   P.lo_dq = f.lo_sign < 0 ? -1 : dq_lo; P.lo_dk = f.lo_sign < 0 ? -1 : dk_lo; P.lo_dv = f.lo_sign < 0 ? -1 : dv_lo;
   P.gscale = f.lo_sign < 0 ? f.scale : 1.f;
+  if (drop) {
+    if (const int e = set_drop(P, d, *drop)) return e;
+    const size_t lds = (f.lo_sign < 0 ? 2 : 4) * (size_t)PLANE + 2 * SQ * sizeof(float);
+    const int nb = d->batch * d->heads, nkb = nkb_of(d->seq_kv);
+    hipStream_t st = (hipStream_t)stream;
+    if (f.lo_sign < 0) return nkb == 8 ? launch(bwd_kernel<8, true, true>, P, nb, lds, st) : launch(bwd_kernel<3, true, true>, P, nb, lds, st);
+    return nkb == 8 ? launch(bwd_kernel<8, false, true>, P, nb, lds, st) : launch(bwd_kernel<3, false, true>, P, nb, lds, st);
+  }
   if (f.lo_sign < 0) {
     const size_t lds = 2 * (size_t)PLANE + 2 * SQ * sizeof(float);
     return nkb_of(d->seq_kv) == 8 ? launch(bwd_kernel<8, true>, P, d->batch * d->heads, lds, (hipStream_t)stream)

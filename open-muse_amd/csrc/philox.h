@@ -18,3 +18,14 @@ __device__ __forceinline__ float u01_open_low(uint32_t r) { return ((float)(r >>
 __device__ __forceinline__ float u01_open_high(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }            // [0, 1)
 
 #define MUSE_DROPOUT_TAG 0x6D757365u   // counter word 2 of the dropout stream (word 3 is 0)
+
+// muse_dropout's multipliers (keep / (1 - p) = scale, or 0) of the four elements 4 * blk .. 4 * blk + 3 of the stream (seed, offset):
+// one Philox block, for the row kernels that apply nn.Dropout to four consecutive, 4-aligned columns of their own result
+__device__ __forceinline__ void dropout_mult4(uint64_t seed, uint64_t offset, uint64_t blk, float p, float scale, float (&m)[4]) {
+  const uint64_t c = offset + blk;
+  const u4 r = philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), MUSE_DROPOUT_TAG, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  m[0] = u01_open_high(r.x) >= p ? scale : 0.0f;
+  m[1] = u01_open_high(r.y) >= p ? scale : 0.0f;
+  m[2] = u01_open_high(r.z) >= p ? scale : 0.0f;
+  m[3] = u01_open_high(r.w) >= p ? scale : 0.0f;
+}

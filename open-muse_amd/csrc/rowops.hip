@@ -2,6 +2,7 @@
 // casts, mask sampling (the optimizer step is optim.hip).  All HBM-bound: 8/16-byte vector accesses, wave64 shuffle reductions, one wave per
 // row where a row fits a wave's registers.
 #include "common.h"
+#include "philox.h"   // the dropped forms draw muse_dropout's keep bits
 #include "../../include/muse_hip.h"
 
 // =================================================================================================================
@@ -1078,6 +1079,122 @@ extern "C" int muse_glu_bwd(const void* ab, const void* dh, void* dab, int32_t d
   const int g = ew_grid(rows * (inter / 4));
   if (dtype == MUSE_F32) hipLaunchKernelGGL(glu_bwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (const float*)dh, (float*)dab, (long)rows, inter);
   else hipLaunchKernelGGL(glu_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab, (long)rows, inter);
+  return (int)hipGetLastError();
+}
+
+// GLU with nn.Dropout on its output (reference muse/modeling_transformer_v2.py:933,947, the U-ViT's `hidden_dropout`): the keep bit of
+// muse_dropout(seed, offset) for flat element r * inter + c of the [rows, inter] result, applied inside the kernel.  A thread owns four
+// consecutive, 4-aligned columns = one Philox block.  forward: h = keep * s * (gelu(a) * b), one f32 product before the output rounding /
+// the plane split / the half image;  backward: d = keep * s * dh in f32, then the expressions of glu_bwd_kernel.  X3: the operand image
+// next to (or instead of: h / dab null) the result, as glu_*_x3_kernel.
+template <typename T, bool X3>
+__global__ void glu_drop_fwd_kernel(const T* __restrict__ ab, T* __restrict__ h, bf16_t* __restrict__ planes, long rows, int inter, ImgFormat f,
+                                    float p, float scale, uint64_t seed, uint64_t offset) {
+  const long n4 = rows * (inter / 4), plane = f.lo_sign * rows * inter;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / (inter / 4);
+    const int c = (int)(i - r * (inter / 4)) * 4;
+    float a[4], b[4], o[4], m[4];
+    V4<T>::load(ab + r * 2 * inter + c, a);
+    V4<T>::load(ab + r * 2 * inter + inter + c, b);
+    dropout_mult4(seed, offset, (uint64_t)i, p, scale, m);       // (r * inter + c) / 4 == i
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = m[j] != 0.0f ? (gelu_erf_t<sizeof(T) == 2>(a[j]) * b[j]) * m[j] : 0.0f;
+    if (h) V4<T>::store(h + r * inter + c, o);
+    if constexpr (X3) store_planes4(planes, plane, f, r * inter + c, o);
+  }
+}
+template <typename T, bool X3>
+__global__ void glu_drop_bwd_kernel(const T* __restrict__ ab, const T* __restrict__ dh, T* __restrict__ dab, bf16_t* __restrict__ planes,
+                                    long rows, int inter, ImgFormat f, float p, float scale, uint64_t seed, uint64_t offset) {
+  const long n4 = rows * (inter / 4), plane = f.lo_sign * rows * 2 * inter;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / (inter / 4);
+    const int c = (int)(i - r * (inter / 4)) * 4;
+    float a[4], b[4], d[4], da[4], db[4], m[4];
+    V4<T>::load(ab + r * 2 * inter + c, a);
+    V4<T>::load(ab + r * 2 * inter + inter + c, b);
+    V4<T>::load(dh + r * inter + c, d);
+    dropout_mult4(seed, offset, (uint64_t)i, p, scale, m);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float de = m[j] != 0.0f ? d[j] * m[j] : 0.0f;
+      da[j] = de * b[j] * gelu_erf_grad_t<sizeof(T) == 2>(a[j]);
+      db[j] = de * gelu_erf_t<sizeof(T) == 2>(a[j]);
+    }
+    if (dab) {
+      V4<T>::store(dab + r * 2 * inter + c, da);
+      V4<T>::store(dab + r * 2 * inter + inter + c, db);
+    }
+    if constexpr (X3) {
+      store_planes4(planes, plane, f, r * 2 * inter + c, da);
+      store_planes4(planes, plane, f, r * 2 * inter + inter + c, db);
+    }
+  }
+}
+static inline int glu_drop_args(const void* ab, int64_t rows, int32_t inter, float p) {
+  if (!ab || inter <= 0 || !(p >= 0.0f && p < 1.0f)) return MUSE_ERR_BAD_ARG;
+  if (inter % 4) return MUSE_ERR_UNSUPPORTED;     // a thread's four columns are one Philox block: the caller drops with muse_dropout
+  (void)rows;
+  return 0;
+}
+extern "C" int muse_glu_drop_fwd(const void* ab, void* h, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
+                                 void* stream) {
+  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
+  if (!h || (dtype != MUSE_F32 && dtype != MUSE_BF16)) return MUSE_ERR_BAD_ARG;
+  if (rows <= 0) return 0;
+  if ((((uintptr_t)ab) | ((uintptr_t)h)) & (dtype == MUSE_F32 ? 15 : 7)) return MUSE_ERR_ALIGN;
+  const int g = ew_grid(rows * (inter / 4));
+  const float scale = 1.0f / (1.0f - p);
+  const ImgFormat f{};
+  if (dtype == MUSE_F32)
+    hipLaunchKernelGGL((glu_drop_fwd_kernel<float, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (float*)h, (bf16_t*)nullptr,
+                       (long)rows, inter, f, p, scale, seed, offset);
+  else
+    hipLaunchKernelGGL((glu_drop_fwd_kernel<bf16_t, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (bf16_t*)h, (bf16_t*)nullptr,
+                       (long)rows, inter, f, p, scale, seed, offset);
+  return (int)hipGetLastError();
+}
+extern "C" int muse_glu_drop_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed,
+                                 uint64_t offset, void* stream) {
+  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
+  if (!dh || !dab || (dtype != MUSE_F32 && dtype != MUSE_BF16)) return MUSE_ERR_BAD_ARG;
+  if (rows <= 0) return 0;
+  if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & (dtype == MUSE_F32 ? 15 : 7)) return MUSE_ERR_ALIGN;
+  const int g = ew_grid(rows * (inter / 4));
+  const float scale = 1.0f / (1.0f - p);
+  const ImgFormat f{};
+  if (dtype == MUSE_F32)
+    hipLaunchKernelGGL((glu_drop_bwd_kernel<float, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (const float*)dh, (float*)dab,
+                       (bf16_t*)nullptr, (long)rows, inter, f, p, scale, seed, offset);
+  else
+    hipLaunchKernelGGL((glu_drop_bwd_kernel<bf16_t, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab,
+                       (bf16_t*)nullptr, (long)rows, inter, f, p, scale, seed, offset);
+  return (int)hipGetLastError();
+}
+extern "C" int muse_glu_drop_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
+                                    int32_t half, float scale, int32_t* stats, void* stream) {
+  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
+  ImgFormat f;
+  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
+  if (rows <= 0) return 0;
+  if (!planes) return MUSE_ERR_BAD_ARG;
+  // (the plain form's (rows * inter) & 3 check is implied here: inter % 4 == 0 was required above)
+  if ((((uintptr_t)ab) | ((uintptr_t)h)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
+  hipLaunchKernelGGL((glu_drop_fwd_kernel<float, true>), dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, h, (bf16_t*)planes,
+                     (long)rows, inter, f, p, 1.0f / (1.0f - p), seed, offset);
+  return (int)hipGetLastError();
+}
+extern "C" int muse_glu_drop_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed,
+                                    uint64_t offset, int32_t half, float scale, int32_t* stats, void* stream) {
+  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
+  ImgFormat f;
+  if (!dh || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
+  if (rows <= 0) return 0;
+  if (!planes) return MUSE_ERR_BAD_ARG;
+  if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
+  hipLaunchKernelGGL((glu_drop_bwd_kernel<float, true>), dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, dh, dab,
+                     (bf16_t*)planes, (long)rows, inter, f, p, 1.0f / (1.0f - p), seed, offset);
   return (int)hipGetLastError();
 }
 

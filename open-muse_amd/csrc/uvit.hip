@@ -4,6 +4,7 @@
 // backward, f32.
 // Everything else of that model (linears, attention, GLU, GELU, gather, cross-entropy) reuses the MaskGit kernels.
 #include "common.h"
+#include "philox.h"   // the dropped forms draw muse_dropout's keep bits
 #include "../../include/muse_hip.h"
 
 // =================================================================================================================
@@ -370,6 +371,46 @@ extern "C" int muse_grn_fwd_ex(const float* x, const float* gamma, const float* 
 extern "C" int muse_grn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* scratch, int32_t batch,
                             int64_t S, int32_t C, void* stream) {
   return muse_grn_fwd_ex(x, gamma, beta, y, nullptr, scratch, batch, S, C, stream);
+}
+// ... followed by nn.Dropout (ResBlock.channelwise[3], reference :607): grn_apply4_kernel with muse_dropout's keep bit of flat element
+// (b * S + s) * C + c applied to the result, after the statistics (which see the undropped input).  A thread's four channels are one
+// Philox block.
+__global__ __launch_bounds__(256) void grn_apply4_drop_kernel(const float* __restrict__ x, const float* __restrict__ nx,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C, float p, float scale,
+                                                              uint64_t seed, uint64_t offset) {
+  const int vpp = C >> 2, b = blockIdx.y;
+  const long base = (long)b * S * C;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < S * vpp; i += gridDim.x * 256) {
+    const int c = (i % vpp) * 4;
+    const long e = base + (long)(i / vpp) * C + c;
+    const f32x4 v = *(const f32x4*)(x + e), nn = *(const f32x4*)(nx + (long)b * C + c);
+    const f32x4 ga = *(const f32x4*)(gamma + c), be = *(const f32x4*)(beta + c);
+    float m[4];
+    dropout_mult4(seed, offset, (uint64_t)(e >> 2), p, scale, m);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = m[j] != 0.0f ? (ga[j] * (v[j] * nn[j]) + be[j] + v[j]) * m[j] : 0.0f;
+    if (y) *(f32x4*)(y + e) = o;
+    if (yb) *(u32x2*)(yb + e) = u32x2{pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3])};
+  }
+}
+extern "C" int muse_grn_drop_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch,
+                                    int32_t batch, int64_t S, int32_t C, float p, uint64_t seed, uint64_t offset, void* stream) {
+  if (!x || !gamma || !beta || !scratch || (!y && !y_bf16) || !(p >= 0.0f && p < 1.0f)) return MUSE_ERR_BAD_ARG;
+  const long n = (long)batch * S * C;
+  if (n <= 0) return 0;
+  if ((C & 3) || S * (long)(C >> 2) >= (1L << 31) || batch > 65535) return MUSE_ERR_UNSUPPORTED;   // (the caller drops with muse_dropout)
+  if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)gamma) | ((uintptr_t)beta) | ((uintptr_t)scratch)) & 15 || (((uintptr_t)y_bf16) & 7))
+    return MUSE_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  float* nx = scratch + (long)batch * C;
+  hipLaunchKernelGGL(grn_colnorm_kernel, dim3((C + 63) / 64, batch), dim3(256), 0, s, x, scratch, (long)S, C);
+  hipLaunchKernelGGL(grn_scale_kernel, dim3(batch), dim3(256), 0, s, (const float*)scratch, nx, C);
+  long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(grn_apply4_drop_kernel, dim3((unsigned)gx, batch), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (bf16_t*)y_bf16,
+                     (int)S, C, p, 1.0f / (1.0f - p), seed, offset);
+  return (int)hipGetLastError();
 }
 
 // =================================================================================================================
@@ -1135,6 +1176,74 @@ extern "C" int muse_grn_bwd(const float* dy, const float* x, const float* gamma,
   hipLaunchKernelGGL(grn_bwd_coef_kernel, dim3(batch), dim3(256), 0, s, stats, stats + bc, gamma, s1, K, C);
   long g = (n + 255) / 256; if (g > 65535) g = 65535;
   hipLaunchKernelGGL(grn_bwd_dx_kernel, dim3((unsigned)g), dim3(256), 0, s, dy, x, stats + bc, (const float*)K, gamma, dx, (long)S, C, n);
+  return (int)hipGetLastError();
+}
+
+// GlobalResponseNorm backward behind nn.Dropout (muse_grn_drop_fwd_ex): the incoming gradient is multiplied by the redrawn keep mask
+// before anything else reads it - the S0 / S1 sums (hence dgamma / dbeta) and dx.  A lane owns four consecutive channels (one Philox
+// block per row); the row order of each column's sum is grn_bwd_reduce_kernel's.
+__global__ __launch_bounds__(256) void grn_bwd_reduce4_drop_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                   float* __restrict__ s0, float* __restrict__ s1, long S, int C, float p,
+                                                                   float scale, uint64_t seed, uint64_t offset) {
+  __shared__ float r0[4][64][4], r1[4][64][4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + lane) * 4;
+  const long b = blockIdx.y;
+  float a[4] = {0.f, 0.f, 0.f, 0.f}, s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < C)
+    for (long r = wv; r < S; r += 4) {
+      const long e = (b * S + r) * C + c;
+      const f32x4 g = *(const f32x4*)(dy + e), v = *(const f32x4*)(x + e);
+      float m[4];
+      dropout_mult4(seed, offset, (uint64_t)(e >> 2), p, scale, m);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float ge = m[j] != 0.0f ? g[j] * m[j] : 0.0f; s[j] += ge; a[j] = fmaf(ge, v[j], a[j]); }
+    }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { r0[wv][lane][j] = s[j]; r1[wv][lane][j] = a[j]; }
+  __syncthreads();
+  if (wv == 0 && c < C) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s0[b * C + c + j] = (r0[0][lane][j] + r0[1][lane][j]) + (r0[2][lane][j] + r0[3][lane][j]);
+      s1[b * C + c + j] = (r1[0][lane][j] + r1[1][lane][j]) + (r1[2][lane][j] + r1[3][lane][j]);
+    }
+  }
+}
+__global__ __launch_bounds__(256) void grn_bwd_dx4_drop_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                               const float* __restrict__ N, const float* __restrict__ K,
+                                                               const float* __restrict__ gamma, float* __restrict__ dx, int S, int C, float p,
+                                                               float scale, uint64_t seed, uint64_t offset) {
+  const int vpp = C >> 2, b = blockIdx.y;
+  const long base = (long)b * S * C;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < S * vpp; i += gridDim.x * 256) {
+    const int c = (i % vpp) * 4;
+    const long e = base + (long)(i / vpp) * C + c;
+    const f32x4 g = *(const f32x4*)(dy + e), v = *(const f32x4*)(x + e);
+    const f32x4 nn = *(const f32x4*)(N + (long)b * C + c), kk = *(const f32x4*)(K + (long)b * C + c), ga = *(const f32x4*)(gamma + c);
+    float m[4];
+    dropout_mult4(seed, offset, (uint64_t)(e >> 2), p, scale, m);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float ge = m[j] != 0.0f ? g[j] * m[j] : 0.0f; o[j] = ge * (ga[j] * nn[j] + 1.0f) + v[j] * kk[j]; }
+    *(f32x4*)(dx + e) = o;
+  }
+}
+extern "C" int muse_grn_drop_bwd(const float* dy, const float* x, const float* gamma, const float* stats, float* dx, float* work,
+                                 int32_t batch, int64_t S, int32_t C, float p, uint64_t seed, uint64_t offset, void* stream) {
+  if (!dy || !x || !gamma || !stats || !dx || !work || !(p >= 0.0f && p < 1.0f)) return MUSE_ERR_BAD_ARG;
+  const long n = (long)batch * S * C, bc = (long)batch * C;
+  if (n <= 0) return 0;
+  if ((C & 3) || S * (long)(C >> 2) >= (1L << 31) || batch > 65535) return MUSE_ERR_UNSUPPORTED;   // (the caller drops dy with muse_dropout)
+  if ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)gamma) | ((uintptr_t)stats) | ((uintptr_t)dx) | ((uintptr_t)work)) & 15) return MUSE_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  float *s0 = work, *s1 = work + bc, *K = work + 2 * bc;
+  const float scale = 1.0f / (1.0f - p);
+  hipLaunchKernelGGL(grn_bwd_reduce4_drop_kernel, dim3((C / 4 + 63) / 64, batch), dim3(256), 0, s, dy, x, s0, s1, (long)S, C, p, scale, seed, offset);
+  hipLaunchKernelGGL(grn_bwd_coef_kernel, dim3(batch), dim3(256), 0, s, stats, stats + bc, gamma, s1, K, C);
+  long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(grn_bwd_dx4_drop_kernel, dim3((unsigned)gx, batch), dim3(256), 0, s, dy, x, stats + bc, (const float*)K, gamma, dx, (int)S, C, p,
+                     scale, seed, offset);
   return (int)hipGetLastError();
 }
 

@@ -75,6 +75,9 @@ SIGNATURES = {
     "muse_attention_x3_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_bwd": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
                               c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, *_IMG, c_void_p],
+    "muse_attention_x3_drop_fwd": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, c_float, C.c_uint64, C.c_uint64, c_i64, c_i64, c_i64, c_i64, *_IMG, c_void_p],
+    "muse_attention_x3_drop_bwd": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p,
+                                   c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_float, C.c_uint64, C.c_uint64, c_i64, c_i64, c_i64, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_fwd_stream": [C.POINTER(AttnDesc), c_void_p, c_void_p, c_i64, *_IMG, c_void_p],
     "muse_attention_x3_bwd_stream": [C.POINTER(AttnDesc), c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                      c_void_p, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, *_IMG, c_void_p],
@@ -88,6 +91,10 @@ SIGNATURES = {
     "muse_glu_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_glu_fwd_x3": [c_void_p, c_void_p, c_void_p, c_i64, c_int, *_IMG, c_void_p],
     "muse_glu_bwd_x3": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, *_IMG, c_void_p],
+    "muse_glu_drop_fwd": [c_void_p, c_void_p, c_int, c_i64, c_int, c_float, C.c_uint64, C.c_uint64, c_void_p],
+    "muse_glu_drop_bwd": [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_float, C.c_uint64, C.c_uint64, c_void_p],
+    "muse_glu_drop_fwd_x3": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, C.c_uint64, C.c_uint64, *_IMG, c_void_p],
+    "muse_glu_drop_bwd_x3": [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, C.c_uint64, C.c_uint64, *_IMG, c_void_p],
     "muse_ffn_mid_rows_per_block": [],
     "muse_ffn_mid_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p],
     "muse_ffn_mid_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
@@ -190,6 +197,10 @@ SIGNATURES = {
     "muse_space_to_depth2_nhwc": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "muse_grn_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
     "muse_grn_fwd_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p],
+    "muse_grn_drop_fwd_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_float, C.c_uint64, C.c_uint64,
+                             c_void_p],
+    "muse_grn_drop_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_float, C.c_uint64, C.c_uint64,
+                          c_void_p],
     "muse_sinusoidal_encode": [c_void_p, c_void_p, c_i64, c_int, c_float, c_void_p],
     "muse_weighted_mean": [c_void_p, c_void_p, c_void_p, c_i64, c_void_p],
     "muse_norm_res_bwd_nblk": [c_i64],

@@ -9,6 +9,8 @@ Everything computes through libmuse_hip.so on channels-last rows ``[B * S, C]``:
   linears / 1x1 convs / attention GEMMs -> muse_gemm;  embedding -> muse_gather_rows;  RMSNorm / LayerNorm with the pre-norm
   residual stream -> muse_norm_res_fwd;  AdaLN -> muse_adaln_fwd;  depthwise 3x3 -> muse_dwconv3x3_nhwc;  GlobalResponseNorm ->
   muse_grn_fwd;  GELU / GLU / softmax / cross-entropy -> the MaskGit kernels;  micro-conditioning -> muse_sinusoidal_encode.
+hidden_dropout / attention_dropout (training mode): Philox masks drawn per site from one seed per forward - hidden dropout inside the
+GLU / GRN kernels (muse_glu_drop_*, muse_grn_drop_*), attention dropout through TapeOps._attention(drop=); DESIGN 5k.
 """
 from __future__ import annotations
 
@@ -236,8 +238,9 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
             raise NotImplementedError("MI355X build of MaskGiTUViT_v2: only the bias-free GLU family is built (norm_type rmsnorm or "
                                       "layernorm, with or without learnable gains, with or without the forced down/up-sampling)")
         self.__dict__["_default_norm_mode"] = 1 if c.norm_type == "layernorm" else 0     # (Norm, reference :632-641)
-        if c.hidden_dropout != 0.0 or c.attention_dropout != 0.0:
-            raise NotImplementedError("dropout > 0 is outside the MI355X hot-path build")
+        for key in ("hidden_dropout", "attention_dropout"):      # nn.Dropout's own range check, minus p = 1 (the scale 1 / (1 - p) is infinite)
+            if not 0.0 <= float(getattr(c, key)) < 1.0:
+                raise ValueError(f"{key} has to be in [0, 1), but got {getattr(c, key)}")
         H, C, cin = c.hidden_size, c.block_out_channels[0], c.in_channels
         for width, heads in ((C, c.block_num_heads), (H, c.num_attention_heads)):     # Attention.__init__ of the reference (:842-847), same text:
             if width % heads != 0:                                                     # configs/cc12m_uvit_clip.yaml as shipped (1024 channels, 12 heads)
@@ -412,7 +415,65 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         self._ada_dss(dss, sv, ada, ada_name, G, scond, dscond)
         return dv
 
-    def _res_block(self, h, blk: _ResBlock, scond, B, side):
+    # ---- dropout (config.hidden_dropout / attention_dropout; active iff self.training) -----------------------------------------
+    # The reference's nn.Dropout modules: ResBlock.channelwise[3] (:607), Attention.dropout on the probabilities (:856,912) of every self-
+    # and cross-attention, GLUFeedForward.dropout (:933,947).  One 62-bit seed per forward; ONE counter over all sites in forward
+    # execution order, site k drawing muse_dropout's stream at Philox offset (k + 1) << 40.  No mask is kept: backward redraws it.
+    def _dropout_site_names(self):
+        """[(module path of the reference's nn.Dropout, "hidden" | "attention")] in forward execution order"""
+        c = self.config
+        names = []
+
+        def block(bname):
+            for i in range(c.num_res_blocks):
+                names.append((f"{bname}.res_blocks.{i}.channelwise.3", "hidden"))
+                names.append((f"{bname}.attention_blocks.{i}.attention.dropout", "attention"))
+                names.append((f"{bname}.attention_blocks.{i}.crossattention.dropout", "attention"))
+        block("down_blocks.0")
+        for li in range(c.num_hidden_layers):
+            nm = f"transformer_layers.{li}"
+            names += [(nm + ".attention.dropout", "attention"), (nm + ".crossattention.dropout", "attention"), (nm + ".ffn.dropout", "hidden")]
+        block("up_blocks.0")
+        return names
+
+    def dropout_sites(self, B, S, L):
+        """every dropout site of one forward over B images of S tokens (what the blocks see: a quarter of the input tokens under
+        force_down_up_sample) with L text states: [(module path of the reference's nn.Dropout, kind, Philox offset, mask shape)].
+        Element numbering inside a site is muse_dropout's over the row-major mask: hidden sites [B * S, cols] (cols = 4 C in a ResBlock,
+        intermediate_size in the feed-forward), attention sites [B * heads, S_q, round_up(S_kv, 8)]."""
+        c = self.config
+        C = c.block_out_channels[0]
+        out = []
+        for k, (name, kind) in enumerate(self._dropout_site_names()):
+            in_block = not name.startswith("transformer_layers.")
+            if kind == "hidden":
+                shape = (B * S, 4 * C if in_block else c.intermediate_size)
+            else:
+                skv = L if (in_block or ".crossattention." in name) else S      # (a conv-stage block's `attention` reads the text states too, :821-823)
+                shape = (B * (c.block_num_heads if in_block else c.num_attention_heads), S, (skv + 7) // 8 * 8)
+            out.append((name, kind, (k + 1) << 40, shape))
+        return out
+
+    def _draw_dropout(self):
+        """the running forward's {site name: (p, seed, offset)} (sites whose p is 0 are absent) - empty in eval mode"""
+        c = self.config
+        p_h = float(c.hidden_dropout) if self.training else 0.0
+        p_a = float(c.attention_dropout) if self.training else 0.0
+        seed = 0
+        pinned = self.__dict__.pop("_next_dropout_seed", None)      # (tests: an int, consumed by this forward)
+        if p_h > 0.0 or p_a > 0.0:
+            seed = int(pinned) if pinned is not None else int(torch.randint(0, 2 ** 62, (1,)))
+        self.__dict__["_last_dropout"] = (seed, p_h, p_a)
+        drops = {}
+        if p_h == 0.0 and p_a == 0.0:
+            return drops
+        for k, (name, kind) in enumerate(self._dropout_site_names()):
+            p = p_h if kind == "hidden" else p_a
+            if p > 0.0:
+                drops[name] = (p, seed, (k + 1) << 40)
+        return drops
+
+    def _res_block(self, h, blk: _ResBlock, scond, B, side, drop=None):
         C = h.shape[1]
         wdw = self._f(blk.depthwise.weight).contiguous()
         d = ops.dwconv3x3_nhwc(h, wdw, B, side, side, C)
@@ -422,18 +483,19 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         grn = blk.channelwise["2"]
         gamma = self._f(grn.gamma).reshape(-1).contiguous()
         # (g is only ever a GEMM operand - forward product and the dW product of the backward: bf16 mode gets it as bf16 from the kernel)
+        # (drop: channelwise[3] - nn.Dropout on GRN's output, applied inside its apply kernel)
         g, stats = ops.grn_fwd(ga, gamma, self._f(grn.beta).reshape(-1).contiguous(), B, side * side, want_stats=True,
-                               out_dtype=self.compute_dtype)
+                               out_dtype=self.compute_dtype, drop=drop)
         x = self._lin(g, blk.channelwise["4"], residual=h)                          # + x_res (:616)
         y, sva = self._adaln(x, blk.adaLN_modulation, scond, B)
-        return y, dict(h=h, d=d, n=n, a=a, ga=ga, g=g, stats=stats, gamma=gamma, wdw=wdw, ada=sva, side=side)
+        return y, dict(h=h, d=d, n=n, a=a, ga=ga, g=g, stats=stats, gamma=gamma, wdw=wdw, ada=sva, side=side, drop=drop)
 
     def _res_block_bwd(self, dy, sv, blk: _ResBlock, name, G, scond, dscond, B):
         C = sv["h"].shape[1]
         side = sv["side"]
         dx = self._adaln_bwd(dy, sv["ada"], blk.adaLN_modulation, name + ".adaLN_modulation", G, scond, dscond, B)
         dg = self._lin_bwd(dx, sv["g"], blk.channelwise["4"], name + ".channelwise.4", G)      # dx also flows to h (residual)
-        dga, dgam, dbet = ops.grn_bwd(dg, sv["ga"], sv["gamma"], sv["stats"], B, side * side)
+        dga, dgam, dbet = ops.grn_bwd(dg, sv["ga"], sv["gamma"], sv["stats"], B, side * side, drop=sv.get("drop"))
         grn = blk.channelwise["2"]
         G[name + ".channelwise.2.gamma"] = dgam.view(grn.gamma.shape)
         G[name + ".channelwise.2.beta"] = dbet.view(grn.beta.shape)
@@ -444,14 +506,14 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         G[name + ".depthwise.weight"] = dwdw
         return dh.add_(dx)                                                           # + residual path
 
-    def _attn_block(self, h, blk: _AttnBlock2D, enc, senc, B, S, L):
+    def _attn_block(self, h, blk: _AttnBlock2D, enc, senc, B, S, L, drops=(None, None)):
         has_map = hasattr(blk, "kv_mapper")
         ctx = self._lin(senc, blk.kv_mapper) if has_map else enc                      # :815-816
         nh = self.config.block_num_heads
         n1, _ = self._norm(h, blk.attn_layer_norm)                                    # residual = h (:819)
-        a1, s1 = self._attention(n1, ctx, blk.attention, B, S, L, nh)
+        a1, s1 = self._attention(n1, ctx, blk.attention, B, S, L, nh, drop=drops[0])
         n2, res = self._norm(a1, blk.crossattn_layer_norm, residual=h, want_pre=True)  # :822
-        y, s2 = self._attention(n2, ctx, blk.crossattention, B, S, L, nh, residual=res)  # + residual (:824)
+        y, s2 = self._attention(n2, ctx, blk.crossattention, B, S, L, nh, residual=res, drop=drops[1])  # + residual (:824)
         return y, dict(h=h, res=res, s1=s1, s2=s2, has_map=has_map)
 
     def _attn_block_bwd(self, dy, sv, blk: _AttnBlock2D, name, G, senc, denc, dsenc):
@@ -508,6 +570,7 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         H, C = c.hidden_size, c.block_out_channels[0]
         f = self._f
         T = {}                                                                        # the tape
+        D = self._draw_dropout()                                                      # {site: (p, seed, offset)}; empty in eval mode / at p = 0
         # text states :252-253
         enc_in = encoder_hidden_states.reshape(B * L, -1).float().contiguous()
         enc0 = self._lin(enc_in, self.encoder_proj)
@@ -536,8 +599,10 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
             T["downsample"] = dict(h=h, x2=x2, wd=wd)
             h = self._mm(x2, wd)
         for i in range(c.num_res_blocks):
-            h, sr = self._res_block(h, blk.res_blocks[i], scond, B, side)
-            h, sa = self._attn_block(h, blk.attention_blocks[i], enc, senc, B, S, L)
+            bn = f"down_blocks.0.res_blocks.{i}", f"down_blocks.0.attention_blocks.{i}"
+            h, sr = self._res_block(h, blk.res_blocks[i], scond, B, side, drop=D.get(bn[0] + ".channelwise.3"))
+            h, sa = self._attn_block(h, blk.attention_blocks[i], enc, senc, B, S, L,
+                                     drops=(D.get(bn[1] + ".attention.dropout"), D.get(bn[1] + ".crossattention.dropout")))
             T["down"].append((sr, sa))
         hd_in = h
         n, _ = self._norm(h, self.project_to_hidden_norm)
@@ -549,11 +614,12 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         # m1 / m2 / m3 are read by the layer's weight GEMMs only (q | k | v, q, wi_0 | wi_1: forward and dW), whatever attention route runs;
         # without biases and with every such weight at least 128 wide they need no f32 tensor in a bf16x3 step
         go = (not self.__dict__.get("_use_bias", False) and c.hidden_size >= 128 and 2 * c.intermediate_size >= 128)
-        for lyr in self.transformer_layers:                                           # TransformerLayer :757-792
+        for li, lyr in enumerate(self.transformer_layers):                            # TransformerLayer :757-792
+            ln = f"transformer_layers.{li}"
             m1, res1, a1s = self._norm_adaln(t, lyr.attn_layer_norm, lyr.self_attn_adaLN_modulation, scond, B, residual=res, gemm_only=go)
-            a, s1 = self._attention(m1, m1, lyr.attention, B, S, S, nh)
+            a, s1 = self._attention(m1, m1, lyr.attention, B, S, S, nh, drop=D.get(ln + ".attention.dropout"))
             m2, res2, a2s = self._norm_adaln(a, lyr.crossattn_layer_norm, lyr.cross_attn_adaLN_modulation, scond, B, residual=res1, gemm_only=go)
-            a2, s2 = self._attention(m2, enc, lyr.crossattention, B, S, L, nh)
+            a2, s2 = self._attention(m2, enc, lyr.crossattention, B, S, L, nh, drop=D.get(ln + ".crossattention.dropout"))
             m3, res3, a3s = self._norm_adaln(a2, lyr.ffn.pre_mlp_layer_norm, lyr.ffn.adaLN_modulation, scond, B, mode=1,
                                              residual=res2, gemm_only=go)                                  # LayerNorm (:928)
             w01 = self._w2(lyr.ffn.wi_0, lyr.ffn.wi_1, rows=m3.shape[0])
@@ -566,10 +632,11 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
             # (bf16x3 step: gl only ever feeds wo's forward and dW products - it exists as their operand planes, no f32 tensor)
             po = (self.compute_dtype == torch.float32 and not self.__dict__.get("_use_bias", False) and ab.dtype == torch.float32
                   and ops.planes_only_ok(ab.shape[0], ab.shape[1] // 2) and min(lyr.ffn.wo.weight.shape) >= 128 and min(w01.shape) >= 128)
-            gl = ops.glu_fwd(ab, planes_only=po)
+            gdrop = D.get(ln + ".ffn.dropout")         # GLUFeedForward.dropout (:947): the keep bit is applied inside the GLU kernel
+            gl = ops.glu_fwd(ab, planes_only=po and (gdrop is None or ops.row_drop_ok(ab.shape[1] // 2)), drop=gdrop)
             t = self._lin(gl, lyr.ffn.wo)
             T["layers"].append(dict(res1=res1, res2=res2, res3=res3, a1s=a1s, a2s=a2s, a3s=a3s, s1=s1, s2=s2, m3=m3, w01=w01, ab=ab,
-                                    gl=gl))
+                                    gl=gl, gdrop=gdrop))
             res = res3
         vlast = None
         n, vlast = self._norm(t, self.project_from_hidden_norm, residual=res, want_pre=True)   # (t + residual) then norm (:288-290)
@@ -578,8 +645,10 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         T["up"] = []
         blk = self.up_blocks[0]
         for i in range(c.num_res_blocks):
-            h, sr = self._res_block(h, blk.res_blocks[i], scond, B, side)
-            h, sa = self._attn_block(h, blk.attention_blocks[i], enc, senc, B, S, L)
+            bn = f"up_blocks.0.res_blocks.{i}", f"up_blocks.0.attention_blocks.{i}"
+            h, sr = self._res_block(h, blk.res_blocks[i], scond, B, side, drop=D.get(bn[0] + ".channelwise.3"))
+            h, sa = self._attn_block(h, blk.attention_blocks[i], enc, senc, B, S, L,
+                                     drops=(D.get(bn[1] + ".attention.dropout"), D.get(bn[1] + ".crossattention.dropout")))
             T["up"].append((sr, sa))
         self.__dict__["_ada_ss"] = {}     # every site has run: the tape holds what backward needs, nothing pins the [Z, B, N] buffers
         if down_up:                                                                   # Norm2D -> ConvTranspose2d(C, C, 2, stride 2)  (:558-562)
@@ -665,7 +734,8 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
                 dgl = ops.linear_dgrad(dtb, wo2)
             else:
                 dgl = self._lin_bwd(dt, sv["gl"], lyr.ffn.wo, nm + ".ffn.wo", G)
-            dab = ops.glu_bwd(sv["ab"], dgl, planes_only=isinstance(sv["gl"], ops.OperandOnly) and ops.planes_only_ok(*sv["ab"].shape))
+            dab = ops.glu_bwd(sv["ab"], dgl, planes_only=isinstance(sv["gl"], ops.OperandOnly) and ops.planes_only_ok(*sv["ab"].shape),
+                              drop=sv.get("gdrop"))
             gw01 = self._mm_dw(dab, sv["m3"], sv["w01"].shape)
             I = gw01.shape[0] // 2
             G[nm + ".ffn.wi_0.weight"], G[nm + ".ffn.wi_1.weight"] = gw01[:I], gw01[I:]
@@ -781,6 +851,9 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
         intermediate = []
         sampled = input_ids
         graph = None
+        if hip_graph and self.training and (self.config.hidden_dropout > 0.0 or self.config.attention_dropout > 0.0):
+            # a captured forward would bake ONE dropout seed into its launches and replay the same masks every step
+            raise MuseHipError("generate2(hip_graph=True) on a model in training mode with dropout > 0: call model.eval() first")
         if hip_graph:
             # The captured forward is KEPT across calls (a serving loop decodes batch after batch of one shape): it reads its inputs from
             # static buffers, so a later call with the same shapes copies its conditioning in and replays - no capture, no per-launch

@@ -1203,10 +1203,25 @@ def attention_x3_blocked(Sq, Skv):
     return Sq > 256 or Skv > 256
 
 
-def attention_x3_streamed(Sq, Skv):
+def attention_x3_streamed(Sq, Skv, dropout=False):
     """whole 256-row blocks on both sides and more than one key block: the streaming kernels (online-softmax forward, dQ and dK / dV
-    passes; csrc/attention3.hip) - one writer per result, so operand images / planes-only gradients work as in the one-tile form"""
-    return X3_STREAM and Sq % 256 == 0 and Skv % 256 == 0 and Skv > 256
+    passes; csrc/attention3.hip) - one writer per result, so operand images / planes-only gradients work as in the one-tile form.
+    dropout: the streaming kernels have no dropout form - those steps take the block-pair route, whose one-tile kernels draw
+    the full-sequence mask through their q0 / k0 arguments"""
+    return X3_STREAM and not dropout and Sq % 256 == 0 and Skv % 256 == 0 and Skv > 256
+
+
+def attention_x3_dropout_fused():
+    """MUSE_X3_ATTN_DROPOUT_FUSED=0 (read per call, like MUSE_ATTN_DROPOUT_FUSED): attention dropout of the bf16x3 / f16 modes on the
+    materialised route instead of inside the kernels of csrc/attention3.hip"""
+    return os.environ.get("MUSE_X3_ATTN_DROPOUT_FUSED", "1") != "0"
+
+
+def _x3_drop(drop, q0, k0, Sq):
+    """drop = (p, seed, offset, ld_mask) -> the dropout arguments of muse_attention_x3_drop_fwd / _bwd for the launch whose first query /
+    key is (q0, k0) of a sequence of Sq queries"""
+    p, seed, offset, ld_mask = _drop_args(drop)
+    return p, seed, offset, ld_mask, int(q0), int(k0), int(Sq)
 
 
 def attention_x3_supported(Sq, Skv, hd):
@@ -1226,7 +1241,7 @@ def _x3_block_desc(q, k, v, o, B, Sq, Skv, nh, hd, alpha, qi, kj, kb):
     return d
 
 
-def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
+def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha, drop=None):
     """-> (ctx [B*Sq, H] f32, lse [Sq // 256, B*nh, 256] f32).  softmax over all keys = the key blocks' softmaxes re-weighted by
     exp(lse_block - lse): exact in exact arithmetic, f32 here (the products inside each block are the kernels' bf16x3 ones)."""
     H = nh * hd
@@ -1236,7 +1251,7 @@ def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
     ctx = torch.empty((B * Sq, H), dtype=torch.float32, device=dev)
     lse = torch.empty((nq, B * nh, 256), dtype=torch.float32, device=dev)
     e0 = _prof_begin()
-    if nk > 1 and X3_STREAM:
+    if nk > 1 and X3_STREAM and drop is None:
         # whole 256-row blocks on both sides: a workgroup keeps its 256 queries and streams the key blocks through LDS with an online
         # softmax (csrc/attention3.hip fwd_stream_kernel) - q read once, the context and its log-sum-exp written once, no partials
         planes = x3_new_planes(ctx)
@@ -1250,6 +1265,10 @@ def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
         for qi in range(nq):
             d = _x3_block_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha, qi, 0, kb)
             pp = None if planes is None else planes.data_ptr() + qi * 256 * H * 2
+            if drop is not None:
+                check(lib().muse_attention_x3_drop_fwd(C.byref(d), lse[qi].data_ptr(), pp, ctx.numel() if planes is not None else 0,
+                                                       *_x3_drop(drop, qi * 256, 0, Sq), *img, stream()), "muse_attention_x3_drop_fwd")
+                continue
             check(lib().muse_attention_x3_fwd(C.byref(d), lse[qi].data_ptr(), pp, ctx.numel() if planes is not None else 0, *img, stream()),
                   "muse_attention_x3_fwd")
         x3_put_planes(ctx, planes)
@@ -1260,6 +1279,10 @@ def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
         for kj in range(nk):
             for qi in range(nq):
                 d = _x3_block_desc(q, k, v, part[kj], B, Sq, Skv, nh, hd, alpha, qi, kj, kb)
+                if drop is not None:     # (dropout commutes with the log-sum-exp merge: a block's partial context is linear in its dropped P)
+                    check(lib().muse_attention_x3_drop_fwd(C.byref(d), lp[kj, qi].data_ptr(), None, 0, *_x3_drop(drop, qi * 256, kj * 256, Sq),
+                                                           *img, stream()), "muse_attention_x3_drop_fwd")
+                    continue
                 check(lib().muse_attention_x3_fwd(C.byref(d), lp[kj, qi].data_ptr(), None, 0, *img, stream()), "muse_attention_x3_fwd")
         planes = x3_new_planes(ctx)          # ctx feeds the output projection: its operand planes come out of the merge kernel
         check(lib().muse_attention_x3_merge(part.data_ptr(), part[0].numel(), lp.data_ptr(), lp[0].numel(), nk, ctx.data_ptr(), lse.data_ptr(),
@@ -1269,7 +1292,7 @@ def _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha):
     return ctx, lse
 
 
-def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq, dk, dv):
+def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq, dk, dv, drop=None):
     """block-pair backward: every (query block, key block) pair with the query block's GLOBAL log-sum-exp and the final context (so the
     probabilities and the row sums dO.O are the full-sequence ones); dq summed over key blocks, dk / dv over query blocks"""
     H = nh * hd
@@ -1291,9 +1314,12 @@ def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha,
         for kj in range(nk):
             d = _x3_block_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha, qi, kj, kb)
             (pq, ldq_), (pk, ldk_), (pv, ldv_) = _row_view(dqp[kj], H), _row_view(dkp[qi], H), _row_view(dvp[qi], H)
-            check(lib().muse_attention_x3_bwd(C.byref(d), pdo + qi * 256 * lddo * 4, lddo, Sq * lddo, lse[qi].data_ptr(),
-                                              pq + qi * 256 * ldq_ * 4, ldq_, Sq * ldq_, pk + kj * 256 * ldk_ * 4, ldk_, Skv * ldk_,
-                                              pv + kj * 256 * ldv_ * 4, ldv_, Skv * ldv_, None, 0, None, 0, None, 0, *img, stream()), "muse_attention_x3_bwd")
+            fn, extra = ((lib().muse_attention_x3_bwd, ()) if drop is None
+                         else (lib().muse_attention_x3_drop_bwd, _x3_drop(drop, qi * 256, kj * 256, Sq)))
+            check(fn(C.byref(d), pdo + qi * 256 * lddo * 4, lddo, Sq * lddo, lse[qi].data_ptr(),
+                     pq + qi * 256 * ldq_ * 4, ldq_, Sq * ldq_, pk + kj * 256 * ldk_ * 4, ldk_, Skv * ldk_,
+                     pv + kj * 256 * ldv_ * 4, ldv_, Skv * ldv_, None, 0, None, 0, None, 0, *extra, *img, stream()),
+                  "muse_attention_x3_bwd" if drop is None else "muse_attention_x3_drop_bwd")
     for stack, g, rows in ((dqs, dq, B * Sq), (dks, dk, B * Skv), (dvs, dv, B * Skv)):
         if stack is not None:
             pg, ldg = _row_view(g, H)
@@ -1304,32 +1330,39 @@ def _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha,
     return dq, dk, dv
 
 
-def attention_x3_fwd(q, k, v, B, Sq, Skv, nh, hd, alpha):
+def attention_x3_fwd(q, k, v, B, Sq, Skv, nh, hd, alpha, drop=None):
     """fused softmax(alpha q k^T) v on f32 tensors with bf16x3 products (TF32-class: <= 2^-16 relative per product); q [B*Sq, H],
-    k / v [B*Skv, H] f32 views (slices of a packed projection are fine) -> (ctx [B*Sq, H] f32, lse [B*nh, 256] f32)"""
+    k / v [B*Skv, H] f32 views (slices of a packed projection are fine) -> (ctx [B*Sq, H] f32, lse [B*nh, 256] f32).
+    drop = (p, seed, offset, ld_mask): nn.Dropout on the probabilities inside the kernels, attention_drop_fwd_ex's mask contract (lse is
+    the undropped softmax's); longer sequences run block by block (never the streaming kernels) and draw the full-sequence mask"""
     require_gpu(q, k, v)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise _hip.MuseHipError("attention_x3: f32 operands")
     if not attention_x3_supported(Sq, Skv, hd):
         raise _hip.MuseHipError(f"attention_x3: shape ({Sq} x {Skv}, head_dim {hd}) outside attention_x3_supported")
     if attention_x3_blocked(Sq, Skv):
-        return _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha)
+        return _attention_x3_fwd_blocks(q, k, v, B, Sq, Skv, nh, hd, alpha, drop=drop)
     ctx = torch.empty((B * Sq, nh * hd), dtype=torch.float32, device=q.device)
     lse = torch.empty((B * nh, Sq), dtype=torch.float32, device=q.device)
     d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
     planes = x3_new_planes(ctx)          # ctx feeds the output projection: its operand planes come out of the kernel
     e0 = _prof_begin()
-    check(lib().muse_attention_x3_fwd(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel(), *_image_args(False, planes), stream()), "muse_attention_x3_fwd")
+    if drop is None:
+        check(lib().muse_attention_x3_fwd(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel(), *_image_args(False, planes), stream()), "muse_attention_x3_fwd")
+    else:
+        check(lib().muse_attention_x3_drop_fwd(C.byref(d), lse.data_ptr(), ptr(planes), ctx.numel(), *_x3_drop(drop, 0, 0, Sq),
+                                               *_image_args(False, planes), stream()), "muse_attention_x3_drop_fwd")
     _prof_end(e0, "attn_fwd_bf16x3", 4.0 * B * nh * Sq * Skv * hd)
     x3_put_planes(ctx, planes)
     return ctx, lse
 
 
-def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None, dk=None, dv=None, planes=None, planes_only=False):
+def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None, dk=None, dv=None, planes=None, planes_only=False, drop=None):
     """-> (dq [B*Sq, H], dk, dv [B*Skv, H]) f32; dq / dk / dv may be views (the column blocks of a packed gradient).
     planes = ((dq_hi, dq_lo_off), (dk_hi, ..), (dv_hi, ..)): hi-plane views shaped / strided like dq / dk / dv and the element distance
     to their lo planes (entries may be None) - the gradients also come out as operand planes (x3_new_planes of the packed tensor).
-    planes_only: no f32 gradients at all (dq / dk / dv stay None; the caller wraps the plane tensors: operand_only)"""
+    planes_only: no f32 gradients at all (dq / dk / dv stay None; the caller wraps the plane tensors: operand_only).
+    drop: attention_x3_fwd's - the same masks, drawn again"""
     require_gpu(q, k, v, ctx, dctx, lse)
     H = nh * hd
     planes = planes or (None, None, None)
@@ -1342,11 +1375,11 @@ def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None
     for t in (ctx, dctx, dq, dk, dv):
         if t is not None and t.dtype != torch.float32:
             raise _hip.MuseHipError("attention_x3: f32 operands")
-    streamed = attention_x3_streamed(Sq, Skv)
+    streamed = attention_x3_streamed(Sq, Skv, drop is not None)
     if attention_x3_blocked(Sq, Skv) and not streamed:
         if planes_only or any(e is not None and e[0] is not None for e in planes):
             raise _hip.MuseHipError("attention_x3_bwd: the block-by-block form (more than 256 query rows or keys) writes f32 gradients, no operand planes")
-        return _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq, dk, dv)
+        return _attention_x3_bwd_blocks(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq, dk, dv, drop=drop)
     d = _attn_desc(q, k, v, ctx, B, Sq, Skv, nh, hd, alpha)
     pdo, lddo = _row_view(dctx, H)
     e0 = _prof_begin()
@@ -1372,6 +1405,9 @@ def attention_x3_bwd(q, k, v, ctx, dctx, lse, B, Sq, Skv, nh, hd, alpha, dq=None
         for t in (dq, dk, dv):
             if t is not None:
                 _touched(t)
+    elif drop is not None:
+        check(lib().muse_attention_x3_drop_bwd(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), *args, *pl, *_x3_drop(drop, 0, 0, Sq), *img, stream()),
+              "muse_attention_x3_drop_bwd")
     else:
         check(lib().muse_attention_x3_bwd(C.byref(d), pdo, lddo, Sq * lddo, lse.data_ptr(), *args, *pl, *img, stream()), "muse_attention_x3_bwd")
     _prof_end(e0, "attn_bwd_bf16x3", 10.0 * B * nh * Sq * Skv * hd)
@@ -1433,9 +1469,86 @@ def x3_put_planes(t, planes):
         _PASS.images.put_planes(t, planes)
 
 
-def glu_fwd(ab, planes_only=False):
-    """planes_only (see planes_only_ok): -> OperandOnly, the result as the running pass's GEMM operand image without its f32 tensor"""
+def _row_drop(drop):
+    """(p, seed, offset) of a dropped row kernel as its C arguments"""
+    p, seed, offset = drop
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"dropout probability has to be in [0, 1), but got {p}")
+    return float(p), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+
+
+def row_drop_ok(cols):
+    """the dropped GLU / GRN kernels take the width: a thread's four consecutive columns are one Philox block"""
+    return cols % 4 == 0
+
+
+def grn_drop_ok(B, S, C_):
+    """muse_grn_drop_fwd_ex / _bwd take the shape (their four-channel kernels index an image with 32 bits and walk images in gridDim.y)"""
+    return row_drop_ok(C_) and S * (C_ >> 2) < (1 << 31) and B <= 65535
+
+
+def _glu_drop_fwd(ab, planes_only, drop):
+    """glu_fwd with nn.Dropout on the result inside the kernel: the keep bits of ops.dropout(result, *drop)"""
+    rows, two_i = ab.shape
+    inter = two_i // 2
+    d = _row_drop(drop)
+    if not row_drop_ok(inter):
+        if planes_only:
+            raise _hip.MuseHipError("glu_fwd(planes_only=True, drop=) needs inter % 4 == 0")
+        h = glu_fwd(ab)
+        return dropout(h, *d, out=h)          # (no operand image of the undropped h is registered: inter % 8 != 0 writes none)
+    if planes_only:
+        if not (planes_only_ok(rows, inter) and ab.dtype == torch.float32 and ab.is_contiguous()):
+            raise _hip.MuseHipError("glu_fwd(planes_only=True) outside planes_only_ok")
+        planes = planes_alloc((rows, inter), ab.device)
+        check(lib().muse_glu_drop_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, inter, *d, *_image_args(False, planes), stream()),
+              "muse_glu_drop_fwd_x3")
+        return operand_only(planes, False)
+    h = torch.empty((rows, inter), dtype=ab.dtype, device=ab.device)
+    im = _x3_producing(ab)
+    if im is not None and inter % 8 == 0:
+        planes = planes_alloc((rows, inter), ab.device)
+        check(lib().muse_glu_drop_fwd_x3(ab.data_ptr(), h.data_ptr(), planes.data_ptr(), rows, inter, *d, *_image_args(False, planes), stream()),
+              "muse_glu_drop_fwd_x3")
+        im.put_planes(h, planes)
+        return h
+    check(lib().muse_glu_drop_fwd(ab.data_ptr(), h.data_ptr(), dt(ab), rows, inter, *d, stream()), "muse_glu_drop_fwd")
+    return h
+
+
+def _glu_drop_bwd(ab, dh, planes_only, drop):
+    rows, two_i = ab.shape
+    inter = two_i // 2
+    d = _row_drop(drop)
+    if not row_drop_ok(inter):
+        return glu_bwd(ab, dropout(dh.contiguous(), *d), planes_only=planes_only)
+    if planes_only:
+        if not (planes_only_ok(rows, two_i) and ab.dtype == torch.float32 and dh.dtype == torch.float32 and ab.is_contiguous() and dh.is_contiguous()):
+            raise _hip.MuseHipError("glu_bwd(planes_only=True) outside planes_only_ok")
+        planes = planes_alloc((rows, two_i), ab.device)
+        check(lib().muse_glu_drop_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, inter, *d, *_image_args(True, planes), stream()),
+              "muse_glu_drop_bwd_x3")
+        return operand_only(planes, True)
+    if dh.dtype != ab.dtype or not dh.is_contiguous() or not ab.is_contiguous():
+        raise _hip.MuseHipError("glu_bwd(drop=) expects contiguous ab and dh of one dtype")
+    dab = torch.empty_like(ab)
+    im = _x3_producing(ab)
+    if im is not None and dh.dtype == torch.float32 and two_i % 16 == 0:
+        planes = planes_alloc((rows, two_i), ab.device)
+        check(lib().muse_glu_drop_bwd_x3(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), planes.data_ptr(), rows, inter, *d, *_image_args(True, planes),
+                                         stream()), "muse_glu_drop_bwd_x3")
+        im.put_planes(dab, planes)
+        return dab
+    check(lib().muse_glu_drop_bwd(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), dt(ab), rows, inter, *d, stream()), "muse_glu_drop_bwd")
+    return dab
+
+
+def glu_fwd(ab, planes_only=False, drop=None):
+    """planes_only (see planes_only_ok): -> OperandOnly, the result as the running pass's GEMM operand image without its f32 tensor.
+    drop = (p, seed, offset): nn.Dropout on the result, drawn inside the kernel (the keep bits of ops.dropout on the [rows, inter] result)"""
     require_gpu(ab)
+    if drop is not None:
+        return _glu_drop_fwd(ab, planes_only, drop)
     rows, two_i = ab.shape
     if planes_only:
         if not (planes_only_ok(rows, two_i // 2) and ab.dtype == torch.float32 and ab.is_contiguous()):
@@ -1455,8 +1568,11 @@ def glu_fwd(ab, planes_only=False):
     return h
 
 
-def glu_bwd(ab, dh, planes_only=False):
+def glu_bwd(ab, dh, planes_only=False, drop=None):
+    """drop = glu_fwd's: the same keep mask, redrawn, multiplies dh before anything else"""
     require_gpu(ab, dh)
+    if drop is not None:
+        return _glu_drop_bwd(ab, dh, planes_only, drop)
     rows, two_i = ab.shape
     if planes_only:
         if not (planes_only_ok(rows, two_i) and ab.dtype == torch.float32 and dh.dtype == torch.float32 and ab.is_contiguous() and dh.is_contiguous()):
@@ -2402,16 +2518,24 @@ def depth_to_space2(x, B, H, W, C_):
     return y
 
 
-def grn_fwd(x, gamma, beta, B, S, want_stats=False, out_dtype=torch.float32):
+def grn_fwd(x, gamma, beta, B, S, want_stats=False, out_dtype=torch.float32, drop=None):
     """GlobalResponseNorm over the S pixels of each image; x [B*S, C] f32.  out_dtype=torch.bfloat16: the result is written
-    only as the bf16 GEMM operand of the bf16 compute mode (no f32 copy, no cast pass)"""
+    only as the bf16 GEMM operand of the bf16 compute mode (no f32 copy, no cast pass).
+    drop = (p, seed, offset): nn.Dropout on the result inside the apply kernel (the keep bits of ops.dropout on the [B*S, C] result); a
+    width the dropped kernel refuses (C % 4 != 0) gets the plain kernels and an ops.dropout pass over the f32 result"""
     require_gpu(x, gamma, beta)
     C_ = x.shape[1]
     bf = out_dtype == torch.bfloat16 and C_ % 4 == 0
     y = torch.empty(x.shape, dtype=torch.bfloat16 if bf else torch.float32, device=x.device)
     stats = torch.empty(2 * B * C_, dtype=torch.float32, device=x.device)   # [G | N], kept for grn_bwd
+    if drop is not None and grn_drop_ok(B, S, C_):
+        check(lib().muse_grn_drop_fwd_ex(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None if bf else y.data_ptr(), y.data_ptr() if bf else None,
+                                         stats.data_ptr(), B, S, C_, *_row_drop(drop), stream()), "muse_grn_drop_fwd_ex")
+        return (y, stats) if want_stats else y
     check(lib().muse_grn_fwd_ex(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None if bf else y.data_ptr(), y.data_ptr() if bf else None,
                                 stats.data_ptr(), B, S, C_, stream()), "muse_grn_fwd_ex")
+    if drop is not None:
+        dropout(y, *_row_drop(drop), out=y)
     return (y, stats) if want_stats else y
 
 
@@ -2562,12 +2686,22 @@ def dwconv3x3_bwd(dy, x, w, B, H, W, C_):
     return dx, dw
 
 
-def grn_bwd(dy, x, gamma, stats, B, S):
-    """-> (dx, dgamma [C], dbeta [C])"""
+def grn_bwd(dy, x, gamma, stats, B, S, drop=None):
+    """-> (dx, dgamma [C], dbeta [C]).  drop = grn_fwd's: the same keep mask, redrawn, multiplies dy before everything else"""
     require_gpu(dy, x, gamma, stats)
     C_ = x.shape[1]
     dx = torch.empty_like(x)
     work = torch.empty(4 * B * C_, dtype=torch.float32, device=x.device)
+    if drop is not None and grn_drop_ok(B, S, C_):
+        if dy.dtype != torch.float32 or not dy.is_contiguous():
+            raise _hip.MuseHipError("grn_bwd(drop=) expects a contiguous f32 gradient")
+        check(lib().muse_grn_drop_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), stats.data_ptr(), dx.data_ptr(), work.data_ptr(), B, S, C_,
+                                      *_row_drop(drop), stream()), "muse_grn_drop_bwd")
+        dbeta = colsum(work[: B * C_].view(B, C_), torch.empty(C_, dtype=torch.float32, device=x.device))
+        dgamma = colsum(work[B * C_: 2 * B * C_].view(B, C_), torch.empty(C_, dtype=torch.float32, device=x.device))
+        return dx, dgamma, dbeta
+    if drop is not None:
+        dy = dropout(dy.contiguous(), *_row_drop(drop))
     check(lib().muse_grn_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), stats.data_ptr(), dx.data_ptr(), work.data_ptr(), B, S, C_,
                              stream()), "muse_grn_bwd")
     dbeta = colsum(work[: B * C_].view(B, C_), torch.empty(C_, dtype=torch.float32, device=x.device))

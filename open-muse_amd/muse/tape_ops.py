@@ -412,8 +412,8 @@ class TapeOps:
 
     def _attention(self, x, ctx, att, B, Sq, Skv, nh, residual=None, drop=None):
         """`drop` = (p, seed, offset): nn.Dropout on the attention probabilities (training mode of models with attention_dropout > 0):
-        drawn inside the fused kernels in bf16 mode (the bits of the materialised [B*nh, Sq, Sp] route, which MUSE_ATTN_DROPOUT_FUSED=0
-        and the other modes take).
+        drawn inside the fused kernels in bf16 mode and in the bf16x3 / f16 modes (the bits of the materialised [B*nh, Sq, Sp] route, which
+        MUSE_ATTN_DROPOUT_FUSED=0 / MUSE_X3_ATTN_DROPOUT_FUSED=0 and the f32 parity mode take).
         reference Attention :834-915.  bf16 compute mode: fused attention kernel (S x S never materialised; self- and
         cross-attention) on a packed q|k|v (self) or k|v (cross) projection.  f32 parity mode: the reference's algorithm
         materialised: scores = alpha q k^T (batched per head), softmax, P v, out projection."""
@@ -438,8 +438,8 @@ class TapeOps:
             y = ops.linear(o, self._wb(att.out), out_dtype=torch.float32, residual=residual, bias=self._b(att.out))
             return y, dict(fused=True, self_attn=self_attn, xb=xb, cb=cb, q=q, qkv=qkv, o=o, lse=lse, drop=fdrop,
                            dims=(B, Sq, Skv, nh, hd, Cq, alpha))
-        if ((self.__dict__.get("_f32_split3", False) or self.__dict__.get("_f32_f16", False)) and _X3_ATTENTION and pdrop == 0.0
-                and ops.attention_x3_supported(Sq, Skv, hd)
+        if ((self.__dict__.get("_f32_split3", False) or self.__dict__.get("_f32_f16", False)) and _X3_ATTENTION
+                and (pdrop == 0.0 or ops.attention_x3_dropout_fused()) and ops.attention_x3_supported(Sq, Skv, hd)
                 and x.dtype == torch.float32 and ctx.dtype == torch.float32 and att.key.weight.shape[1] % 8 == 0):
             # "bf16x3" mode: the same fused form on f32 tensors, every product of the core as three bf16 MFMA products like the mode's
             # GEMMs (csrc/attention3.hip); packed q|k|v (self) / k|v (cross) projections: one forward, one dX and one dW product each
@@ -454,9 +454,11 @@ class TapeOps:
                 w = self._w2(att.key, att.value, rows=ctx.shape[0])
                 qkv = self._mm(ctx, w, bias=self._b(att.key, att.value))
                 k, v = qkv[:, :Cq], qkv[:, Cq:]
-            o, lse = ops.attention_x3_fwd(q, k, v, B, Sq, Skv, nh, hd, alpha)
+            fdrop = (*drop, (Skv + 7) // 8 * 8) if pdrop > 0.0 else None      # + the materialised route's row pitch: the same mask bits
+            o, lse = ops.attention_x3_fwd(q, k, v, B, Sq, Skv, nh, hd, alpha, **({} if fdrop is None else dict(drop=fdrop)))
             y = self._lin(o, att.out, residual=residual)
-            return y, dict(fused_x3=True, self_attn=self_attn, x=x, ctx=ctx, q=q, qkv=qkv, w=w, o=o, lse=lse, dims=(B, Sq, Skv, nh, hd, Cq, alpha))
+            return y, dict(fused_x3=True, self_attn=self_attn, x=x, ctx=ctx, q=q, qkv=qkv, w=w, o=o, lse=lse, drop=fdrop,
+                           dims=(B, Sq, Skv, nh, hd, Cq, alpha))
         q, k, v = self._lin(x, att.query), self._lin(ctx, att.key), self._lin(ctx, att.value)
         Sp = (Skv + 7) // 8 * 8
         P = torch.empty((B * nh, Sq, Sp), dtype=torch.float32, device=x.device)
@@ -511,7 +513,9 @@ class TapeOps:
         q, qkv, w = sv["q"], sv["qkv"], sv["w"]
         ub = self.__dict__.get("_use_bias", False)
         # (block-by-block form of the long sequences: f32 gradients, no operand planes - the streaming form writes them like the one-tile one)
-        blocked = ops.attention_x3_blocked(Sq, Skv) and not ops.attention_x3_streamed(Sq, Skv)
+        fdrop = sv.get("drop")
+        dk_ = {} if fdrop is None else dict(drop=fdrop)        # (p = 0: today's calls, argument for argument)
+        blocked = ops.attention_x3_blocked(Sq, Skv) and not ops.attention_x3_streamed(Sq, Skv, fdrop is not None)
         if sv["self_attn"]:
             if not self_attn:
                 raise MuseHipError("self-attention tape replayed as cross-attention")
@@ -520,14 +524,14 @@ class TapeOps:
                 # dqkv feeds one dW and one dX product and nothing else: it exists as their operand planes only
                 pl = ops.planes_alloc(tuple(qkv.shape), qkv.device)
                 ops.attention_x3_bwd(q, qkv[:, Cq:2 * Cq], qkv[:, 2 * Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, planes_only=True,
-                                     planes=((pl[0][:, :Cq], lo), (pl[0][:, Cq:2 * Cq], lo), (pl[0][:, 2 * Cq:], lo)))
+                                     planes=((pl[0][:, :Cq], lo), (pl[0][:, Cq:2 * Cq], lo), (pl[0][:, 2 * Cq:], lo)), **dk_)
                 dqkv = ops.operand_only(pl, True)
             else:
                 dqkv = torch.empty_like(qkv)
                 pl = None if blocked else ops.x3_new_planes(dqkv)       # ... or as f32 and planes, both out of the kernel
                 ops.attention_x3_bwd(q, qkv[:, Cq:2 * Cq], qkv[:, 2 * Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha,
                                      dq=dqkv[:, :Cq], dk=dqkv[:, Cq:2 * Cq], dv=dqkv[:, 2 * Cq:],
-                                     planes=None if pl is None else ((pl[0][:, :Cq], lo), (pl[0][:, Cq:2 * Cq], lo), (pl[0][:, 2 * Cq:], lo)))
+                                     planes=None if pl is None else ((pl[0][:, :Cq], lo), (pl[0][:, Cq:2 * Cq], lo), (pl[0][:, 2 * Cq:], lo)), **dk_)
                 ops.x3_put_planes(dqkv, pl)
             gqkv = self._mm_dw(dqkv, sv["x"], (3 * Cq, Cq))
             G[name + ".query.weight"], G[name + ".key.weight"], G[name + ".value.weight"] = gqkv[:Cq], gqkv[Cq:2 * Cq], gqkv[2 * Cq:]
@@ -541,7 +545,7 @@ class TapeOps:
             plq = ops.planes_alloc(tuple(q.shape), q.device)
             plkv = ops.planes_alloc(tuple(qkv.shape), q.device)
             ops.attention_x3_bwd(q, qkv[:, :Cq], qkv[:, Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, planes_only=True,
-                                 planes=((plq[0], q.numel()), (plkv[0][:, :Cq], qkv.numel()), (plkv[0][:, Cq:], qkv.numel())))
+                                 planes=((plq[0], q.numel()), (plkv[0][:, :Cq], qkv.numel()), (plkv[0][:, Cq:], qkv.numel())), **dk_)
             dq, dkv = ops.operand_only(plq, True), ops.operand_only(plkv, True)
         else:
             dq = torch.empty_like(q)
@@ -549,7 +553,7 @@ class TapeOps:
             plq, plkv = (None, None) if blocked else (ops.x3_new_planes(dq), ops.x3_new_planes(dkv))
             ops.attention_x3_bwd(q, qkv[:, :Cq], qkv[:, Cq:], sv["o"], do, sv["lse"], B, Sq, Skv, nh, hd, alpha, dq=dq, dk=dkv[:, :Cq], dv=dkv[:, Cq:],
                                  planes=(None if plq is None else (plq[0], dq.numel()), None if plkv is None else (plkv[0][:, :Cq], dkv.numel()),
-                                         None if plkv is None else (plkv[0][:, Cq:], dkv.numel())))
+                                         None if plkv is None else (plkv[0][:, Cq:], dkv.numel())), **dk_)
             ops.x3_put_planes(dq, plq)
             ops.x3_put_planes(dkv, plkv)
         dx = self._lin_bwd(dq, sv["x"], att.query, name + ".query", G)
