@@ -1,7 +1,6 @@
 // Dense / strided-batched GEMM entry point of libmuse_hip (see include/muse_hip.h: muse_gemm).
 #include "gemm_core.h"
-#include "gemm256.h"
-#include "gemm_p.h"
+#include "gemm256_host.h"
 #include "../../include/muse_hip.h"
 
 template <typename T, typename TC, int BM>
@@ -46,7 +45,7 @@ static int fill_params(const muse_gemm_desc* d, GemmParams& p) {
   return 0;
 }
 
-// does this descriptor go to the 256 x 256 LDS-DMA kernel (gemm256.h)?
+// does this descriptor go to the 256 x 256 LDS-DMA kernel (gemm256.h; gemm256_ok of gemm_p.h, gemm256_preferred of gemm256_host.h)?
 static bool takes_gemm256(const muse_gemm_desc* d, const GemmParams& p, int batch) {
   if (d->dtype == MUSE_F16) {
     // half operands exist on the 256^2 kernels only, with f32 output: no cost model - whatever those kernels take (the caller keeps
@@ -156,7 +155,7 @@ extern "C" int muse_gemm_group(const muse_gemm_desc* d, int32_t n, int32_t split
   const int rc = group_fill(d, n, split_k, gp);
   if (rc) return rc;
   const bool half_ops = d[0].dtype == MUSE_F16;
-  auto kern = half_ops ? g256::kernel_group<float, 1, 1, true, true> : g256::kernel_group<float, 1, 1, true>;
+  auto kern = half_ops ? g256::kernel_group<float, 1, 1, true> : g256::kernel_group<float, 1, 1>;
   set_max_dynamic_lds((const void*)kern, g256::LDS_BYTES);
   hipLaunchKernelGGL(kern, dim3(gp.tile_start[n], split_k, 1), dim3(512), g256::LDS_BYTES, (hipStream_t)stream, gp);
   return (int)hipGetLastError();

@@ -21,9 +21,11 @@
 //     row tiles first, the ragged last row tile (M = 16448 = 64 x 256 + 64) last.  A workgroup that starts late because another
 //     stream's kernel held its CU simply takes fewer tiles.  The counters clean themselves: the last workgroup to leave zeroes them.
 //
-// The wave tiling, LDS images, swizzles, fragment ring and the per-group DMA spreading are those of g256::Pipe<AL, BL, true>; the
-// products and their accumulation order per output element are identical (bf16 outputs are bit-identical to the launch-per-tile
-// kernel; f32 outputs with a residual differ by the order of one addition).
+// The wave tiling, LDS images, swizzles, fragment ring and the per-group DMA spreading are g256::Ring, the code g256::Pipe runs (PipeP is
+// the schedule around it: modes, tickets, tile change, epilogue); the products and their accumulation order per output element are
+// identical (bf16 outputs are bit-identical to the launch-per-tile kernel; f32 outputs with a residual differ by the order of one
+// addition).  DmaP restates the chunk geometry of g256::Dma<L, 64>::init and Sched::decode the arithmetic of g256::xcd_tile_index and
+// g256::raster_origin: written through those, these kernels compiled differently (profiles/gemm256_refactor_isa.md).
 #pragma once
 #include "gemm256.h"
 
@@ -45,6 +47,7 @@ struct Sched {
     const int full = q + (x < r ? 1 : 0);
     if (l < 0) return false;
     if (l < full) {
+      // (g256::xcd_tile_index's ranges, from the host's q / r and a queue position)
       const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
       constexpr int GM = 4;
       const int grp = id / (GM * ntn), first_m = grp * GM;
@@ -126,39 +129,38 @@ struct DmaP {
     r0off = L == 0 ? (unsigned)r0 * ld2 : (unsigned)r0 * 2u;
   }
   __device__ __forceinline__ unsigned kk(int j) const { return L == 0 ? (kk0 ^ ((unsigned)(j & 1) << 5)) : (kk0 + 2u * j); }
-  template <int LDS_OFF, int J>
-  __device__ __forceinline__ void issue1(unsigned char* smem, int kt, int wave) const {
+  template <int J>
+  __device__ __forceinline__ void issue1(unsigned char* smem, int LDS_OFF, int kt, int wave) const {
     const bool ok = ((unsigned)kt * 64u + kk(J)) < (unsigned)kend && ((vmask >> J) & 1u);
     const unsigned vo = ok ? voff0[J] : oob;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)(smem + LDS_OFF + (wave * 4 + J) * 1024), 16, (int)vo,
                                              (int)((unsigned)kt * kstep + r0off), 0, 0);
   }
-  template <int LDS_OFF>
-  __device__ __forceinline__ void issue(unsigned char* smem, int kt, int wave) const {
-    issue1<LDS_OFF, 0>(smem, kt, wave); issue1<LDS_OFF, 1>(smem, kt, wave);
-    issue1<LDS_OFF, 2>(smem, kt, wave); issue1<LDS_OFF, 3>(smem, kt, wave);
+  __device__ __forceinline__ void issue(unsigned char* smem, int LDS_OFF, int kt, int wave) const {
+    issue1<0>(smem, LDS_OFF, kt, wave); issue1<1>(smem, LDS_OFF, kt, wave);
+    issue1<2>(smem, LDS_OFF, kt, wave); issue1<3>(smem, LDS_OFF, kt, wave);
   }
 };
 
 enum { M_NORMAL = 0, M_FIRST = 1, M_LAST = 2, M_PUBLISH = 3 };
 
 template <typename TC, int AL, int BL, bool H = false>   // H: half operands (g256::mfma16)
-struct PipeP {
-  static constexpr bool F32OUT = sizeof(TC) == 4;
-  static constexpr int RA = AL ? 2 : 1, RB = BL ? 2 : 1, NB = NI * RB;
-  static constexpr int NSLOT = 4, DIST = NSLOT - 1;
-  static constexpr int GB1 = 8 - DIST, GBAR = 16 - DIST;
-  // stores one lane issues per tile: the first barrier of the next tile may leave that many operations in flight
-  // (the 8-byte bring-up epilogue issues 32; waiting with the smaller count is merely stricter)
-  static constexpr int NST = F32OUT ? 32 : 16;
+struct PipeP : Ring<PipeP<TC, AL, BL, H>, AL, BL, H> {
+  using R = Ring<PipeP<TC, AL, BL, H>, AL, BL, H>;
+  using R::GBAR; using R::NSLOT;
   DmaP<AL> da;
   DmaP<BL> db;
-  Frags<AL, MI> fa;
-  Frags<BL, NI> fb;
+  Frags<AL, MI, 64> fa;
+  Frags<BL, NI, 64> fb;
   f32x4 acc[MI][NI];
   bf16x8 ring[NSLOT];
   bf16x8 bk[2][NI];
   unsigned char* smem;
+  int wave;
+  static constexpr bool F32OUT = sizeof(TC) == 4;
+  // stores one lane issues per tile: the first barrier of the next tile may leave that many operations in flight
+  // (the 8-byte bring-up epilogue issues 32; waiting with the smaller count is merely stricter)
+  static constexpr int NST = F32OUT ? 32 : 16;
   Sched sched;
   unsigned* counters;
   int nk2, dyn, epi, staux, stagger, M, N;
@@ -168,30 +170,10 @@ struct PipeP {
   unsigned oobC, oobI, ldI;
   const void* init_src;
   unsigned tk;             // wave 0, lane 0: ticket drawn for the next tile
-  int wave, lane, wr, wc, xcd, nbx;
+  int lane, wr, wc, xcd, nbx;
   int kti;                 // K-tile index, relative to the tile the DMA currently targets
   int nm0, nn0;
   bool has_next, pend;
-
-  static constexpr int nB(int x) { x = ((x % 16) + 16) % 16; return (x == GB1 || x == GBAR) ? NB : 0; }
-  static constexpr int waitN(int g) {
-    int n = DIST * RA;
-    for (int x = g - DIST + 1; x <= g; ++x) n += nB(x);
-    return n > 15 ? 15 : n;
-  }
-  template <int S, int GA>
-  __device__ __forceinline__ void read_a() {
-    constexpr int st = GA < 16 ? S : (S ^ 1), g = GA & 15;
-    fa.template read<st, (g >> 3), (g & 7)>(ring[GA & (NSLOT - 1)]);
-  }
-  template <int STAGE, int Q>
-  __device__ __forceinline__ void issue_piece(int kt) {
-    if constexpr (Q < 4) da.template issue1<A_BASE + STAGE * TILE, Q>(smem, kt, wave);
-    else db.template issue1<B_BASE + STAGE * TILE, Q - 4>(smem, kt, wave);
-  }
-  template <int G> __device__ __forceinline__ void prologue_a() {
-    if constexpr (G < DIST) { read_a<0, G>(); prologue_a<G + 1>(); }
-  }
 
   // compiler-level fence: memory operations (DMA pieces, stores, loads) keep their program order across it
   static __device__ __forceinline__ void fence() {
@@ -244,17 +226,10 @@ struct PipeP {
       if constexpr (MODE == M_LAST) next_tile();
       if constexpr (MODE == M_PUBLISH) publish_ticket();
       __builtin_amdgcn_sched_barrier(0);
-      fb.template read_range<S ^ 1, 0, 0, NI>(bk[0]);
+      this->template read_b_next<S>();
     }
-    if constexpr (G >= GBAR) issue_piece<S, G - GBAR>(kti + 2);
-    else if constexpr (G < 8 - (16 - GBAR) && MODE != M_FIRST) issue_piece<S ^ 1, G + (16 - GBAR)>(kti + 1);
-    if constexpr (G == GB1) fb.template read_range<S, 1, 0, NI>(bk[1]);
-    read_a<S, G + DIST>();
-    wait_lgkm<waitN(G)>();
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-      acc[G & 7][j] = mfma16<H>(bk[G >> 3][j], ring[G & (NSLOT - 1)], acc[G & 7][j]);
-    __builtin_amdgcn_sched_barrier(0);
+    this->template spread<S, G, MODE != M_FIRST>(kti);   // (M_FIRST: the tile change issued pieces 3..7 ahead of the stores)
+    this->template step<S, G>();
     if constexpr (G + 1 < 16) group<S, G + 1, MODE>();
     else ++kti;
   }
@@ -440,7 +415,8 @@ struct PipeP {
       ktile<0, M_LAST>();      // from its barrier on the DMA fetches the next tile
       ktile<1, M_NORMAL>();
       // tile change: the rest of the next tile's second K-tile goes out ahead of the stores
-      issue_piece<1, 3>(1); issue_piece<1, 4>(1); issue_piece<1, 5>(1); issue_piece<1, 6>(1); issue_piece<1, 7>(1);
+      this->template issue_piece<1, 3>(1); this->template issue_piece<1, 4>(1); this->template issue_piece<1, 5>(1);
+      this->template issue_piece<1, 6>(1); this->template issue_piece<1, 7>(1);
       fence();
       epilogue(m0, n0);
       fence();
@@ -463,10 +439,10 @@ struct PipeP {
     }
     da.set_tile(m0, true, wave, lane);
     db.set_tile(n0, true, wave, lane);
-    da.template issue<A_BASE>(smem, 0, wave);
-    db.template issue<B_BASE>(smem, 0, wave);
-    da.template issue<A_BASE + TILE>(smem, 1, wave);
-    db.template issue<B_BASE + TILE>(smem, 1, wave);
+    da.issue(smem, A_BASE, 0, wave);
+    db.issue(smem, B_BASE, 0, wave);
+    da.issue(smem, A_BASE + TILE, 1, wave);
+    db.issue(smem, B_BASE + TILE, 1, wave);
     fence();   // (the waits below count on this issue order: DMA pieces, then accumulator loads)
     const bool loads = init_acc(m0, n0);
     fence();
@@ -475,9 +451,7 @@ struct PipeP {
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    fb.template read_range<0, 0, 0, NI>(bk[0]);
-    prologue_a<0>();
-    __builtin_amdgcn_sched_barrier(0);
+    this->prime();
     kti = 0;
     pend = false;
     has_next = false;

@@ -1,6 +1,11 @@
 // Host side of the persistent 256 x 256 GEMM (gemm256p.h): eligibility, tile queues, launch.  Called from muse_gemm (gemm.hip).
 #include "gemm256p.h"
 #include "gemm_p.h"
+// Not used here.  It instantiates the four half-operand g256::kernel<float, .., 64, true> in this translation unit as well (through the
+// non-template launch_gemm256_f16), as the device header itself did before the launchers moved out of it: without them hipcc compiles
+// g256p::kernel<unsigned short, 0, 1> (dX) with two set-up instructions fewer, and that build measured 0.3 - 0.6 us above the parent's
+// spread on dX QKV (profiles/gemm256_refactor_isa.md).  Delete the line to drop the duplicates (~76 KB of code) when that is re-measured.
+#include "gemm256_host.h"
 #include <mutex>
 #include <stdio.h>
 

@@ -1,7 +1,7 @@
-// Stand-alone harness for the 256 x 256 LDS-DMA GEMM kernel (open-muse_amd/csrc/gemm256.h): correctness of every operand
+// Stand-alone harness for the 256 x 256 LDS-DMA GEMM kernel (open-muse_amd/csrc/gemm256.h, launched through gemm256_host.h): correctness of every operand
 // layout against a naive kernel (non-symmetric random data, ragged M / N / K, split-K) and timing on the transformer shapes.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value -I open-muse_amd/csrc scripts/exp/gemm256g.hip -o /tmp/g256g && /tmp/g256g
-#include "gemm256.h"
+#include "gemm256_host.h"
 #include <cstdio>
 #include <cstring>
 #include <vector>

@@ -6,7 +6,7 @@ Why integers: with |a|, |b| integers and K max|a| max|b| < 2^24 every product an
 so the f32 result does not depend on the accumulation order, the tile shape, the K split or the pipeline depth - every path must return
 the reference bit for bit, and a bf16 output must be the bf16 rounding of it.  `assert_exact` guards that bound for every case.
 
-Storage contract of an operand (include/muse_hip.h, PlainLoader of csrc/gemm_core.h, Dma / Dma32 of csrc/gemm256.h): the loaders fetch
+Storage contract of an operand (include/muse_hip.h, PlainLoader of csrc/gemm_core.h, Dma<L, BK> of csrc/gemm256.h): the loaders fetch
 16-byte chunks along the contiguous dimension and mask a chunk by its FIRST element, so they may read
   k-contiguous X(r, k) at r * ld + k:  rows r < R, columns k < roundup(K, chunk) - the columns K .. roundup(K, chunk) must hold zeros;
   k-major      X(r, k) at k * ld + r:  rows k < K exactly, columns r < roundup(R, chunk) - those extra columns only feed output rows /

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every GEMM path of csrc/ (gemm_core.h, gemm256.h, gemm256p.h, gemm_p.hip, gemm.hip) and the slice reducers of rowops.hip
+"""GPU (-m gpu): every GEMM path of csrc/ (gemm_core.h, gemm256.h, gemm256_host.h, gemm256p.h, gemm_p.h, gemm_p.hip, gemm.hip) and the slice reducers of rowops.hip
 with EXACT integer probes at each edge of their dispatch, plus a small per-element rounding leg.  tests/gemm_cpu.py holds the reference,
 the storage builders, the checks and a tiled contract model; tests/test_gemm_cpu.py proves on a CPU that the checks fail for nine seeded
 bookkeeping defects.  profiles/gemm_edges.md has the edge table and the MI355X's figures; DESIGN.md ("GEMM output contract") the contract.
@@ -7,7 +7,7 @@ Every exact case (run_case):
   * operands are seeded integers with K max|a| max|b| < 2^24 (gemm_cpu.assert_exact), the reference is float64 on the CPU: an f32 output
     must be torch.equal to it, a bf16 output bit-equal to its round-to-nearest-even - or, with a residual / an old C, to the once- or
     twice-rounded value DESIGN.md lists for the path (contract_rounding);
-  * operand storage contract (include/muse_hip.h "Requirements", PlainLoader::load of gemm_core.h, Dma::init / issue of gemm256.h): the
+  * operand storage contract (include/muse_hip.h "Requirements", PlainLoader::load of gemm_core.h, Dma<L, BK>::init / issue of gemm256.h): the
     loaders fetch 16-byte chunks and mask a chunk by its first element, so a k-contiguous operand is read on rows r < R and columns
     k < roundup(K, chunk) - columns K .. roundup(K, chunk) must hold zeros and do -, a k-major one on k rows < K and columns
     r < roundup(R, chunk).  Everything else (rows past M / N / K, columns up to ld, the bytes in front of the operand's offset, the gap
@@ -25,9 +25,9 @@ Edges (thresholds as the code has them; file: function):
       EPC = 4 f32 / 8 bf16 (gemm_kernel: `fast`); each condition flipped alone (EPILOGUE_FLIPS)
     atomic split-K: split_k in {2, 3, 7} at nk = 4 and 9 (per = ceil(nk / split_k): nk = 4, split 3 leaves slice 2 empty; nk = 9,
       split 7 leaves slices 5, 6 empty); workspace split-K: the same, into NaN
-  256^2 launch-per-tile kernel, MUSE_GEMM256=1 MUSE_G256P=0 (gemm256.h: tile_body, Pipe / Pipe32, gemm256_ok; gemm.hip: takes_gemm256)
+  256^2 launch-per-tile kernel, MUSE_GEMM256=1 MUSE_G256P=0 (gemm256.h: tile_body, Pipe / Pipe32; gemm_p.h: gemm256_ok; gemm.hip: takes_gemm256)
     M in {8, 64, 248, 256, 264, 520}, N in {8, 256, 264}, K in {8, 56, 64, 72, 120, 128, 136, 200} (kt_last even round-up: nk = 1, 3),
-    MUSE_G256_BK = 64 | 32 (launch_gemm256_l), act = 1 -> 128 (gemm256_ok)
+    MUSE_G256_BK = 64 | 32 (gemm256_host.h: launch_gemm256_l), act = 1 -> 128 (gemm256_ok)
   persistent kernel, MUSE_G256P=1 (gemm_p.hip: eligible, launch; gemm256p.h): K <= 128 -> 256; M < 256 has ntm_full = 0 (strip only);
     N = 256 t at M = 256, t = 1 .. 9: nfull % 8 = 1 .. 7, 0, 1 (sc.q, sc.r: the per-XCD queue lengths); > 256 tiles -> a.dyn
   muse_gemm_x3 (gemm.hip; gemm256.h: PipeX3): M, N >= 128, K >= 64, batch 1, no act, a_lo / b_lo positive multiples of 8

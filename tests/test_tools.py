@@ -351,3 +351,48 @@ def test_bf16x3_attention_shape_logic_and_step_timeline_on_cpu(tmp_path):
     lines = [l for l in out.splitlines() if " ms | " in l]
     assert len(lines) >= 10 and lines[2].split("|")[2].strip().startswith("1.00") and lines[7].split("|")[2].strip().startswith("0.00")
     assert (tmp_path / "step.csv").read_text().count("\n") >= 3
+
+
+def test_kernel_digest_parser_on_a_synthetic_listing():
+    """scripts/kernel_digest.py: kernels only (.amdhsa_kernel), instructions counted without labels / directives / comments, figures from the
+    '; Kernel info' block, and a digest that ignores comments and the function number of local labels but not an instruction or its order"""
+    spec = importlib.util.spec_from_file_location("kernel_digest", os.path.join(ROOT, "scripts", "kernel_digest.py"))
+    kd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kd)
+
+    def listing(fn, body):
+        return f"""\t.text
+\t.globl\t_Z1kv
+_Z1kv:                                  ; @_Z1kv
+; %bb.0:
+\ts_load_dword s0, s[4:5], 0x0       ; a comment
+{body}
+\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.amdhsa_kernel _Z1kv
+\t\t.amdhsa_next_free_vgpr 7
+\t.end_amdhsa_kernel
+\t.text
+.Lfunc_end{fn}:
+\t.size\t_Z1kv, .Lfunc_end{fn}-_Z1kv
+; Kernel info:
+; codeLenInByte = 40
+; TotalNumSgprs: 12
+; NumVgprs: 7
+; ScratchSize: 16
+; Occupancy: 8
+_Z6helperv:
+\tv_mov_b32_e32 v0, 0
+\ts_setpc_b64 s[30:31]
+.Lfunc_end{fn + 1}:
+; NumVgprs: 99
+"""
+    loop = lambda fn, a, b: f"\ts_cmp_lt_i32 s0, 1\n\ts_cbranch_scc1 .LBB{fn}_2\n.LBB{fn}_1:   ; loop\n\t{a}\n\t{b}\n.LBB{fn}_2:"
+    k, = kd.parse(listing(0, loop(0, "v_add_u32_e32 v1, v0, v0", "v_mul_lo_u32 v2, v1, v1")))
+    assert k["name"] == "_Z1kv" and k["insts"] == 6                      # (the device function is no kernel; labels are no instructions)
+    assert (k["vgprs"], k["sgprs"], k["scratch"], k["occupancy"]) == (7, 12, 16, 8)
+    same, = kd.parse(listing(3, loop(3, "v_add_u32_e32   v1, v0, v0 ; other comment", "v_mul_lo_u32 v2, v1, v1")))
+    assert same["digest"] == k["digest"]                                 # another function number, spacing, comments
+    swapped, = kd.parse(listing(0, loop(0, "v_mul_lo_u32 v2, v1, v1", "v_add_u32_e32 v1, v0, v0")))
+    renamed, = kd.parse(listing(0, loop(0, "v_add_u32_e32 v1, v0, v0", "v_mul_lo_u32 v3, v1, v1")))
+    assert swapped["insts"] == 6 and len({k["digest"], swapped["digest"], renamed["digest"]}) == 3
