@@ -186,6 +186,27 @@ template <bool FAST> __device__ __forceinline__ float gelu_erf_grad_t(float x) {
   return cdf + x * pdf;
 }
 
+// ---- the bias-free GLU element: h = gelu(a) * b,  d(a, b) = (d * b * gelu'(a), d * gelu(a)) -----------------------------------------
+// The ONE definition every kernel that computes it uses (rowops.hip: the glu_* and ffn_mid_* kernels).  The *_erf forms are for a
+// kernel that has e = erf_rsqrt2<FAST>(a) already: one erf serves gelu (0.5 a (1 + e)), the distribution function of gelu'
+// (0.5 (1 + e)) and, with FAST, the exponential of its density.
+// glu_bwd_elem and glu_bwd_elem_erf are the same expressions but NOT interchangeable, hence the two names: which product of
+// cdf + a * pdf the compiler fuses into the addition depends on whether 1 + e has a second use, and the other choice rounds d(a)
+// differently in its last f32 bits.  Each kernel stays on the form it was written with; a kernel and its dropped / operand-image twin,
+// which the tests hold together bit for bit in f32, share a form.  The gradient comes first in the parameter list: the compiler
+// orders the operands of d * b by it (profiles/glu_refactor_isa.md).
+template <bool FAST> __device__ __forceinline__ float glu_fwd_elem_erf(float a, float b, float e) { return 0.5f * a * (1.0f + e) * b; }
+template <bool FAST> __device__ __forceinline__ float glu_fwd_elem(float a, float b) { return gelu_erf_t<FAST>(a) * b; }
+template <bool FAST> __device__ __forceinline__ void glu_bwd_elem_erf(float d, float a, float b, float e, float& da, float& db) {
+  const float cdf = 0.5f * (1.0f + e), pdf = 0.39894228040143267794f * __expf(-0.5f * a * a);
+  da = d * b * (cdf + a * pdf);
+  db = d * (0.5f * a * (1.0f + e));
+}
+template <bool FAST> __device__ __forceinline__ void glu_bwd_elem(float d, float a, float b, float& da, float& db) {
+  da = d * b * gelu_erf_grad_t<FAST>(a);
+  db = d * gelu_erf_t<FAST>(a);
+}
+
 #define MUSE_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
 // ---- per-device launch state (host) ------------------------------------------------------------------------------------------------

@@ -442,7 +442,7 @@ __global__ __launch_bounds__(256) void ffn_mid_fwd_kernel(const T* __restrict__ 
         float a[4], b[4], o[4];
         V4<T>::load(abr + c, a); V4<T>::load(abr + inter + c, b);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = gelu_erf_t<sizeof(T) == 2>(a[j]) * b[j];
+        for (int j = 0; j < 4; ++j) o[j] = glu_fwd_elem<sizeof(T) == 2>(a[j], b[j]);
         if (h) V4<T>::store(h + (long)row * inter + c, o);
         if (sizeof(T) == 2) {  // LayerNorm sees the stored (bf16-rounded) h, exactly like the unfused path
 #pragma unroll
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256) void ffn_mid_bwd_kernel(const T* __restrict__ 
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             ev[k][j] = erf_rsqrt2<sizeof(T) == 2>(a[j]);
-            x[j] = 0.5f * a[j] * (1.0f + ev[k][j]) * b[j];           // == gelu_erf(a) * b, bit for bit
+            x[j] = glu_fwd_elem_erf<sizeof(T) == 2>(a[j], b[j], ev[k][j]);
             if (sizeof(T) == 2) x[j] = bf16_to_f32(f32_to_bf16(x[j]));
           }
         } else {
@@ -562,17 +562,14 @@ __global__ __launch_bounds__(256) void ffn_mid_bwd_kernel(const T* __restrict__ 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if constexpr (RECOMP) {
-            const float e = ev[k][j], g = 0.5f * a[j] * (1.0f + e);
-            float hq = g * b[j];
+            const float e = ev[k][j];
+            float hq = glu_fwd_elem_erf<sizeof(T) == 2>(a[j], b[j], e);
             if (sizeof(T) == 2) hq = bf16_to_f32(f32_to_bf16(hq));
             const float dh = rs * (gk[k][j] - c1 - ((hq - mu) * rs) * c2);
-            const float cdf = 0.5f * (1.0f + e), pdf = 0.39894228040143267794f * __expf(-0.5f * a[j] * a[j]);
-            da[j] = dh * b[j] * (cdf + a[j] * pdf);                  // == gelu_erf_grad(a)
-            db[j] = dh * g;
+            glu_bwd_elem_erf<sizeof(T) == 2>(dh, a[j], b[j], e, da[j], db[j]);
           } else {
             const float dh = rs * (gk[k][j] - c1 - xh[k][j] * c2);
-            da[j] = dh * b[j] * gelu_erf_grad_t<sizeof(T) == 2>(a[j]);
-            db[j] = dh * gelu_erf_t<sizeof(T) == 2>(a[j]);
+            glu_bwd_elem<sizeof(T) == 2>(dh, a[j], b[j], da[j], db[j]);
           }
         }
         V4<T>::store(dr + c, da); V4<T>::store(dr + inter + c, db);
@@ -639,7 +636,7 @@ __global__ __launch_bounds__(256) void ffn_mid_fwd2_kernel(const bf16_t* __restr
       float a[8], b[8];
       unpack8(ra[k], a); unpack8(rb[k], b);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) hv[k][j] = gelu_erf_t<true>(a[j]) * b[j];
+      for (int j = 0; j < 8; ++j) hv[k][j] = glu_fwd_elem<true>(a[j], b[j]);
       const u32x4 o = pack8(hv[k]);
       if (live && h) *(u32x4*)(h + (long)row * inter + k * 1024 + t * 8) = o;   // (h == nullptr: the backward recomputes it)
       unpack8(o, hv[k]);   // LayerNorm sees the stored (bf16-rounded) h, exactly like the unfused path
@@ -723,8 +720,7 @@ __global__ __launch_bounds__(256) void ffn_mid_bwd2_kernel(const bf16_t* __restr
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float dh = rs * (gk[k][j] - c1 - xh[k][j] * c2);
-          da[j] = dh * b[j] * gelu_erf_grad_t<true>(a[j]);
-          db[j] = dh * gelu_erf_t<true>(a[j]);
+          glu_bwd_elem<true>(dh, a[j], b[j], da[j], db[j]);
         }
         *(u32x4*)(dr + k * 1024 + t * 8) = pack8(da);
         *(u32x4*)(dr + inter + k * 1024 + t * 8) = pack8(db);
@@ -915,20 +911,66 @@ extern "C" int muse_softmax_bwd(const void* p, const void* dp, void* ds, int32_t
 // =================================================================================================================
 // GLU / GELU element kernels (4 elements per thread)
 // =================================================================================================================
-template <typename T>
-__global__ void glu_fwd_kernel(const T* __restrict__ ab, T* __restrict__ h, long rows, int inter) {
-  const long n4 = rows * (inter / 4);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+// The GLU (common.h glu_fwd_elem / glu_bwd_elem*) over [rows, 2 * inter] -> [rows, inter], a thread owning four consecutive, 4-aligned
+// columns of a row.  The forward kernels are ONE grid-stride loop (glu_fwd_body); what they differ in is three switches of it:
+//   DROP  nn.Dropout on the GLU's output (reference muse/modeling_transformer_v2.py:933,947, the U-ViT's `hidden_dropout`): the keep bit
+//         of muse_dropout(seed, offset) for flat element r * inter + c of the [rows, inter] result - the thread's four columns are one
+//         Philox block.  forward: h = keep * s * (gelu(a) * b), one f32 product before the output rounding / the plane split / the half
+//         image;  backward: d = keep * s * dh in f32, then the plain expressions.
+//   OPT   the result pointer (h / dab) may be null: only the operand image is written
+//   IMG   the result ALSO as the operand image of the product that reads it (muse_gemm_x3: h feeds the FFN's output projection, d(ab) the
+//         dX and dW products of its input projection) - the separate split pass (read 4 + write 4 bytes per element) becomes 4 written
+//         bytes here.  "bf16x3" mode: planes [2][rows][cols] bf16, hi plane first, the bits of muse_split_f32_to_bf16x2; "f16" mode: the
+//         half image instead (ImgFormat, common.h store_image4).
+// Every forward __global__ is a wrapper that reads the grid builtins and hands them to the body (GLU_WALK, a macro for that reason): read inside the shared
+// body, the block size would come through the generic implicit-argument path (5 to 6 instructions more per kernel); the index
+// arithmetic stays in the body, behind n4, where the compiler schedules it as it did for the separate kernels
+// (profiles/glu_refactor_isa.md).
+struct Keep { float p, scale; uint64_t seed, offset; };         // scale = 1 / (1 - p)
+struct GridWalk {
+  unsigned block, width, lane, blocks;
+  __device__ __forceinline__ long origin() const { return (long)block * width + lane; }
+  __device__ __forceinline__ long step() const { return (long)blocks * width; }
+};
+#define GLU_WALK GridWalk{blockIdx.x, blockDim.x, threadIdx.x, gridDim.x}      // (a macro: see above)
+__device__ __forceinline__ void store_planes4(bf16_t* hi, long plane, const ImgFormat& f, long idx, const float (&o)[4]) {
+  store_image4(hi + idx, plane, f.scale, f.stats, o[0], o[1], o[2], o[3]);
+}
+template <typename T, bool DROP, bool OPT, bool IMG>
+__device__ __forceinline__ void glu_fwd_body(GridWalk w, const T* __restrict__ ab, T* __restrict__ h, bf16_t* __restrict__ planes,
+                                             long rows, int inter, ImgFormat f, Keep k) {
+  const long n4 = rows * (inter / 4), plane = f.lo_sign * rows * inter;
+  for (long i = w.origin(); i < n4; i += w.step()) {
     const long r = i / (inter / 4);
     const int c = (int)(i - r * (inter / 4)) * 4;
-    float a[4], b[4], o[4];
+    float a[4], b[4], o[4], m[4];
     V4<T>::load(ab + r * 2 * inter + c, a);
     V4<T>::load(ab + r * 2 * inter + inter + c, b);
+    if constexpr (DROP) dropout_mult4(k.seed, k.offset, (uint64_t)i, k.p, k.scale, m);       // (r * inter + c) / 4 == i
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gelu_erf_t<sizeof(T) == 2>(a[j]) * b[j];
-    V4<T>::store(h + r * inter + c, o);
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (DROP) o[j] = m[j] != 0.0f ? glu_fwd_elem<sizeof(T) == 2>(a[j], b[j]) * m[j] : 0.0f;
+      else o[j] = glu_fwd_elem<sizeof(T) == 2>(a[j], b[j]);
+    }
+    if (!OPT || h) V4<T>::store(h + r * inter + c, o);
+    if constexpr (IMG) store_planes4(planes, plane, f, r * inter + c, o);
   }
 }
+template <typename T>
+__global__ void glu_fwd_kernel(const T* __restrict__ ab, T* __restrict__ h, long rows, int inter) {
+  glu_fwd_body<T, false, false, false>(GLU_WALK, ab, h, nullptr, rows, inter, ImgFormat{}, Keep{});
+}
+__global__ void glu_fwd_x3_kernel(const float* __restrict__ ab, float* __restrict__ h, bf16_t* __restrict__ planes, long rows, int inter, ImgFormat f) {
+  glu_fwd_body<float, false, true, true>(GLU_WALK, ab, h, planes, rows, inter, f, Keep{});
+}
+template <typename T, bool X3>
+__global__ void glu_drop_fwd_kernel(const T* __restrict__ ab, T* __restrict__ h, bf16_t* __restrict__ planes, long rows, int inter, ImgFormat f,
+                                    float p, float scale, uint64_t seed, uint64_t offset) {
+  glu_fwd_body<T, true, true, X3>(GLU_WALK, ab, h, planes, rows, inter, f, Keep{p, scale, seed, offset});
+}
+// The backward keeps one loop per kernel.  Behind a shared body the compiler commutes multiplies and assigns the store addresses of the
+// operand-image kernels differently, and those two ran 1.4 to 2.0 % slower on an MI355X (profiles/glu_refactor_isa.md); written out,
+// every backward kernel is the code it was.  What the three share is the element function.
 template <typename T>
 __global__ void glu_bwd_kernel(const T* __restrict__ ab, const T* __restrict__ dh, T* __restrict__ dab, long rows, int inter) {
   const long n4 = rows * (inter / 4);
@@ -940,31 +982,9 @@ __global__ void glu_bwd_kernel(const T* __restrict__ ab, const T* __restrict__ d
     V4<T>::load(ab + r * 2 * inter + inter + c, b);
     V4<T>::load(dh + r * inter + c, d);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { da[j] = d[j] * b[j] * gelu_erf_grad_t<sizeof(T) == 2>(a[j]); db[j] = d[j] * gelu_erf_t<sizeof(T) == 2>(a[j]); }
+    for (int j = 0; j < 4; ++j) glu_bwd_elem<sizeof(T) == 2>(d[j], a[j], b[j], da[j], db[j]);
     V4<T>::store(dab + r * 2 * inter + c, da);
     V4<T>::store(dab + r * 2 * inter + inter + c, db);
-  }
-}
-// f32 GLU of the "bf16x3" compute mode: the same expressions as glu_*_kernel<float> (the same f32 bits), and the result ALSO as the
-// (hi, lo) bf16 operand planes of the product that reads it (muse_gemm_x3: h feeds the FFN's output projection, d(ab) the dX and dW
-// products of its input projection) - the separate split pass (read 4 + write 4 bytes per element) becomes 4 written bytes here.
-// planes: [2][rows][cols] bf16, hi plane first; split4 is the split muse_split_f32_to_bf16x2 applies, so the planes are its bits.
-// (ImgFormat: the "f16" mode's half image instead - common.h store_image4)
-__device__ __forceinline__ void store_planes4(bf16_t* hi, long plane, const ImgFormat& f, long idx, const float (&o)[4]) {
-  store_image4(hi + idx, plane, f.scale, f.stats, o[0], o[1], o[2], o[3]);
-}
-__global__ void glu_fwd_x3_kernel(const float* __restrict__ ab, float* __restrict__ h, bf16_t* __restrict__ planes, long rows, int inter, ImgFormat f) {
-  const long n4 = rows * (inter / 4), plane = f.lo_sign * rows * inter;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const long r = i / (inter / 4);
-    const int c = (int)(i - r * (inter / 4)) * 4;
-    float a[4], b[4], o[4];
-    V4<float>::load(ab + r * 2 * inter + c, a);
-    V4<float>::load(ab + r * 2 * inter + inter + c, b);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gelu_erf_t<false>(a[j]) * b[j];
-    if (h) V4<float>::store(h + r * inter + c, o);
-    store_planes4(planes, plane, f, r * inter + c, o);
   }
 }
 __global__ void glu_bwd_x3_kernel(const float* __restrict__ ab, const float* __restrict__ dh, float* __restrict__ dab, bf16_t* __restrict__ planes,
@@ -978,130 +998,13 @@ __global__ void glu_bwd_x3_kernel(const float* __restrict__ ab, const float* __r
     V4<float>::load(ab + r * 2 * inter + inter + c, b);
     V4<float>::load(dh + r * inter + c, d);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { da[j] = d[j] * b[j] * gelu_erf_grad_t<false>(a[j]); db[j] = d[j] * gelu_erf_t<false>(a[j]); }
+    for (int j = 0; j < 4; ++j) glu_bwd_elem<false>(d[j], a[j], b[j], da[j], db[j]);
     if (dab) {
       V4<float>::store(dab + r * 2 * inter + c, da);
       V4<float>::store(dab + r * 2 * inter + inter + c, db);
     }
     store_planes4(planes, plane, f, r * 2 * inter + c, da);
     store_planes4(planes, plane, f, r * 2 * inter + inter + c, db);
-  }
-}
-extern "C" int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, int32_t half, float scale, int32_t* stats,
-                               void* stream) {
-  ImgFormat f;
-  if (inter % 4 || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (!planes) return MUSE_ERR_BAD_ARG;
-  if ((((uintptr_t)ab) | ((uintptr_t)h)) & 15 || (((uintptr_t)planes) & 7) || ((rows * inter) & 3)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL(glu_fwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, h, (bf16_t*)planes, (long)rows, inter, f);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, int32_t half, float scale,
-                               int32_t* stats, void* stream) {
-  ImgFormat f;
-  if (inter % 4 || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (!planes) return MUSE_ERR_BAD_ARG;
-  if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL(glu_bwd_x3_kernel, dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, dh, dab, (bf16_t*)planes, (long)rows, inter, f);
-  return (int)hipGetLastError();
-}
-// bf16, inter % 8 == 0: eight columns of one row per thread (16-byte accesses), rows walked by blockIdx.y - no 64-bit index
-// division per element (the generic kernels above spend more on `i / (inter / 4)` than on the arithmetic), erf evaluated once per
-// element in the backward.  Same expressions per element as the generic kernels -> the same bits.
-__device__ __forceinline__ void unpack8_bf16(const u32x4& v, float (&o)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { o[2 * j] = __uint_as_float(v[j] << 16); o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u); }
-}
-__device__ __forceinline__ u32x4 pack8_bf16(const float (&x)[8]) {
-  return u32x4{pack2_bf16(x[0], x[1]), pack2_bf16(x[2], x[3]), pack2_bf16(x[4], x[5]), pack2_bf16(x[6], x[7])};
-}
-__global__ __launch_bounds__(256) void glu_fwd8_kernel(const bf16_t* __restrict__ ab, bf16_t* __restrict__ h, long rows, int inter) {
-  const int c = (blockIdx.x * 256 + threadIdx.x) * 8;
-  if (c >= inter) return;
-  for (long r = blockIdx.y; r < rows; r += gridDim.y) {
-    const bf16_t* src = ab + r * 2 * inter + c;
-    const u32x4 ra = *(const u32x4*)src, rb = *(const u32x4*)(src + inter);
-    float a[8], b[8], o[8];
-    unpack8_bf16(ra, a); unpack8_bf16(rb, b);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = gelu_erf_t<true>(a[j]) * b[j];
-    *(u32x4*)(h + r * inter + c) = pack8_bf16(o);
-  }
-}
-__global__ __launch_bounds__(256) void glu_bwd8_kernel(const bf16_t* __restrict__ ab, const bf16_t* __restrict__ dh, bf16_t* __restrict__ dab,
-                                                       long rows, int inter) {
-  const int c = (blockIdx.x * 256 + threadIdx.x) * 8;
-  if (c >= inter) return;
-  for (long r = blockIdx.y; r < rows; r += gridDim.y) {
-    const bf16_t* src = ab + r * 2 * inter + c;
-    const u32x4 ra = *(const u32x4*)src, rb = *(const u32x4*)(src + inter), rd = *(const u32x4*)(dh + r * inter + c);
-    float a[8], b[8], d[8], da[8], db[8];
-    unpack8_bf16(ra, a); unpack8_bf16(rb, b); unpack8_bf16(rd, d);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float e = erf_rsqrt2<true>(a[j]);
-      const float cdf = 0.5f * (1.0f + e), pdf = 0.39894228040143267794f * __expf(-0.5f * a[j] * a[j]);
-      da[j] = d[j] * b[j] * (cdf + a[j] * pdf);               // == d * b * gelu_erf_grad(a)
-      db[j] = d[j] * (0.5f * a[j] * (1.0f + e));              // == d * gelu_erf(a)
-    }
-    bf16_t* dst = dab + r * 2 * inter + c;
-    *(u32x4*)dst = pack8_bf16(da);
-    *(u32x4*)(dst + inter) = pack8_bf16(db);
-  }
-}
-static inline dim3 glu8_grid(long rows, int inter) {
-  const int gx = (inter / 8 + 255) / 256;
-  long gy = 16384 / gx; if (gy > rows) gy = rows; if (gy < 1) gy = 1;
-  return dim3(gx, (unsigned)gy);
-}
-
-extern "C" int muse_glu_fwd(const void* ab, void* h, int32_t dtype, int64_t rows, int32_t inter, void* stream) {
-  if (inter % 4) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (dtype == MUSE_BF16 && (inter % 8) == 0 && !((((uintptr_t)ab) | ((uintptr_t)h)) & 15)) {
-    hipLaunchKernelGGL(glu_fwd8_kernel, glu8_grid(rows, inter), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (bf16_t*)h, (long)rows, inter);
-    return (int)hipGetLastError();
-  }
-  const int g = ew_grid(rows * (inter / 4));
-  if (dtype == MUSE_F32) hipLaunchKernelGGL(glu_fwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (float*)h, (long)rows, inter);
-  else hipLaunchKernelGGL(glu_fwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (bf16_t*)h, (long)rows, inter);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_glu_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64_t rows, int32_t inter, void* stream) {
-  if (inter % 4) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (dtype == MUSE_BF16 && (inter % 8) == 0 && !((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & 15)) {
-    hipLaunchKernelGGL(glu_bwd8_kernel, glu8_grid(rows, inter), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab, (long)rows, inter);
-    return (int)hipGetLastError();
-  }
-  const int g = ew_grid(rows * (inter / 4));
-  if (dtype == MUSE_F32) hipLaunchKernelGGL(glu_bwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (const float*)dh, (float*)dab, (long)rows, inter);
-  else hipLaunchKernelGGL(glu_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab, (long)rows, inter);
-  return (int)hipGetLastError();
-}
-
-// GLU with nn.Dropout on its output (reference muse/modeling_transformer_v2.py:933,947, the U-ViT's `hidden_dropout`): the keep bit of
-// muse_dropout(seed, offset) for flat element r * inter + c of the [rows, inter] result, applied inside the kernel.  A thread owns four
-// consecutive, 4-aligned columns = one Philox block.  forward: h = keep * s * (gelu(a) * b), one f32 product before the output rounding /
-// the plane split / the half image;  backward: d = keep * s * dh in f32, then the expressions of glu_bwd_kernel.  X3: the operand image
-// next to (or instead of: h / dab null) the result, as glu_*_x3_kernel.
-template <typename T, bool X3>
-__global__ void glu_drop_fwd_kernel(const T* __restrict__ ab, T* __restrict__ h, bf16_t* __restrict__ planes, long rows, int inter, ImgFormat f,
-                                    float p, float scale, uint64_t seed, uint64_t offset) {
-  const long n4 = rows * (inter / 4), plane = f.lo_sign * rows * inter;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const long r = i / (inter / 4);
-    const int c = (int)(i - r * (inter / 4)) * 4;
-    float a[4], b[4], o[4], m[4];
-    V4<T>::load(ab + r * 2 * inter + c, a);
-    V4<T>::load(ab + r * 2 * inter + inter + c, b);
-    dropout_mult4(seed, offset, (uint64_t)i, p, scale, m);       // (r * inter + c) / 4 == i
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = m[j] != 0.0f ? (gelu_erf_t<sizeof(T) == 2>(a[j]) * b[j]) * m[j] : 0.0f;
-    if (h) V4<T>::store(h + r * inter + c, o);
-    if constexpr (X3) store_planes4(planes, plane, f, r * inter + c, o);
   }
 }
 template <typename T, bool X3>
@@ -1119,8 +1022,7 @@ __global__ void glu_drop_bwd_kernel(const T* __restrict__ ab, const T* __restric
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float de = m[j] != 0.0f ? d[j] * m[j] : 0.0f;
-      da[j] = de * b[j] * gelu_erf_grad_t<sizeof(T) == 2>(a[j]);
-      db[j] = de * gelu_erf_t<sizeof(T) == 2>(a[j]);
+      glu_bwd_elem<sizeof(T) == 2>(de, a[j], b[j], da[j], db[j]);
     }
     if (dab) {
       V4<T>::store(dab + r * 2 * inter + c, da);
@@ -1132,70 +1034,136 @@ __global__ void glu_drop_bwd_kernel(const T* __restrict__ ab, const T* __restric
     }
   }
 }
-static inline int glu_drop_args(const void* ab, int64_t rows, int32_t inter, float p) {
-  if (!ab || inter <= 0 || !(p >= 0.0f && p < 1.0f)) return MUSE_ERR_BAD_ARG;
-  if (inter % 4) return MUSE_ERR_UNSUPPORTED;     // a thread's four columns are one Philox block: the caller drops with muse_dropout
-  (void)rows;
-  return 0;
+// bf16, inter % 8 == 0: eight columns of one row per thread (16-byte accesses), rows walked by blockIdx.y - no 64-bit index
+// division per element (the generic kernels above spend more on `i / (inter / 4)` than on the arithmetic).  The same element
+// functions as the generic kernels -> the same bits.
+__global__ __launch_bounds__(256) void glu_fwd8_kernel(const bf16_t* __restrict__ ab, bf16_t* __restrict__ h, long rows, int inter) {
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (c >= inter) return;
+  for (long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const bf16_t* src = ab + r * 2 * inter + c;
+    const u32x4 ra = *(const u32x4*)src, rb = *(const u32x4*)(src + inter);
+    float a[8], b[8], o[8];
+    unpack8(ra, a); unpack8(rb, b);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = glu_fwd_elem<true>(a[j], b[j]);
+    *(u32x4*)(h + r * inter + c) = pack8(o);
+  }
+}
+__global__ __launch_bounds__(256) void glu_bwd8_kernel(const bf16_t* __restrict__ ab, const bf16_t* __restrict__ dh, bf16_t* __restrict__ dab,
+                                                       long rows, int inter) {
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 8;
+  if (c >= inter) return;
+  for (long r = blockIdx.y; r < rows; r += gridDim.y) {
+    const bf16_t* src = ab + r * 2 * inter + c;
+    const u32x4 ra = *(const u32x4*)src, rb = *(const u32x4*)(src + inter), rd = *(const u32x4*)(dh + r * inter + c);
+    float a[8], b[8], d[8], da[8], db[8];
+    unpack8(ra, a); unpack8(rb, b); unpack8(rd, d);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) glu_bwd_elem_erf<true>(d[j], a[j], b[j], erf_rsqrt2<true>(a[j]), da[j], db[j]);
+    bf16_t* dst = dab + r * 2 * inter + c;
+    *(u32x4*)dst = pack8(da);
+    *(u32x4*)(dst + inter) = pack8(db);
+  }
+}
+static inline dim3 glu8_grid(long rows, int inter) {
+  const int gx = (inter / 8 + 255) / 256;
+  long gy = 16384 / gx; if (gy > rows) gy = rows; if (gy < 1) gy = 1;
+  return dim3(gx, (unsigned)gy);
+}
+
+// ONE launcher behind the eight entry points.  dh: backward only; keep: the dropped forms; img: the *_x3 forms (f32 only).
+struct GluImage { void* planes; int32_t half; float scale; int32_t* stats; };
+struct GluCall { const void* ab; const void* dh; void* out; int32_t dtype; int64_t rows; int32_t inter; const Keep* keep; const GluImage* img; };
+template <typename T, bool BWD>
+static void glu_enqueue(const GluCall& c, const ImgFormat& f, hipStream_t s) {
+  const dim3 grid(ew_grid(c.rows * (c.inter / 4))), block(256);
+  const T *ab = (const T*)c.ab, *dh = (const T*)c.dh;
+  T* out = (T*)c.out;
+  bf16_t* planes = c.img ? (bf16_t*)c.img->planes : nullptr;
+  const long rows = c.rows;
+  const int inter = c.inter;
+  const Keep k = c.keep ? *c.keep : Keep{};
+  if constexpr (!BWD) {
+    if (!c.keep && !c.img) hipLaunchKernelGGL(glu_fwd_kernel<T>, grid, block, 0, s, ab, out, rows, inter);
+    else if (!c.img) hipLaunchKernelGGL((glu_drop_fwd_kernel<T, false>), grid, block, 0, s, ab, out, planes, rows, inter, f, k.p, k.scale, k.seed, k.offset);
+    else if constexpr (sizeof(T) == 4) {
+      if (!c.keep) hipLaunchKernelGGL(glu_fwd_x3_kernel, grid, block, 0, s, ab, out, planes, rows, inter, f);
+      else hipLaunchKernelGGL((glu_drop_fwd_kernel<float, true>), grid, block, 0, s, ab, out, planes, rows, inter, f, k.p, k.scale, k.seed, k.offset);
+    }
+  } else {
+    if (!c.keep && !c.img) hipLaunchKernelGGL(glu_bwd_kernel<T>, grid, block, 0, s, ab, dh, out, rows, inter);
+    else if (!c.img) hipLaunchKernelGGL((glu_drop_bwd_kernel<T, false>), grid, block, 0, s, ab, dh, out, planes, rows, inter, f, k.p, k.scale, k.seed, k.offset);
+    else if constexpr (sizeof(T) == 4) {
+      if (!c.keep) hipLaunchKernelGGL(glu_bwd_x3_kernel, grid, block, 0, s, ab, dh, out, planes, rows, inter, f);
+      else hipLaunchKernelGGL((glu_drop_bwd_kernel<float, true>), grid, block, 0, s, ab, dh, out, planes, rows, inter, f, k.p, k.scale, k.seed, k.offset);
+    }
+  }
+}
+template <bool BWD>
+static int glu_launch(const GluCall& c, void* stream) {
+  if (c.keep) {
+    if (!c.ab || c.inter <= 0 || !(c.keep->p >= 0.0f && c.keep->p < 1.0f)) return MUSE_ERR_BAD_ARG;
+    if (c.inter % 4) return MUSE_ERR_UNSUPPORTED;   // a thread's four columns are one Philox block: the caller drops with muse_dropout
+    if ((BWD && !c.dh) || (!c.img && (!c.out || (c.dtype != MUSE_F32 && c.dtype != MUSE_BF16)))) return MUSE_ERR_BAD_ARG;
+  } else if (c.inter % 4) return MUSE_ERR_BAD_ARG;
+  ImgFormat f{};
+  if (c.img && c.dtype != MUSE_F32) return MUSE_ERR_BAD_ARG;     // (the operand-image kernels are f32 only)
+  if (c.img && !image_format(c.img->half, c.img->scale, c.img->stats, &f)) return MUSE_ERR_BAD_ARG;
+  if (c.rows <= 0) return 0;
+  if (c.img && !c.img->planes) return MUSE_ERR_BAD_ARG;
+  const uintptr_t addr = (uintptr_t)c.ab | (uintptr_t)c.dh | (uintptr_t)c.out;
+  if (c.keep || c.img) {
+    // (with inter % 4 == 0 every row of the result and of the image starts aligned when the tensor does)
+    if ((addr & (c.dtype == MUSE_F32 ? 15 : 7)) || (c.img && ((uintptr_t)c.img->planes & 7))) return MUSE_ERR_ALIGN;
+  } else if (c.dtype == MUSE_BF16 && (c.inter % 8) == 0 && !(addr & 15)) {
+    if constexpr (!BWD) hipLaunchKernelGGL(glu_fwd8_kernel, glu8_grid(c.rows, c.inter), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)c.ab, (bf16_t*)c.out, (long)c.rows, c.inter);
+    else hipLaunchKernelGGL(glu_bwd8_kernel, glu8_grid(c.rows, c.inter), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)c.ab, (const bf16_t*)c.dh, (bf16_t*)c.out, (long)c.rows, c.inter);
+    return (int)hipGetLastError();
+  }
+  if (c.dtype == MUSE_F32) glu_enqueue<float, BWD>(c, f, (hipStream_t)stream);
+  else glu_enqueue<bf16_t, BWD>(c, f, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
+static inline Keep glu_keep(float p, uint64_t seed, uint64_t offset) { return Keep{p, 1.0f / (1.0f - p), seed, offset}; }
+
+extern "C" int muse_glu_fwd(const void* ab, void* h, int32_t dtype, int64_t rows, int32_t inter, void* stream) {
+  return glu_launch<false>(GluCall{ab, nullptr, h, dtype, rows, inter, nullptr, nullptr}, stream);
+}
+extern "C" int muse_glu_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64_t rows, int32_t inter, void* stream) {
+  return glu_launch<true>(GluCall{ab, dh, dab, dtype, rows, inter, nullptr, nullptr}, stream);
+}
+extern "C" int muse_glu_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, int32_t half, float scale, int32_t* stats,
+                               void* stream) {
+  const GluImage img{planes, half, scale, stats};
+  return glu_launch<false>(GluCall{ab, nullptr, h, MUSE_F32, rows, inter, nullptr, &img}, stream);
+}
+extern "C" int muse_glu_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, int32_t half, float scale,
+                               int32_t* stats, void* stream) {
+  const GluImage img{planes, half, scale, stats};
+  return glu_launch<true>(GluCall{ab, dh, dab, MUSE_F32, rows, inter, nullptr, &img}, stream);
 }
 extern "C" int muse_glu_drop_fwd(const void* ab, void* h, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
                                  void* stream) {
-  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
-  if (!h || (dtype != MUSE_F32 && dtype != MUSE_BF16)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if ((((uintptr_t)ab) | ((uintptr_t)h)) & (dtype == MUSE_F32 ? 15 : 7)) return MUSE_ERR_ALIGN;
-  const int g = ew_grid(rows * (inter / 4));
-  const float scale = 1.0f / (1.0f - p);
-  const ImgFormat f{};
-  if (dtype == MUSE_F32)
-    hipLaunchKernelGGL((glu_drop_fwd_kernel<float, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (float*)h, (bf16_t*)nullptr,
-                       (long)rows, inter, f, p, scale, seed, offset);
-  else
-    hipLaunchKernelGGL((glu_drop_fwd_kernel<bf16_t, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (bf16_t*)h, (bf16_t*)nullptr,
-                       (long)rows, inter, f, p, scale, seed, offset);
-  return (int)hipGetLastError();
+  const Keep k = glu_keep(p, seed, offset);
+  return glu_launch<false>(GluCall{ab, nullptr, h, dtype, rows, inter, &k, nullptr}, stream);
 }
 extern "C" int muse_glu_drop_bwd(const void* ab, const void* dh, void* dab, int32_t dtype, int64_t rows, int32_t inter, float p, uint64_t seed,
                                  uint64_t offset, void* stream) {
-  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
-  if (!dh || !dab || (dtype != MUSE_F32 && dtype != MUSE_BF16)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & (dtype == MUSE_F32 ? 15 : 7)) return MUSE_ERR_ALIGN;
-  const int g = ew_grid(rows * (inter / 4));
-  const float scale = 1.0f / (1.0f - p);
-  const ImgFormat f{};
-  if (dtype == MUSE_F32)
-    hipLaunchKernelGGL((glu_drop_bwd_kernel<float, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)ab, (const float*)dh, (float*)dab,
-                       (bf16_t*)nullptr, (long)rows, inter, f, p, scale, seed, offset);
-  else
-    hipLaunchKernelGGL((glu_drop_bwd_kernel<bf16_t, false>), dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)ab, (const bf16_t*)dh, (bf16_t*)dab,
-                       (bf16_t*)nullptr, (long)rows, inter, f, p, scale, seed, offset);
-  return (int)hipGetLastError();
+  const Keep k = glu_keep(p, seed, offset);
+  return glu_launch<true>(GluCall{ab, dh, dab, dtype, rows, inter, &k, nullptr}, stream);
 }
 extern "C" int muse_glu_drop_fwd_x3(const float* ab, float* h, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed, uint64_t offset,
                                     int32_t half, float scale, int32_t* stats, void* stream) {
-  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
-  ImgFormat f;
-  if (!image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (!planes) return MUSE_ERR_BAD_ARG;
-  // (the plain form's (rows * inter) & 3 check is implied here: inter % 4 == 0 was required above)
-  if ((((uintptr_t)ab) | ((uintptr_t)h)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL((glu_drop_fwd_kernel<float, true>), dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, h, (bf16_t*)planes,
-                     (long)rows, inter, f, p, 1.0f / (1.0f - p), seed, offset);
-  return (int)hipGetLastError();
+  const Keep k = glu_keep(p, seed, offset);
+  const GluImage img{planes, half, scale, stats};
+  return glu_launch<false>(GluCall{ab, nullptr, h, MUSE_F32, rows, inter, &k, &img}, stream);
 }
 extern "C" int muse_glu_drop_bwd_x3(const float* ab, const float* dh, float* dab, void* planes, int64_t rows, int32_t inter, float p, uint64_t seed,
                                     uint64_t offset, int32_t half, float scale, int32_t* stats, void* stream) {
-  if (const int e = glu_drop_args(ab, rows, inter, p)) return e;
-  ImgFormat f;
-  if (!dh || !image_format(half, scale, stats, &f)) return MUSE_ERR_BAD_ARG;
-  if (rows <= 0) return 0;
-  if (!planes) return MUSE_ERR_BAD_ARG;
-  if ((((uintptr_t)ab) | ((uintptr_t)dh) | ((uintptr_t)dab)) & 15 || (((uintptr_t)planes) & 7)) return MUSE_ERR_ALIGN;
-  hipLaunchKernelGGL((glu_drop_bwd_kernel<float, true>), dim3(ew_grid(rows * (inter / 4))), dim3(256), 0, (hipStream_t)stream, ab, dh, dab,
-                     (bf16_t*)planes, (long)rows, inter, f, p, 1.0f / (1.0f - p), seed, offset);
-  return (int)hipGetLastError();
+  const Keep k = glu_keep(p, seed, offset);
+  const GluImage img{planes, half, scale, stats};
+  return glu_launch<true>(GluCall{ab, dh, dab, MUSE_F32, rows, inter, &k, &img}, stream);
 }
 
 template <typename T, int MODE>  // MODE 0: y = gelu(x); 1: dx = dy * gelu'(x)

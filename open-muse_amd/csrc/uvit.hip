@@ -329,56 +329,14 @@ __global__ __launch_bounds__(256) void grn_apply_kernel(const float* __restrict_
   }
 }
 // C % 4 == 0: four channels per thread, the image in blockIdx.y (no 64-bit index division per element), f32 and / or bf16 output -
-// the bf16 copy is the next GEMM's operand in the bf16 compute mode, written here instead of by a cast pass over the f32 result
-__global__ __launch_bounds__(256) void grn_apply4_kernel(const float* __restrict__ x, const float* __restrict__ nx,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C) {
-  const int vpp = C >> 2, b = blockIdx.y;
-  const long base = (long)b * S * C;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < S * vpp; i += gridDim.x * 256) {
-    const int c = (i % vpp) * 4;
-    const long e = base + (long)(i / vpp) * C + c;
-    const f32x4 v = *(const f32x4*)(x + e), nn = *(const f32x4*)(nx + (long)b * C + c);
-    const f32x4 ga = *(const f32x4*)(gamma + c), be = *(const f32x4*)(beta + c);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = ga[j] * (v[j] * nn[j]) + be[j] + v[j];
-    if (y) *(f32x4*)(y + e) = o;
-    if (yb) *(u32x2*)(yb + e) = u32x2{pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3])};
-  }
-}
-extern "C" int muse_grn_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch,
-                               int32_t batch, int64_t S, int32_t C, void* stream) {
-  const long n = (long)batch * S * C;
-  if (n <= 0) return 0;
-  if (!y && !y_bf16) return MUSE_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  float* nx = scratch + (long)batch * C;   // scratch = [G | N], both kept for the backward
-  const bool v4 = (C & 3) == 0 && S * (long)(C >> 2) < (1L << 31) && batch <= 65535 && !((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)y_bf16)) & 15);
-  if (y_bf16 && !v4) return MUSE_ERR_UNSUPPORTED;   // only grn_apply4_kernel writes bf16: refused before the statistics are launched
-  hipLaunchKernelGGL(grn_colnorm_kernel, dim3((C + 63) / 64, batch), dim3(256), 0, s, x, scratch, (long)S, C);
-  hipLaunchKernelGGL(grn_scale_kernel, dim3(batch), dim3(256), 0, s, (const float*)scratch, nx, C);
-  if (v4) {
-    long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(grn_apply4_kernel, dim3((unsigned)gx, batch), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (bf16_t*)y_bf16,
-                       (int)S, C);
-    return (int)hipGetLastError();
-  }
-  long g = (n + 255) / 256; if (g > 65535) g = 65535;
-  hipLaunchKernelGGL(grn_apply_kernel, dim3((unsigned)g), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (long)S, C, n);
-  return (int)hipGetLastError();
-}
-extern "C" int muse_grn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* scratch, int32_t batch,
-                            int64_t S, int32_t C, void* stream) {
-  return muse_grn_fwd_ex(x, gamma, beta, y, nullptr, scratch, batch, S, C, stream);
-}
-// ... followed by nn.Dropout (ResBlock.channelwise[3], reference :607): grn_apply4_kernel with muse_dropout's keep bit of flat element
+// the bf16 copy is the next GEMM's operand in the bf16 compute mode, written here instead of by a cast pass over the f32 result.
+// DROP: ... followed by nn.Dropout (ResBlock.channelwise[3], reference :607): muse_dropout's keep bit of flat element
 // (b * S + s) * C + c applied to the result, after the statistics (which see the undropped input).  A thread's four channels are one
 // Philox block.
-__global__ __launch_bounds__(256) void grn_apply4_drop_kernel(const float* __restrict__ x, const float* __restrict__ nx,
-                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C, float p, float scale,
-                                                              uint64_t seed, uint64_t offset) {
+template <bool DROP>
+__device__ __forceinline__ void grn_apply4_body(const float* __restrict__ x, const float* __restrict__ nx, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta, float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C,
+                                                float p, float scale, uint64_t seed, uint64_t offset) {
   const int vpp = C >> 2, b = blockIdx.y;
   const long base = (long)b * S * C;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < S * vpp; i += gridDim.x * 256) {
@@ -387,13 +345,59 @@ __global__ __launch_bounds__(256) void grn_apply4_drop_kernel(const float* __res
     const f32x4 v = *(const f32x4*)(x + e), nn = *(const f32x4*)(nx + (long)b * C + c);
     const f32x4 ga = *(const f32x4*)(gamma + c), be = *(const f32x4*)(beta + c);
     float m[4];
-    dropout_mult4(seed, offset, (uint64_t)(e >> 2), p, scale, m);
+    if constexpr (DROP) dropout_mult4(seed, offset, (uint64_t)(e >> 2), p, scale, m);
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = m[j] != 0.0f ? (ga[j] * (v[j] * nn[j]) + be[j] + v[j]) * m[j] : 0.0f;
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (DROP) o[j] = m[j] != 0.0f ? (ga[j] * (v[j] * nn[j]) + be[j] + v[j]) * m[j] : 0.0f;
+      else o[j] = ga[j] * (v[j] * nn[j]) + be[j] + v[j];
+    }
     if (y) *(f32x4*)(y + e) = o;
     if (yb) *(u32x2*)(yb + e) = u32x2{pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3])};
   }
+}
+__global__ __launch_bounds__(256) void grn_apply4_kernel(const float* __restrict__ x, const float* __restrict__ nx,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C) {
+  grn_apply4_body<false>(x, nx, gamma, beta, y, yb, S, C, 0.f, 0.f, 0, 0);
+}
+__global__ __launch_bounds__(256) void grn_apply4_drop_kernel(const float* __restrict__ x, const float* __restrict__ nx,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float* __restrict__ y, bf16_t* __restrict__ yb, int S, int C, float p, float scale,
+                                                              uint64_t seed, uint64_t offset) {
+  grn_apply4_body<true>(x, nx, gamma, beta, y, yb, S, C, p, scale, seed, offset);
+}
+// the two statistics launches: scratch = [G | N], both kept for the backward; -> N
+static const float* grn_launch_stats(const float* x, float* scratch, int32_t batch, int64_t S, int32_t C, hipStream_t s) {
+  float* nx = scratch + (long)batch * C;
+  hipLaunchKernelGGL(grn_colnorm_kernel, dim3((C + 63) / 64, batch), dim3(256), 0, s, x, scratch, (long)S, C);
+  hipLaunchKernelGGL(grn_scale_kernel, dim3(batch), dim3(256), 0, s, (const float*)scratch, nx, C);
+  return nx;
+}
+static dim3 grn_apply4_grid(int32_t batch, int64_t S, int32_t C) {
+  long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
+  return dim3((unsigned)gx, batch);
+}
+extern "C" int muse_grn_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch,
+                               int32_t batch, int64_t S, int32_t C, void* stream) {
+  const long n = (long)batch * S * C;
+  if (n <= 0) return 0;
+  if (!y && !y_bf16) return MUSE_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool v4 = (C & 3) == 0 && S * (long)(C >> 2) < (1L << 31) && batch <= 65535 && !((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)y_bf16)) & 15);
+  if (y_bf16 && !v4) return MUSE_ERR_UNSUPPORTED;   // only grn_apply4_kernel writes bf16: refused before the statistics are launched
+  const float* nx = grn_launch_stats(x, scratch, batch, S, C, s);
+  if (v4) {
+    hipLaunchKernelGGL(grn_apply4_kernel, grn_apply4_grid(batch, S, C), dim3(256), 0, s, x, nx, gamma, beta, y, (bf16_t*)y_bf16, (int)S, C);
+    return (int)hipGetLastError();
+  }
+  long g = (n + 255) / 256; if (g > 65535) g = 65535;
+  hipLaunchKernelGGL(grn_apply_kernel, dim3((unsigned)g), dim3(256), 0, s, x, nx, gamma, beta, y, (long)S, C, n);
+  return (int)hipGetLastError();
+}
+extern "C" int muse_grn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* scratch, int32_t batch,
+                            int64_t S, int32_t C, void* stream) {
+  return muse_grn_fwd_ex(x, gamma, beta, y, nullptr, scratch, batch, S, C, stream);
 }
 extern "C" int muse_grn_drop_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y_bf16, float* scratch,
                                     int32_t batch, int64_t S, int32_t C, float p, uint64_t seed, uint64_t offset, void* stream) {
@@ -404,12 +408,9 @@ extern "C" int muse_grn_drop_fwd_ex(const float* x, const float* gamma, const fl
   if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)gamma) | ((uintptr_t)beta) | ((uintptr_t)scratch)) & 15 || (((uintptr_t)y_bf16) & 7))
     return MUSE_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
-  float* nx = scratch + (long)batch * C;
-  hipLaunchKernelGGL(grn_colnorm_kernel, dim3((C + 63) / 64, batch), dim3(256), 0, s, x, scratch, (long)S, C);
-  hipLaunchKernelGGL(grn_scale_kernel, dim3(batch), dim3(256), 0, s, (const float*)scratch, nx, C);
-  long gx = (S * (long)(C >> 2) + 255) / 256; if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(grn_apply4_drop_kernel, dim3((unsigned)gx, batch), dim3(256), 0, s, x, (const float*)nx, gamma, beta, y, (bf16_t*)y_bf16,
-                     (int)S, C, p, 1.0f / (1.0f - p), seed, offset);
+  const float* nx = grn_launch_stats(x, scratch, batch, S, C, s);
+  hipLaunchKernelGGL(grn_apply4_drop_kernel, grn_apply4_grid(batch, S, C), dim3(256), 0, s, x, nx, gamma, beta, y, (bf16_t*)y_bf16, (int)S, C,
+                     p, 1.0f / (1.0f - p), seed, offset);
   return (int)hipGetLastError();
 }
 

@@ -1487,109 +1487,65 @@ def grn_drop_ok(B, S, C_):
     return row_drop_ok(C_) and S * (C_ >> 2) < (1 << 31) and B <= 65535
 
 
-def _glu_drop_fwd(ab, planes_only, drop):
-    """glu_fwd with nn.Dropout on the result inside the kernel: the keep bits of ops.dropout(result, *drop)"""
-    rows, two_i = ab.shape
-    inter = two_i // 2
-    d = _row_drop(drop)
-    if not row_drop_ok(inter):
-        if planes_only:
-            raise _hip.MuseHipError("glu_fwd(planes_only=True, drop=) needs inter % 4 == 0")
-        h = glu_fwd(ab)
-        return dropout(h, *d, out=h)          # (no operand image of the undropped h is registered: inter % 8 != 0 writes none)
-    if planes_only:
-        if not (planes_only_ok(rows, inter) and ab.dtype == torch.float32 and ab.is_contiguous()):
-            raise _hip.MuseHipError("glu_fwd(planes_only=True) outside planes_only_ok")
-        planes = planes_alloc((rows, inter), ab.device)
-        check(lib().muse_glu_drop_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, inter, *d, *_image_args(False, planes), stream()),
-              "muse_glu_drop_fwd_x3")
-        return operand_only(planes, False)
-    h = torch.empty((rows, inter), dtype=ab.dtype, device=ab.device)
-    im = _x3_producing(ab)
-    if im is not None and inter % 8 == 0:
-        planes = planes_alloc((rows, inter), ab.device)
-        check(lib().muse_glu_drop_fwd_x3(ab.data_ptr(), h.data_ptr(), planes.data_ptr(), rows, inter, *d, *_image_args(False, planes), stream()),
-              "muse_glu_drop_fwd_x3")
-        im.put_planes(h, planes)
-        return h
-    check(lib().muse_glu_drop_fwd(ab.data_ptr(), h.data_ptr(), dt(ab), rows, inter, *d, stream()), "muse_glu_drop_fwd")
-    return h
-
-
-def _glu_drop_bwd(ab, dh, planes_only, drop):
-    rows, two_i = ab.shape
-    inter = two_i // 2
-    d = _row_drop(drop)
-    if not row_drop_ok(inter):
-        return glu_bwd(ab, dropout(dh.contiguous(), *d), planes_only=planes_only)
-    if planes_only:
-        if not (planes_only_ok(rows, two_i) and ab.dtype == torch.float32 and dh.dtype == torch.float32 and ab.is_contiguous() and dh.is_contiguous()):
-            raise _hip.MuseHipError("glu_bwd(planes_only=True) outside planes_only_ok")
-        planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_drop_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, inter, *d, *_image_args(True, planes), stream()),
-              "muse_glu_drop_bwd_x3")
-        return operand_only(planes, True)
-    if dh.dtype != ab.dtype or not dh.is_contiguous() or not ab.is_contiguous():
-        raise _hip.MuseHipError("glu_bwd(drop=) expects contiguous ab and dh of one dtype")
-    dab = torch.empty_like(ab)
-    im = _x3_producing(ab)
-    if im is not None and dh.dtype == torch.float32 and two_i % 16 == 0:
-        planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_drop_bwd_x3(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), planes.data_ptr(), rows, inter, *d, *_image_args(True, planes),
-                                         stream()), "muse_glu_drop_bwd_x3")
-        im.put_planes(dab, planes)
-        return dab
-    check(lib().muse_glu_drop_bwd(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), dt(ab), rows, inter, *d, stream()), "muse_glu_drop_bwd")
-    return dab
-
-
 def glu_fwd(ab, planes_only=False, drop=None):
     """planes_only (see planes_only_ok): -> OperandOnly, the result as the running pass's GEMM operand image without its f32 tensor.
     drop = (p, seed, offset): nn.Dropout on the result, drawn inside the kernel (the keep bits of ops.dropout on the [rows, inter] result)"""
     require_gpu(ab)
-    if drop is not None:
-        return _glu_drop_fwd(ab, planes_only, drop)
     rows, two_i = ab.shape
+    inter = two_i // 2
+    d = () if drop is None else _row_drop(drop)
+    if d and not row_drop_ok(inter):          # a width the dropped kernels refuse: the plain kernel, then ops.dropout
+        if planes_only:
+            raise _hip.MuseHipError("glu_fwd(planes_only=True, drop=) needs inter % 4 == 0")
+        h = glu_fwd(ab)
+        return dropout(h, *d, out=h)          # (no operand image of the undropped h is registered: inter % 8 != 0 writes none)
+    fn = "muse_glu_drop_fwd" if d else "muse_glu_fwd"
     if planes_only:
-        if not (planes_only_ok(rows, two_i // 2) and ab.dtype == torch.float32 and ab.is_contiguous()):
+        if not (planes_only_ok(rows, inter) and ab.dtype == torch.float32 and ab.is_contiguous()):
             raise _hip.MuseHipError("glu_fwd(planes_only=True) outside planes_only_ok")
-        planes = planes_alloc((rows, two_i // 2), ab.device)
-        check(lib().muse_glu_fwd_x3(ab.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(False, planes), stream()), "muse_glu_fwd_x3")
-        return operand_only(planes, False)
-    h = torch.empty((rows, two_i // 2), dtype=ab.dtype, device=ab.device)
-    im = _x3_producing(ab)
-    if im is not None and (two_i // 2) % 8 == 0:
-        planes = planes_alloc((rows, two_i // 2), ab.device)
-        check(lib().muse_glu_fwd_x3(ab.data_ptr(), h.data_ptr(), planes.data_ptr(), rows, two_i // 2, *_image_args(False, planes), stream()),
-              "muse_glu_fwd_x3")
+        h = im = None
+    else:
+        h = torch.empty((rows, inter), dtype=ab.dtype, device=ab.device)
+        im = _x3_producing(ab)
+    if planes_only or (im is not None and inter % 8 == 0):
+        planes = planes_alloc((rows, inter), ab.device)
+        check(getattr(lib(), fn + "_x3")(ab.data_ptr(), ptr(h), planes.data_ptr(), rows, inter, *d, *_image_args(False, planes), stream()), fn + "_x3")
+        if planes_only:
+            return operand_only(planes, False)
         im.put_planes(h, planes)
         return h
-    check(lib().muse_glu_fwd(ab.data_ptr(), h.data_ptr(), dt(ab), rows, two_i // 2, stream()), "muse_glu_fwd")
+    check(getattr(lib(), fn)(ab.data_ptr(), h.data_ptr(), dt(ab), rows, inter, *d, stream()), fn)
     return h
 
 
 def glu_bwd(ab, dh, planes_only=False, drop=None):
     """drop = glu_fwd's: the same keep mask, redrawn, multiplies dh before anything else"""
     require_gpu(ab, dh)
-    if drop is not None:
-        return _glu_drop_bwd(ab, dh, planes_only, drop)
     rows, two_i = ab.shape
+    inter = two_i // 2
+    d = () if drop is None else _row_drop(drop)
+    if d and not row_drop_ok(inter):
+        return glu_bwd(ab, dropout(dh.contiguous(), *d), planes_only=planes_only)
+    fn = "muse_glu_drop_bwd" if d else "muse_glu_bwd"
     if planes_only:
         if not (planes_only_ok(rows, two_i) and ab.dtype == torch.float32 and dh.dtype == torch.float32 and ab.is_contiguous() and dh.is_contiguous()):
             raise _hip.MuseHipError("glu_bwd(planes_only=True) outside planes_only_ok")
+        dab = im = None
+    else:
+        # (only the dropped route refuses these; without drop a non-contiguous dh merely keeps the call off the operand-image kernel)
+        if d and (dh.dtype != ab.dtype or not dh.is_contiguous() or not ab.is_contiguous()):
+            raise _hip.MuseHipError("glu_bwd(drop=) expects contiguous ab and dh of one dtype")
+        dab = torch.empty_like(ab)
+        im = _x3_producing(ab)
+    if planes_only or (im is not None and dh.dtype == torch.float32 and dh.is_contiguous() and two_i % 16 == 0):
         planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), None, planes.data_ptr(), rows, two_i // 2, *_image_args(True, planes), stream()),
-              "muse_glu_bwd_x3")
-        return operand_only(planes, True)
-    dab = torch.empty_like(ab)
-    im = _x3_producing(ab)
-    if im is not None and dh.dtype == torch.float32 and dh.is_contiguous() and two_i % 16 == 0:
-        planes = planes_alloc((rows, two_i), ab.device)
-        check(lib().muse_glu_bwd_x3(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), planes.data_ptr(), rows, two_i // 2, *_image_args(True, planes),
-                                    stream()), "muse_glu_bwd_x3")
+        check(getattr(lib(), fn + "_x3")(ab.data_ptr(), dh.data_ptr(), ptr(dab), planes.data_ptr(), rows, inter, *d, *_image_args(True, planes), stream()),
+              fn + "_x3")
+        if planes_only:
+            return operand_only(planes, True)
         im.put_planes(dab, planes)
         return dab
-    check(lib().muse_glu_bwd(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), dt(ab), rows, two_i // 2, stream()), "muse_glu_bwd")
+    check(getattr(lib(), fn)(ab.data_ptr(), dh.data_ptr(), dab.data_ptr(), dt(ab), rows, inter, *d, stream()), fn)
     return dab
 
 

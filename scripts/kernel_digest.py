@@ -6,7 +6,9 @@
 Compiles to gfx950 assembly with the Makefile's flags (CXXFLAGS and the file's FLAGS_<name>) plus --cuda-device-only -S (no GPU needed) and
 prints per kernel (demangled): instructions, VGPRs, SGPRs, scratch bytes per lane, occupancy, and a digest of the instruction stream - comments
 and directives dropped, the function number of local labels (.LBB<n>_) normalised - so that a refactor which only moves inlined code between
-templates can show that every kernel came out the same, instruction for instruction.  profiles/gemm256_refactor_isa.md is this output."""
+templates can show that every kernel came out the same, instruction for instruction.  The second digest ("body") is that of the stream from
+the first local label to the end: a kernel whose set-up code before its first branch target was merely reordered shows the same body (a
+kernel without a label has one digest).  profiles/gemm256_refactor_isa.md and profiles/glu_refactor_isa.md are this output."""
 import argparse
 import hashlib
 import os
@@ -18,7 +20,7 @@ INFO = {"NumVgprs": "vgprs", "NumSgprs": "sgprs", "TotalNumSgprs": "sgprs", "Scr
 
 
 def parse(asm):
-    """-> [{name (mangled), insts, vgprs, sgprs, scratch, occupancy, digest}] for every kernel (.amdhsa_kernel) of an assembly listing"""
+    """-> [{name (mangled), insts, vgprs, sgprs, scratch, occupancy, digest, body}] for every kernel (.amdhsa_kernel) of an assembly listing"""
     funcs, kernels, cur, last, info = {}, [], None, None, None
     for raw in asm.splitlines():
         m = re.match(r";\s*(\w+):\s*(\d+)\s*$", raw.strip())
@@ -41,7 +43,8 @@ def parse(asm):
         f = funcs[k]
         stream = f.pop("stream")
         f["insts"] = sum(1 for s in stream if not s.endswith(":"))
-        f["digest"] = hashlib.sha256("\n".join(stream).encode()).hexdigest()[:16]
+        first = next((i for i, s in enumerate(stream) if s.startswith(".LBB") and s.endswith(":")), 0)
+        f["digest"], f["body"] = (hashlib.sha256("\n".join(part).encode()).hexdigest()[:16] for part in (stream, stream[first:]))
         out.append(f)
     return out
 
@@ -73,7 +76,7 @@ if __name__ == "__main__":
             raise SystemExit(r.stderr[-2000:])
         ks = parse(r.stdout)
         names = demangle([k["name"] for k in ks])
-        print(f"### {src}: {len(ks)} kernels\n\n| kernel | insts | VGPRs | SGPRs | scratch | occupancy | digest |\n|---|---|---|---|---|---|---|")
+        print(f"### {src}: {len(ks)} kernels\n\n| kernel | insts | VGPRs | SGPRs | scratch | occupancy | digest | body |\n|---|---|---|---|---|---|---|---|")
         for k in sorted(ks, key=lambda k: names[k["name"]]):
-            print(f"| `{names[k['name']]}` | {k['insts']} | {k.get('vgprs')} | {k.get('sgprs')} | {k.get('scratch')} | {k.get('occupancy')} | {k['digest']} |")
+            print(f"| `{names[k['name']]}` | {k['insts']} | {k.get('vgprs')} | {k.get('sgprs')} | {k.get('scratch')} | {k.get('occupancy')} | {k['digest']} | {k['body']} |")
         print()

@@ -15,7 +15,9 @@ image.
     of the extra multiplication;
   * shapes: rows 1, 63, 257 (one thread row, an odd count, more than one block at 8 columns), cols 8 and 2816 (config 4's
     intermediate_size), 256 rows for the operand-only forms (planes_only_ok wants whole 8-row groups); cols % 4 != 0 is refused by the
-    entry points and served by ops through the two-pass route."""
+    entry points and served by ops through the two-pass route;
+  * a thread's second trip through each GLU loop, plain and dropped: 2049 x 2052 and 2056 x 2048 (more four-column groups than the grid
+    cap of 4096 x 256 threads), 16385 x 8 bf16 (one row more than the 8-wide kernels' 16384 blocks)."""
 import numpy as np
 import pytest
 import torch
@@ -133,6 +135,76 @@ def test_glu_dropped_operand_images_are_the_split_or_cast_of_the_f32_result(mode
                 assert torch.equal(only.planes[0] if mode == "f16" else only.planes, image(want))
             else:
                 assert rows != 256
+
+
+def _halves(fn, cut, *tensors):
+    """fn on the rows [0, cut) and [cut, rows) of its arguments, concatenated: a GLU row depends on nothing but itself"""
+    return torch.cat([fn(*(t[:cut] for t in tensors)), fn(*(t[cut:] for t in tensors))])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_glu_second_trip_through_the_grid_stride_loop(dtype):
+    """2049 x 2052: 1,051,137 four-column groups against the generic kernels' 4096 x 256 = 1,048,576 threads (inter % 8 == 4 keeps
+    bf16 on them too), so the last groups are a thread's second trip.  Plain: the bits of the same call on two row halves (one trip
+    each).  Dropped at p = 0.5 (the scale 2 is exact, so bf16 composes bit for bit as well): the plain kernel and ops.dropout."""
+    ops = _ops()
+    rows, inter, d = 2049, 2052, DROPS[0]
+    assert d[0] == 0.5 and rows * (inter // 4) > 4096 * 256 >= 1025 * (inter // 4) and inter % 8 == 4
+    ab, dh = rnd((rows, 2 * inter), 950).to(dtype).to(DEV), rnd((rows, inter), 951).to(dtype).to(DEV)
+    h, dab = ops.glu_fwd(ab), ops.glu_bwd(ab, dh)
+    assert torch.equal(h, _halves(ops.glu_fwd, 1024, ab))
+    assert torch.equal(dab, _halves(ops.glu_bwd, 1024, ab, dh))
+    assert torch.equal(ops.glu_fwd(ab, drop=d), ops.dropout(h, *d))
+    assert torch.equal(ops.glu_bwd(ab, dh, drop=d), ops.glu_bwd(ab, ops.dropout(dh, *d)))
+
+
+@pytest.mark.parametrize("drop", [None, DROPS[0]], ids=["plain", "dropped"])
+@pytest.mark.parametrize("mode", ["bf16x3", "f16"])
+def test_glu_operand_images_on_a_second_trip_through_the_loop(mode, drop):
+    """2056 x 2048: 1,052,672 groups, the operand-image kernels' second trip.  The result written next to its image is the result
+    outside the step; the image, next to it or alone (planes_only), is the split / half cast of that result."""
+    ops = _ops()
+    rows, inter = 2056, 2048
+    assert rows * (inter // 4) > 4096 * 256
+    ab, dh = rnd((rows, 2 * inter), 952).to(DEV), (rnd((rows, inter), 953) * 1e-3).to(DEV)
+    h0, dab0 = ops.glu_fwd(ab, drop=drop), ops.glu_bwd(ab, dh, drop=drop)
+    # the reference itself stands on calls of one trip each (dropped: the two-pass composition; its keep bits depend on the row offset)
+    h1, dab1 = _halves(ops.glu_fwd, 1024, ab), _halves(ops.glu_bwd, 1024, ab, dh if drop is None else ops.dropout(dh, *drop))
+    assert torch.equal(h0, h1 if drop is None else ops.dropout(h1, *drop)) and torch.equal(dab0, dab1)
+    gs = 2.0 ** 10
+    for bwd in (False, True):
+        if mode == "f16":
+            im = ops.F16Images()
+            im.backward = bwd
+            im.set_grad_scale(gs)
+            scope = ops.f32_gemms_as_f16(True, im)
+        else:
+            im = ops.X3Images()
+            im.backward = bwd
+            scope = ops.f32_gemms_as_bf16x3(True, im)
+        want = dab0 if bwd else h0
+        scale = gs if (bwd and mode == "f16") else 1.0
+        image = (lambda t: ops.cast_to_f16(t, scale)) if mode == "f16" else ops._split_planes_now
+        with scope:
+            got = ops.glu_bwd(ab, dh, drop=drop) if bwd else ops.glu_fwd(ab, drop=drop)
+            assert torch.equal(got, want)
+            misses = im.misses
+            seen = im.image(got, scale) if mode == "f16" else ops.split_planes(got)
+            assert im.misses == misses, "the product reading the result would split / cast it again"
+            assert torch.equal(seen, image(want))
+            assert ops.planes_only_ok(*want.shape)
+            only = ops.glu_bwd(ab, dh, planes_only=True, drop=drop) if bwd else ops.glu_fwd(ab, planes_only=True, drop=drop)
+            assert isinstance(only, ops.OperandOnly) and tuple(only.shape) == tuple(want.shape)
+            assert torch.equal(only.planes[0] if mode == "f16" else only.planes, image(want))
+
+
+def test_glu_eight_wide_kernels_walk_more_rows_than_their_grid():
+    """bf16, inter 8: the 8-wide kernels' grid is 1 x 16384, so row 16384 of 16385 is block 0's second trip"""
+    ops = _ops()
+    rows, inter = 16385, 8
+    ab, dh = rnd((rows, 2 * inter), 954).to(torch.bfloat16).to(DEV), rnd((rows, inter), 955).to(torch.bfloat16).to(DEV)
+    assert torch.equal(ops.glu_fwd(ab), _halves(ops.glu_fwd, 16384, ab))
+    assert torch.equal(ops.glu_bwd(ab, dh), _halves(ops.glu_bwd, 16384, ab, dh))
 
 
 GRN_SHAPES = [(B, S_, C) for (B, S_) in ((1, 1), (3, 21), (1, 257)) for C in (8, 2816)]

@@ -355,7 +355,8 @@ def test_bf16x3_attention_shape_logic_and_step_timeline_on_cpu(tmp_path):
 
 def test_kernel_digest_parser_on_a_synthetic_listing():
     """scripts/kernel_digest.py: kernels only (.amdhsa_kernel), instructions counted without labels / directives / comments, figures from the
-    '; Kernel info' block, and a digest that ignores comments and the function number of local labels but not an instruction or its order"""
+    '; Kernel info' block, and a digest that ignores comments and the function number of local labels but not an instruction or its order;
+    the body digest starts at the first local label, so it ignores the set-up code before it, and is the whole digest without a label"""
     spec = importlib.util.spec_from_file_location("kernel_digest", os.path.join(ROOT, "scripts", "kernel_digest.py"))
     kd = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kd)
@@ -396,3 +397,10 @@ _Z6helperv:
     swapped, = kd.parse(listing(0, loop(0, "v_mul_lo_u32 v2, v1, v1", "v_add_u32_e32 v1, v0, v0")))
     renamed, = kd.parse(listing(0, loop(0, "v_add_u32_e32 v1, v0, v0", "v_mul_lo_u32 v3, v1, v1")))
     assert swapped["insts"] == 6 and len({k["digest"], swapped["digest"], renamed["digest"]}) == 3
+    assert len({k["body"], swapped["body"], renamed["body"]}) == 3 and k["body"] != k["digest"] and same["body"] == k["body"]
+    setup = lambda fn, a, b: f"\t{a}\n\t{b}\n" + loop(fn, "v_add_u32_e32 v1, v0, v0", "v_mul_lo_u32 v2, v1, v1")
+    one, = kd.parse(listing(0, setup(0, "s_mov_b32 s1, 0", "s_mov_b32 s2, 1")))
+    two, = kd.parse(listing(5, setup(5, "s_mov_b32 s2, 1", "s_mov_b32 s1, 0")))
+    assert one["body"] == two["body"] == k["body"] and one["digest"] != two["digest"]   # they differ only before the first label
+    flat, = kd.parse(listing(0, "\tv_add_u32_e32 v1, v0, v0"))
+    assert flat["insts"] == 3 and flat["body"] == flat["digest"]                          # no label: one digest
