@@ -499,6 +499,30 @@ int muse_sample_step(const float* cond_logits, const float* uncond_logits, float
                      uint32_t step, float temperature, int32_t sched_mask_len, int32_t batch, int32_t seq, int64_t* raw_sampled,
                      int64_t* sampled, int64_t* next_ids, float* conf_scratch, void* stream);
 
+/* muse_sample_step sampling from a truncated distribution: top-k and / or nucleus (top-p) filtering inside the same launch pair.
+ * l_j is the logit of code j < vocab after the guidance mix uncond + scale * (cond - uncond), rounded exactly as muse_sample_step
+ * rounds it (the same instructions: f32 difference, then the multiply-add).
+ *   top_k (integer, 1 <= top_k): keep j iff l_j >= v_k, v_k the k-th largest value of the row; all ties at v_k are kept;
+ *     top_k >= vocab means off.
+ *   top_p (float, 0 < top_p <= 1): with p_j = softmax(l)_j over the codes that survive top_k, keep j iff the mass strictly above it,
+ *     M_gt(j) = sum over {i : l_i > l_j} of p_i, is < top_p; a group of tied logits is kept or dropped as a whole; the largest logit
+ *     is always kept; top_p == 1 means off.
+ *   Both given: top_k first, then the nucleus over the distribution renormalised on the top-k set.
+ *   Filtered codes behave exactly as if their logit were -inf before muse_sample_step: probability exactly 0 in the categorical race
+ *     (index-first tie-breaking unchanged), the confidence of a sampled code uses the renormalised probability, and everything after
+ *     the draw is unchanged (known tokens kept, FLT_MAX confidence for them, mask_len, the k-th-smallest threshold, re-mask).
+ *   Both filters reduce to one per-row cutoff tau, the kept set being {j : l_j >= tau}; cutoff (f32 [batch*seq], may be NULL) receives
+ *     tau, -inf for a row with both filters off.
+ * The nucleus mass is summed in 64-bit fixed point (exp(l_j - max) * 2^40, truncated), so the result is the same bits run to run.
+ * The Philox stream is muse_sample_step's: a draw belongs to (row, code, step) whether the code is kept or not, and with both
+ * filters off the results are muse_sample_step's bit for bit.  2 <= seq <= 4096 and vocab <= 16384 (else MUSE_ERR_UNSUPPORTED);
+ * top_k < 1, or top_p outside (0, 1] or NaN: MUSE_ERR_BAD_ARG. */
+int muse_sample_step_filtered(const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride, int64_t ld,
+                              int32_t vocab, const int64_t* input_ids, int64_t mask_id, const float* noise_exp, const float* noise_u,
+                              uint64_t seed, uint32_t step, float temperature, int32_t sched_mask_len, int32_t batch, int32_t seq,
+                              int64_t* raw_sampled, int64_t* sampled, int64_t* next_ids, float* conf_scratch, int32_t top_k, float top_p,
+                              float* cutoff, void* stream);
+
 /* training/train_muse.py:149-226 mask_or_random_replace_tokens on the device.  mask_prob = cos(pi/2 t) clipped to
  * min_masking_rate (timesteps given) or mask_prob_in as is (the eval_mask_ratios branch); k = round(seq * mask_prob) >= 1;
  * mask = argsort(noise) < k (noise given) or the rectangle rects[b] = (y0, x0, h, w) on the sqrt(seq) grid (contiguous-region

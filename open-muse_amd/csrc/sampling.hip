@@ -2,6 +2,7 @@
 //   muse_sample_step   - one iteration of MaskGit parallel decoding (muse/modeling_transformer.py:1409-1454 and
 //                        muse/modeling_transformer_v2.py:434-474 with muse/sampling.py:30-35): classifier-free-guidance mix,
 //                        softmax, categorical sample, confidence with Gumbel noise, k-th-smallest threshold, re-mask
+//   muse_sample_step_filtered - the same step sampling from a top-k / nucleus (top-p) truncated distribution
 //   muse_mask_tokens   - training/train_muse.py:149-226 mask_or_random_replace_tokens (random or contiguous-region masks,
 //                        labels / loss weights variants)
 //   muse_cond_dropout  - training/train_muse.py:715-731 (conditioning dropout for classifier-free guidance)
@@ -15,27 +16,159 @@
 __device__ __forceinline__ float clamp_log(float t) { return logf(fmaxf(t, 1e-20f)); }   // muse/sampling.py:9-10
 
 // =================================================================================================================
-// phase 1: one wave per (image, position) row
+// truncated sampling (muse_sample_step_filtered): the per-row cutoff of top-k / nucleus filtering, found without sorting the row
 // =================================================================================================================
+// order-preserving 32-bit key of a logit: a > b  <=>  key(a) > key(b)  (-0 shares +0's key, as it compares equal)
+__device__ __forceinline__ uint32_t order_key(float f) {
+  const uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+// a wave's histogram lives in its own 256 bins: its lanes run in lockstep and the LDS serves one wave's instructions in order,
+// so the fence (no reordering by the compiler, LDS counter drained) is all the synchronisation there is
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// sum over the lanes above this one (lane 63: 0) of a per-lane value
+template <typename T> __device__ __forceinline__ T lanes_above_sum(T own, int lane) {
+  T incl = own;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_down(incl, o, 64);
+    if (lane + o < 64) incl += t;
+  }
+  return incl - own;
+}
+
+// The cutoff tau of one row, kept set = {j : logit_j >= tau}; one wave, `cnt` / `mass` its 256 LDS bins.  Radix descent over
+// order_key, one byte per level: each level re-reads the row (L2), histograms the byte below the prefix found so far over the codes
+// that carry the prefix, and picks one bin; lane l owns bins 4 l .. 4 l + 3.  Everything is integer arithmetic, so the result does not
+// depend on the order the LDS adds land in:
+//   top-k    the bin that holds the k-th largest key (counts);
+//   nucleus  over the codes the top-k set keeps, with mass e_j = trunc(exp(logit_j - max) * 2^40) (at most 2^54 a row): the lowest
+//            non-empty bin whose mass above it, A, has A < top_p * sum_j e_j - its largest code has M_gt < top_p, the largest code
+//            of the next non-empty bin below has not.  Tied logits share a key, hence a bin at every level.
+template <typename L>
+__device__ __forceinline__ float filter_cutoff(L logit, int V, int lane, int top_k, float top_p, float m, unsigned* cnt,
+                                               unsigned long long* mass) {
+  uint32_t kmin = 0;   // keys below are filtered
+  if (top_k == 1) kmin = order_key(m);
+  else if (top_k > 0) {
+    uint32_t prefix = 0;
+    int need = top_k;   // rank still to descend among the codes that carry the prefix
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      *(uint4*)(cnt + 4 * lane) = uint4{0u, 0u, 0u, 0u};
+      wave_lds_sync();
+      for (int j = lane; j < V; j += 64) {
+        const uint32_t key = order_key(logit(j));
+        if (shift == 24 || (key >> (shift + 8)) == prefix) atomicAdd(cnt + ((key >> shift) & 255u), 1u);
+      }
+      wave_lds_sync();
+      const uint4 h4 = *(const uint4*)(cnt + 4 * lane);
+      const int h[4] = {(int)h4.x, (int)h4.y, (int)h4.z, (int)h4.w};
+      int above = lanes_above_sum(h[0] + h[1] + h[2] + h[3], lane);
+      int b = -1, nb = 0;
+#pragma unroll
+      for (int i = 3; i >= 0; --i) {
+        if (above < need && need <= above + h[i]) { b = 4 * lane + i; nb = need - above; }
+        above += h[i];
+      }
+      const unsigned long long hit = __ballot(b >= 0);   // exactly one lane: 1 <= need <= the number of codes under the prefix
+      const int src = hit ? __ffsll(hit) - 1 : 0;
+      b = max(__shfl(b, src, 64), 0);
+      need = __shfl(nb, src, 64);
+      prefix = (prefix << 8) | (uint32_t)b;
+    }
+    kmin = prefix;
+  }
+  if (top_p < 1.0f) {
+    const uint32_t kk = kmin;
+    uint32_t prefix = 0;
+    unsigned long long base = 0;   // mass of the codes above every code that carries the prefix
+    double target = 0.0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      *(uint4*)(cnt + 4 * lane) = uint4{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mass[4 * lane + i] = 0ull;
+      wave_lds_sync();
+      for (int j = lane; j < V; j += 64) {
+        const float l = logit(j);
+        const uint32_t key = order_key(l);
+        if (key >= kk && (shift == 24 || (key >> (shift + 8)) == prefix)) {
+          const uint32_t bin = (key >> shift) & 255u;
+          atomicAdd(cnt + bin, 1u);
+          atomicAdd(mass + bin, (unsigned long long)(expf(l - m) * 0x1p40f));
+        }
+      }
+      wave_lds_sync();
+      const uint4 h4 = *(const uint4*)(cnt + 4 * lane);
+      const unsigned h[4] = {h4.x, h4.y, h4.z, h4.w};
+      unsigned long long e[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) e[i] = mass[4 * lane + i];
+      const unsigned long long own = e[0] + e[1] + e[2] + e[3];
+      unsigned long long a = lanes_above_sum(own, lane);
+      if (shift == 24) target = (double)top_p * (double)__shfl(a + own, 0, 64);   // lane 0's inclusive sum: the whole row
+      a += base;
+      int b = -1;
+      unsigned long long ab = 0;
+#pragma unroll
+      for (int i = 3; i >= 0; --i) {   // high to low: the lowest bin that qualifies stays
+        if (h[i] && (double)a < target) { b = 4 * lane + i; ab = a; }
+        a += e[i];
+      }
+      const unsigned long long hit = __ballot(b >= 0);   // never empty: the bin of the row's (or the prefix's) largest code qualifies
+      const int src = hit ? __ffsll(hit) - 1 : 0;        // the lowest lane owns the lowest bins
+      b = max(__shfl(b, src, 64), 0);
+      base = __shfl(ab, src, 64);
+      prefix = (prefix << 8) | (uint32_t)b;
+    }
+    kmin = prefix;
+  }
+  return key_value(kmin);
+}
+
+// =================================================================================================================
+// phase 1: one wave per (image, position) row.  FILTERED (muse_sample_step_filtered with a filter on): codes below the row's
+// cutoff take the logit -inf - probability exactly 0 in the sum, the race and the confidence; top_k 0 / top_p 1: that filter is off
+// =================================================================================================================
+template <bool FILTERED>
 __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ cond, const float* __restrict__ uncond, float guidance,
                                                           int64_t img_stride, int64_t ld, int seq, int V, const int64_t* __restrict__ input_ids, int64_t mask_id,
                                                           const float* __restrict__ noise_exp, const float* __restrict__ noise_u,
                                                           uint64_t seed, uint32_t step, float temperature, int64_t rows,
-                                                          int64_t* __restrict__ raw_ids, int64_t* __restrict__ ids, float* __restrict__ conf) {
+                                                          int64_t* __restrict__ raw_ids, int64_t* __restrict__ ids, float* __restrict__ conf,
+                                                          int top_k, float top_p, float* __restrict__ cutoff) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
   const int64_t img = row / seq, pos = row - img * seq;
   const float* c = cond + img * img_stride + pos * ld;
   const float* u = uncond ? uncond + img * img_stride + pos * ld : nullptr;
-  auto logit = [&](int j) {
+  auto mixed = [&](int j) {
     if (!u) return c[j];
     const float uu = u[j];
-    return __fadd_rn(uu, __fmul_rn(guidance, __fsub_rn(c[j], uu)));   // uncond + scale * (cond - uncond), three roundings (:403)
+    // uncond + scale * (cond - uncond) (:403).  (The _rn forms are plain operators in HIP: the multiply and the add compile to one fma.)
+    return __fadd_rn(uu, __fmul_rn(guidance, __fsub_rn(c[j], uu)));
   };
   float m = -INFINITY;
-  for (int j = lane; j < V; j += 64) m = fmaxf(m, logit(j));
+  for (int j = lane; j < V; j += 64) m = fmaxf(m, mixed(j));
   m = wave_max(m);
+  float tau = -INFINITY;
+  if constexpr (FILTERED) {
+    __shared__ alignas(16) unsigned cnt[4][256];
+    __shared__ alignas(16) unsigned long long mass[4][256];
+    tau = filter_cutoff(mixed, V, lane, top_k, top_p, m, cnt[threadIdx.x >> 6], mass[threadIdx.x >> 6]);
+  }
+  if (cutoff && lane == 0) cutoff[row] = tau;
+  auto logit = [&](int j) {
+    const float l = mixed(j);
+    if constexpr (FILTERED) return l < tau ? -INFINITY : l;
+    else return l;
+  };
   float s = 0.f;
   for (int j = lane; j < V; j += 64) s += expf(logit(j) - m);
   s = wave_sum(s);
@@ -122,22 +255,49 @@ __global__ __launch_bounds__(256) void remask_kernel(const int64_t* __restrict__
   }
 }
 
-extern "C" int muse_sample_step(const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride, int64_t ld,
-                                int32_t vocab,
-                                const int64_t* input_ids, int64_t mask_id, const float* noise_exp, const float* noise_u,
-                                uint64_t seed, uint32_t step, float temperature, int32_t sched_mask_len, int32_t batch, int32_t seq,
-                                int64_t* raw_sampled, int64_t* sampled, int64_t* next_ids, float* conf_scratch, void* stream) {
+static int sample_step_launch(bool filtered, const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride,
+                              int64_t ld, int32_t vocab, const int64_t* input_ids, int64_t mask_id, const float* noise_exp,
+                              const float* noise_u, uint64_t seed, uint32_t step, float temperature, int32_t sched_mask_len, int32_t batch,
+                              int32_t seq, int64_t* raw_sampled, int64_t* sampled, int64_t* next_ids, float* conf_scratch, int top_k,
+                              float top_p, float* cutoff, void* stream) {
   if (!cond_logits || !input_ids || !sampled || !next_ids || !conf_scratch || vocab <= 0) return MUSE_ERR_BAD_ARG;
   if (seq > 4096 || seq < 2) return MUSE_ERR_UNSUPPORTED;
   if (batch <= 0) return 0;
   const int64_t rows = (int64_t)batch * seq;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, cond_logits, uncond_logits, guidance_scale,
-                     img_stride, ld, seq, vocab, input_ids, mask_id, noise_exp, noise_u, seed, step, temperature, rows, raw_sampled, sampled, conf_scratch);
+  const auto rows_kernel = filtered ? sample_rows_kernel<true> : sample_rows_kernel<false>;
+  hipLaunchKernelGGL(rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st,
+                     cond_logits, uncond_logits, guidance_scale, img_stride, ld, seq, vocab, input_ids, mask_id, noise_exp, noise_u, seed, step,
+                     temperature, rows, raw_sampled, sampled, conf_scratch, top_k, top_p, cutoff);
   MUSE_CHECK_LAUNCH();
   hipLaunchKernelGGL(remask_kernel, dim3(batch), dim3(256), 0, st, input_ids, (const int64_t*)sampled, (const float*)conf_scratch,
                      next_ids, seq, mask_id, sched_mask_len);
   return (int)hipGetLastError();
+}
+
+extern "C" int muse_sample_step(const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride, int64_t ld,
+                                int32_t vocab,
+                                const int64_t* input_ids, int64_t mask_id, const float* noise_exp, const float* noise_u,
+                                uint64_t seed, uint32_t step, float temperature, int32_t sched_mask_len, int32_t batch, int32_t seq,
+                                int64_t* raw_sampled, int64_t* sampled, int64_t* next_ids, float* conf_scratch, void* stream) {
+  return sample_step_launch(false, cond_logits, uncond_logits, guidance_scale, img_stride, ld, vocab, input_ids, mask_id, noise_exp, noise_u,
+                            seed, step, temperature, sched_mask_len, batch, seq, raw_sampled, sampled, next_ids, conf_scratch, 0, 1.0f,
+                            nullptr, stream);
+}
+
+// The semantics of top_k / top_p / cutoff are stated once, at the prototype in include/muse_hip.h.  With both filters off this is
+// muse_sample_step's own kernel (plus the -inf cutoff), so the two agree bit for bit.
+extern "C" int muse_sample_step_filtered(const float* cond_logits, const float* uncond_logits, float guidance_scale, int64_t img_stride,
+                                         int64_t ld, int32_t vocab, const int64_t* input_ids, int64_t mask_id, const float* noise_exp,
+                                         const float* noise_u, uint64_t seed, uint32_t step, float temperature, int32_t sched_mask_len,
+                                         int32_t batch, int32_t seq, int64_t* raw_sampled, int64_t* sampled, int64_t* next_ids,
+                                         float* conf_scratch, int32_t top_k, float top_p, float* cutoff, void* stream) {
+  if (top_k < 1 || !(top_p > 0.0f && top_p <= 1.0f)) return MUSE_ERR_BAD_ARG;   // (a NaN top_p fails the comparison)
+  if (vocab > 16384) return MUSE_ERR_UNSUPPORTED;   // the row's fixed-point mass, at most vocab * 2^40, stays far inside 64 bits
+  const int k = top_k >= vocab ? 0 : top_k;
+  return sample_step_launch(k > 0 || top_p < 1.0f, cond_logits, uncond_logits, guidance_scale, img_stride, ld, vocab, input_ids, mask_id,
+                            noise_exp, noise_u, seed, step, temperature, sched_mask_len, batch, seq, raw_sampled, sampled, next_ids,
+                            conf_scratch, k, top_p, cutoff, stream);
 }
 
 // =================================================================================================================

@@ -790,11 +790,13 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
     @torch.no_grad()
     def generate2(self, input_ids=None, class_ids=None, encoder_hidden_states=None, negative_embeds=None, temperature=1.0,
                   timesteps=18, guidance_scale=0, noise_schedule=cosine_schedule, generator=None, noise=None, hip_graph=False,
-                  **kwargs):
+                  top_k=None, top_p=None, **kwargs):
         """-> sampled ids [B, num_vq_tokens].  `noise` (tests): per step a pair (exponential draws [B*S, codebook_size],
         uniform draws [B, S]) replacing the in-kernel Philox stream, e.g. the draws the reference's CPU generator produced.
         hip_graph=True captures the forward once (fixed input buffer) and replays it every step: one graph launch instead of
         ~12 kernel launches per layer - what small-batch decoding is bound by.
+        top_k / top_p: truncated sampling at every step (ops.sample_step states the semantics); `topk_filter_thres`, which the
+        reference's generate2 ignores as well, lands in **kwargs and stays without effect.
         Like the reference, `class_ids` is shifted by codebook_size IN PLACE (:1388-1389) and the temperature compounds
         across steps (:1451)."""
         cfg = self.config
@@ -835,7 +837,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
                                                     scheduled_mask_len(S, step, timesteps, noise_schedule),
                                                     uncond_logits=logits[B:, off:] if guided else None,
                                                     guidance_scale=float(guidance_scale) if guided else 0.0,
-                                                    noise_exp=q, noise_u=u, seed=seed, step=step)
+                                                    noise_exp=q, noise_u=u, seed=seed, step=step, top_k=top_k, top_p=top_p)
         return sampled
 
     def _decode_graph(self, B, S, device):

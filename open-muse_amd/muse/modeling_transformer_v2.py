@@ -812,12 +812,14 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
                   negative_embeds=None, negative_cond_embeds=None, temperature=1.0, timesteps=18, guidance_scale=0,
                   guidance_schedule=None, noise_schedule=cosine_schedule, generator=None, return_intermediate=False,
                   seq_len=None, use_tqdm=None, topk_filter_thres=None, noise_type=None, predict_all_tokens=None, noise=None,
-                  hip_graph=False):
+                  hip_graph=False, top_k=None, top_p=None):
         """reference :330-479 — iterative parallel decoding with classifier-free guidance.  Per step: one forward on the HIP
         path (batch doubled under guidance) and ONE device call for the guidance mix + everything token-level
         (muse_sample_step).  `noise` (tests): per step (exponential draws [B*S, codebook], uniform draws [B, S]) replacing the
         in-kernel Philox stream.  (The reference leaves `model_input` undefined for guidance_scale == 0; here that case feeds
-        input_ids.)  hip_graph=True captures the forward once on a fixed input buffer and replays it every step."""
+        input_ids.)  hip_graph=True captures the forward once on a fixed input buffer and replays it every step.
+        top_k / top_p: truncated sampling at every step (ops.sample_step states the semantics); `topk_filter_thres` is the reference's
+        legacy argument, ignored there and here."""
         B = encoder_hidden_states.shape[0]
         S = 256 if seq_len is None else seq_len
         dev = encoder_hidden_states.device
@@ -888,7 +890,8 @@ class MaskGiTUViT_v2(TapeOps, ModelMixin, ConfigMixin):
             sampled, input_ids, raw = ops.sample_step(out[:B], input_ids, mask_id, V, float(temperatures[step]),
                                                       scheduled_mask_len(S, step, timesteps, noise_schedule),
                                                       uncond_logits=out[B:] if guided else None, guidance_scale=float(scales[step]),
-                                                      noise_exp=q, noise_u=u, seed=seed, step=step, want_raw=return_intermediate)
+                                                      noise_exp=q, noise_u=u, seed=seed, step=step, want_raw=return_intermediate,
+                                                      top_k=top_k, top_p=top_p)
             if return_intermediate:
                 intermediate.append(raw)
         return (sampled, intermediate) if return_intermediate else sampled

@@ -1981,9 +1981,28 @@ def mask_sample(tokens, class_ids, timesteps, noise, mask_id, codebook_size, min
 
 
 def sample_step(cond_logits, input_ids, mask_id, vocab, temperature, sched_mask_len, *, uncond_logits=None, guidance_scale=0.0,
-                noise_exp=None, noise_u=None, seed=0, step=0, want_raw=False):
+                noise_exp=None, noise_u=None, seed=0, step=0, want_raw=False, top_k=None, top_p=None, want_cutoff=False):
     """one MaskGit decoding iteration (muse_sample_step): cond_logits [B, S, >= vocab] f32 view (last dim contiguous; a slice
-    that skips the class-token row is fine) -> (sampled [B,S], next_input_ids [B,S], raw samples or None)"""
+    that skips the class-token row is fine) -> (sampled [B,S], next_input_ids [B,S], raw samples or None)
+
+    Truncated sampling (muse_sample_step_filtered, taken when top_k or top_p is not None; vocab <= 16384), with l_j the logit of
+    code j < vocab after the guidance mix, rounded exactly as the plain step rounds it:
+      top_k (integer, 1 <= top_k): keep j iff l_j >= v_k, v_k the k-th largest value of the row; all ties at v_k are kept;
+        top_k >= vocab means off.
+      top_p (float, 0 < top_p <= 1): with p_j = softmax(l)_j over the codes that survive top_k, keep j iff the mass strictly above
+        it, M_gt(j) = sum over {i : l_i > l_j} of p_i, is < top_p; a group of tied logits is kept or dropped as a whole; the largest
+        logit is always kept; top_p == 1 means off.
+      Both given: top_k first, then the nucleus over the distribution renormalised on the top-k set.
+      Filtered codes behave exactly as if their logit were -inf before the step.
+    Both filters reduce to one per-row cutoff tau, the kept set being {j : l_j >= tau}; want_cutoff appends tau [B, S] f32 (-inf for
+    a row with both filters off) to the returned tuple."""
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
+        raise ValueError(f"sample_step: top_k must be an integer >= 1, got {top_k!r}")
+    if top_p is not None and not (isinstance(top_p, (int, float)) and not isinstance(top_p, bool) and 0.0 < top_p <= 1.0):
+        raise ValueError(f"sample_step: top_p must lie in (0, 1], got {top_p!r}")
+    filtered = top_k is not None or top_p is not None
+    if want_cutoff and not filtered:
+        raise ValueError("sample_step: want_cutoff needs top_k or top_p (top_k=vocab / top_p=1.0 turn a filter off)")
     require_gpu(cond_logits, input_ids)
     B, S = input_ids.shape
 
@@ -2003,11 +2022,17 @@ def sample_step(cond_logits, input_ids, mask_id, vocab, temperature, sched_mask_
         noise_exp = noise_exp.reshape(B * S, vocab).to(device=ids.device, dtype=torch.float32).contiguous()
     if noise_u is not None:
         noise_u = noise_u.reshape(B * S).to(device=ids.device, dtype=torch.float32).contiguous()
-    check(lib().muse_sample_step(cond_logits.data_ptr(), ptr(uncond_logits), float(guidance_scale), lay[0], lay[1], int(vocab),
-                                 ids.data_ptr(), int(mask_id), ptr(noise_exp), ptr(noise_u), int(seed) & (2 ** 64 - 1), int(step),
-                                 float(temperature), int(sched_mask_len), B, S, ptr(raw), sampled.data_ptr(), nxt.data_ptr(),
-                                 conf.data_ptr(), stream()), "muse_sample_step")
-    return sampled, nxt, raw
+    args = (cond_logits.data_ptr(), ptr(uncond_logits), float(guidance_scale), lay[0], lay[1], int(vocab), ids.data_ptr(), int(mask_id),
+            ptr(noise_exp), ptr(noise_u), int(seed) & (2 ** 64 - 1), int(step), float(temperature), int(sched_mask_len), B, S, ptr(raw),
+            sampled.data_ptr(), nxt.data_ptr(), conf.data_ptr())
+    if not filtered:
+        check(lib().muse_sample_step(*args, stream()), "muse_sample_step")
+        return sampled, nxt, raw
+    cutoff = torch.empty((B, S), dtype=torch.float32, device=ids.device) if want_cutoff else None
+    k = 2 ** 31 - 1 if top_k is None else min(top_k, 2 ** 31 - 1)
+    check(lib().muse_sample_step_filtered(*args, k, 1.0 if top_p is None else float(top_p), ptr(cutoff), stream()),
+          "muse_sample_step_filtered")
+    return (sampled, nxt, raw, cutoff) if want_cutoff else (sampled, nxt, raw)
 
 
 def mask_tokens(tokens, mask_id, *, timesteps=None, mask_prob=None, noise=None, rects=None, min_masking_rate=0.0, all_labels=False,

@@ -54,14 +54,17 @@ class PipelineMuse:
                  use_fp16: bool = False, noise_type="mask", predict_all_tokens=False, orig_size=(512, 512), crop_coords=(0, 0),
                  aesthetic_score=6.0, return_intermediate: bool = False, use_tqdm=True, transformer_seq_len=None,
                  clip_skip: int = None, output_type: str = "pil", empty_embeds: Optional[torch.Tensor] = None,
-                 empty_pooled_embeds: Optional[torch.Tensor] = None):
+                 empty_pooled_embeds: Optional[torch.Tensor] = None, top_k: Optional[int] = None, top_p: Optional[float] = None):
         """reference :66-243, same argument names and defaults.  Three executable paths: class-conditional MaskGitTransformer
         (`class_ids`), text-conditioned MaskGitTransformer on PRE-COMPUTED text states (`prompt_embeds`, `negative_prompt_embeds`),
         and MaskGiTUViT conditioned on PRE-COMPUTED text states (`prompt_embeds` [B, 77, D] + `pooled_embeds`
         [B, D], with `empty_embeds` / `empty_pooled_embeds` or the negative_* pair for classifier-free guidance).  `text=` is encoded
         by the pipeline's own `text_encoder` / `tokenizer` when the constructor was given them (`_encode_text`: the reference's calls).
         `temperature` may be the reference's (start, end) tuple: MaskGitTransformer.generate2 takes a float, so the tuple's first
-        entry is used there."""
+        entry is used there.
+        `topk_filter_thres` is the reference's legacy argument: its generate2 never reads it, and it stays ignored here.  The two that
+        act are `top_k` (keep the k most likely codes) and `top_p` (keep the smallest set of codes whose probability mass reaches p):
+        they truncate the distribution every decoding step samples from, on all three paths (ops.sample_step states the semantics)."""
         if text is None and class_ids is None and prompt_embeds is None:
             raise ValueError("Either text or class_ids must be provided.")
         if text is not None and class_ids is not None:
@@ -78,7 +81,7 @@ class PipelineMuse:
         ids, intermediate = self._generate(None, class_ids, prompt_embeds, pooled_embeds, negative_prompt_embeds, negative_pooled_embeds,
                                            empty_embeds, empty_pooled_embeds, timesteps, noise_schedule, guidance_scale, guidance_schedule,
                                            temperature, num_images_per_prompt, generator, orig_size, crop_coords, aesthetic_score,
-                                           return_intermediate, transformer_seq_len)
+                                           return_intermediate, transformer_seq_len, top_k, top_p)
         images = self._decode(ids, output_type)
         if intermediate is not None:
             return images, [self._decode(t, output_type) for t in intermediate]
@@ -123,7 +126,8 @@ class PipelineMuse:
     # ---- tokens from conditioning (shared by the inpainting pipeline, which starts from a partly masked token grid) --------------------------
     def _generate(self, input_ids, class_ids, prompt_embeds, pooled_embeds, negative_prompt_embeds, negative_pooled_embeds, empty_embeds,
                   empty_pooled_embeds, timesteps, noise_schedule, guidance_scale, guidance_schedule, temperature, num_images_per_prompt,
-                  generator, orig_size, crop_coords, aesthetic_score, return_intermediate=False, transformer_seq_len=None):
+                  generator, orig_size, crop_coords, aesthetic_score, return_intermediate=False, transformer_seq_len=None, top_k=None,
+                  top_p=None):
         from .sampling import get_mask_chedule
         schedule = get_mask_chedule(noise_schedule) if isinstance(noise_schedule, str) else noise_schedule
         start = {} if input_ids is None else {"input_ids": input_ids}
@@ -133,7 +137,7 @@ class PipelineMuse:
             class_ids = torch.as_tensor(class_ids, device=self.device, dtype=torch.long).repeat_interleave(num_images_per_prompt, dim=0)
             t0 = float(temperature[0]) if isinstance(temperature, (tuple, list)) else float(temperature)
             ids = self.transformer.generate2(class_ids=class_ids, timesteps=timesteps, temperature=t0, guidance_scale=guidance_scale,
-                                             noise_schedule=schedule, generator=generator, **start)
+                                             noise_schedule=schedule, generator=generator, top_k=top_k, top_p=top_p, **start)
             intermediate = None
         elif isinstance(self.transformer, MaskGitTransformer):
             # text-conditioned MaskGitTransformer on pre-computed text states (reference :207-243 hands the same keyword set to
@@ -146,7 +150,7 @@ class PipelineMuse:
             # negative_embeds are given (:1398-1402) - so does ours
             ids = self.transformer.generate2(encoder_hidden_states=rep(prompt_embeds), negative_embeds=rep(negative_prompt_embeds), timesteps=timesteps,
                                              temperature=t0, guidance_scale=guidance_scale, noise_schedule=schedule,
-                                             generator=generator, **start)
+                                             generator=generator, top_k=top_k, top_p=top_p, **start)
             intermediate = None
         else:
             n = num_images_per_prompt
@@ -165,7 +169,7 @@ class PipelineMuse:
                 negative_embeds=rep(negative_prompt_embeds), negative_cond_embeds=rep(negative_pooled_embeds), temperature=temp,
                 timesteps=timesteps, guidance_scale=guidance_scale, guidance_schedule=guidance_schedule, noise_schedule=schedule,
                 generator=generator, return_intermediate=return_intermediate, seq_len=seq,
-                use_tqdm=False, hip_graph=use_graph, **start)
+                use_tqdm=False, hip_graph=use_graph, top_k=top_k, top_p=top_p, **start)
             ids, intermediate = out if return_intermediate else (out, None)
         return ids, intermediate
 
@@ -268,9 +272,11 @@ class PipelineMuseInpainting(PipelineMuse):
                  image_size: int = 256, orig_size=(256, 256), crop_coords=(0, 0), aesthetic_score=6.0,
                  prompt_embeds: Optional[torch.Tensor] = None, pooled_embeds: Optional[torch.Tensor] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, negative_pooled_embeds: Optional[torch.Tensor] = None,
-                 empty_embeds: Optional[torch.Tensor] = None, empty_pooled_embeds: Optional[torch.Tensor] = None, output_type: str = "pil"):
+                 empty_embeds: Optional[torch.Tensor] = None, empty_pooled_embeds: Optional[torch.Tensor] = None, output_type: str = "pil",
+                 top_k: Optional[int] = None, top_p: Optional[float] = None):
         """same arguments as the reference; in addition the pre-computed text states PipelineMuse takes, and `image` may already be a
-        [3, H, W] tensor in [0, 1].  `mask`: bool [tokens] (or [h, w]) over the token grid, True = repaint"""
+        [3, H, W] tensor in [0, 1].  `mask`: bool [tokens] (or [h, w]) over the token grid, True = repaint.  `topk_filter_thres` is the
+        reference's legacy argument and stays ignored; `top_k` / `top_p` truncate the sampling distribution as in PipelineMuse."""
         assert use_maskgit_generate
         if text is None and class_ids is None and prompt_embeds is None:
             raise ValueError("Either text or class_ids must be provided.")
@@ -292,6 +298,6 @@ class PipelineMuseInpainting(PipelineMuse):
         tokens = tokens.repeat(batch * num_images_per_prompt, 1)
         ids, _ = self._generate(tokens, class_ids, prompt_embeds, pooled_embeds, negative_prompt_embeds, negative_pooled_embeds,
                                 empty_embeds, empty_pooled_embeds, timesteps, "cosine", guidance_scale, guidance_schedule, temperature,
-                                num_images_per_prompt, generator, orig_size, crop_coords, aesthetic_score)
+                                num_images_per_prompt, generator, orig_size, crop_coords, aesthetic_score, top_k=top_k, top_p=top_p)
         return self._decode(ids, output_type)
 
