@@ -520,7 +520,7 @@ class MaskGitTransformer(GeneralMaskGitEngine, ModelMixin, ConfigMixin):
                 ops.gemm(Pd, qkv, ctx, S, hd, S, la=0, lb=1, lda=Sp, ldb=3 * H, ldc=H, b_off=2 * H, batch=B * nh, zdiv=nh,
                          sA=(nh * S * Sp, S * Sp), sB=(S * 3 * H, hd), sC=(S * H, hd))
             ao = ops.linear(ctx, w_out)
-            if ops.layernorm_pair_ok(ao, x, cd, 1):   # both LayerNorms in one pass (bit-identical to the two calls below)
+            if ops.layernorm_pair_ok(ao, x, cd, 1):   # both LayerNorms in one pass (the two calls below up to the last f32 bit of x1)
                 x1, mu_p, rs_p, ln2, mu2, rs2 = ops.layernorm_pair_fwd(ao, x, w_post, w_pre, eps)
             else:
                 x1, mu_p, rs_p = ops.layernorm_fwd(ao, w_post, eps, torch.float32, residual=x)   # x + LN(attn)  (:882-884)
