@@ -939,6 +939,22 @@ int muse_masked_mean_probs(const void* logits, int32_t dtype, const int64_t* inp
                            float* mean_probs, float* entropy, int32_t batch, int32_t seq, int32_t vocab, int64_t ld, int64_t mask_id,
                            void* stream);
 
+/* ---- feature statistics for the Frechet distance on CLIP image embeds (moments.hip; muse/frechet.py: FeatureStats.update) - the
+ * accumulation behind the reference's fid.compute_fid (scripts/calculate_fid.py:215-220, tabulated by benchmark/model_quality.py:18-60), on the features of
+ * muse.CLIPImageEncoder instead of an Inception network.
+ * muse_moments_f64: for x f32 [n, d] with row stride ldx >= d (elements), IN PLACE,
+ *     sum[i]      += sum_n (double)x[n][i]                        sum f64 [d]
+ *     outer[i][j] += sum_n (double)x[n][i] * (double)x[n][j]      outer f64 [d, d] row-major, j >= i only
+ *   The strict lower triangle of outer is neither read nor written.  Products are formed in f64 from the converted f32 values and are
+ *   therefore exact (24 + 24 < 53 bits); only the additions round, one rounding each, on v_mfma_f64_16x16x4_f64.  One workgroup per
+ *   64 x 64 tile of the upper triangle, every output element owned by one lane, no atomics, no workspace.  Rows are consumed in ascending
+ *   order in groups of four counted from row 0 of the call, a ragged last group padded with zeros (not with clamped addresses): equal
+ *   call sequences give equal bits.  inf / NaN propagate as in x^T x.  No byte of x outside the n rows' first d columns is read.
+ *   d <= 0, d % 4 != 0, n < 0, ldx < d or a NULL pointer: MUSE_ERR_BAD_ARG.  x not 16-byte aligned, sum or outer not 8-byte aligned:
+ *   MUSE_ERR_ALIGN.  More than 2^31 - 1 tiles (d > 4,194,240): MUSE_ERR_UNSUPPORTED.  A refused call launches and writes nothing.
+ *   n == 0 (with valid arguments) returns 0 and launches nothing. */
+int muse_moments_f64(const float* x, int64_t n, int32_t d, int64_t ldx, double* sum, double* outer, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

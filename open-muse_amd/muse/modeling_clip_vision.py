@@ -352,12 +352,23 @@ class CLIPScorer:
         return embeds
 
     @torch.no_grad()
-    def __call__(self, images=None, text=None, input_ids=None, text_embeds=None, pixel_values=None):
+    def image_embeds(self, images=None, pixel_values=None):
+        """the image half of `__call__` on its own: [B, projection_dim] f32 on the device, un-normalised as the tower returns them - the
+        features `accumulate` feeds to a muse.FeatureStats"""
         if (images is None) == (pixel_values is None):
             raise ValueError("CLIPScorer: pass exactly one of images= and pixel_values=")
         if pixel_values is None:
             pixel_values = self.preprocess(images)
-        image_embeds = self.image_encoder(pixel_values).image_embeds
+        return self.image_encoder(pixel_values).image_embeds
+
+    def accumulate(self, stats, images=None, pixel_values=None):
+        """embed a batch and add it to `stats` (a muse.FeatureStats of the tower's projection_dim, on the same device) for a Frechet
+        distance on CLIP image embeds (muse/frechet.py): the embeds go straight into `stats.update`, nothing visits the host"""
+        return stats.update(self.image_embeds(images=images, pixel_values=pixel_values))
+
+    @torch.no_grad()
+    def __call__(self, images=None, text=None, input_ids=None, text_embeds=None, pixel_values=None):
+        image_embeds = self.image_embeds(images=images, pixel_values=pixel_values)
         if text_embeds is None:
             text_embeds = self._text_embeds(text, input_ids, image_embeds.device)
         cosine, logits = clip_scores(image_embeds, text_embeds, self.image_encoder.logit_scale.data)

@@ -3077,3 +3077,29 @@ def l2_normalize_rows(x, mult=None, log_mult=None, out=None):
                                        ptr(log_mult), stream()), "muse_l2_normalize_rows")
     _prof_end(e0, "l2_normalize_rows", _nbytes(x, out), "byte")
     return _touched(out)
+
+
+# ---- feature statistics (csrc/moments.hip; muse.FeatureStats): the accumulation behind the Frechet distance on CLIP image embeds ---------
+def moments_f64_(x, sum, outer):
+    """sum f64 [d] += column sums of x, outer f64 [d, d] += x^T x on its upper triangle and diagonal (the strict lower triangle is
+    neither read nor written), both IN PLACE, in f64 from exact products, in one launch (muse_moments_f64).  x: f32 [n, d], unit stride
+    along a row and any row stride >= d (a column slice of a wider matrix is fine), d a multiple of 4, 16-byte aligned; n = 0 is a
+    no-op.  Equal call sequences give equal bits."""
+    require_gpu(x, sum, outer)
+    if x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _hip.MuseHipError(f"moments_f64_: x is an f32 [n, d] tensor with contiguous rows, got {x.dtype} {tuple(x.shape)} strides {tuple(x.stride())}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    ldx = int(x.stride(0)) if n > 1 else d
+    if d < 1 or d % 4 or ldx < d:
+        raise _hip.MuseHipError(f"moments_f64_: the width {d} is a positive multiple of 4 and the row stride {ldx} is at least the width")
+    if sum.dtype != torch.float64 or tuple(sum.shape) != (d,) or not sum.is_contiguous():
+        raise _hip.MuseHipError(f"moments_f64_: sum is a contiguous f64 [{d}] tensor, got {sum.dtype} {tuple(sum.shape)}")
+    if outer.dtype != torch.float64 or tuple(outer.shape) != (d, d) or not outer.is_contiguous():
+        raise _hip.MuseHipError(f"moments_f64_: outer is a contiguous f64 [{d}, {d}] tensor, got {outer.dtype} {tuple(outer.shape)}")
+    if n == 0:                  # an empty tensor has no storage to point at
+        return outer
+    e0 = _prof_begin()
+    check(lib().muse_moments_f64(x.data_ptr(), n, d, ldx, sum.data_ptr(), outer.data_ptr(), stream()), "muse_moments_f64")
+    _prof_end(e0, "moments_f64", float(n) * d * (d + 1), "flop")
+    _touched(sum)
+    return _touched(outer)
