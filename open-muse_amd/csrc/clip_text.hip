@@ -49,7 +49,10 @@ __global__ __launch_bounds__(256) void bias_quick_gelu_kernel(const T* x, const 
 }
 
 // LayerNorm with weight AND bias (nn.LayerNorm: CLIPEncoderLayer.layer_norm1 / 2, final_layer_norm), f32 in, one wave per row:
-// mean, then the variance of the centred values, then (x - mean) * rstd * w + b in one pass over the row
+// mean, then the variance of the centred values, then (x - mean) * rstd * w + b in one pass over the row.  Everything is taken
+// relative to the row's first element: d = x - x[0] is exact for a row whose values lie within a factor of two of each other, so a
+// row with |mean| >> std (1e3 + N(0, 1)) keeps the digits an f32 mean of the raw values cannot hold (the mean alone would be off by
+// up to ulp(1e3) / 2 = 3e-5 of the std); the centred value is d - mean(d).  A constant row gives d = 0 and the bias, exactly.
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_bias_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                              T* __restrict__ y, long rows, int cols, float eps) {
@@ -57,13 +60,14 @@ __global__ __launch_bounds__(256) void layernorm_bias_kernel(const float* __rest
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* xr = x + row * cols;
+  const float x0 = xr[0];
   float s = 0.f;
-  for (int c = lane; c < cols; c += 64) s += xr[c];
-  const float mean = wave_sum(s) / (float)cols;
+  for (int c = lane; c < cols; c += 64) s += xr[c] - x0;
+  const float dmean = wave_sum(s) / (float)cols;   // mean - x0
   float q = 0.f;
-  for (int c = lane; c < cols; c += 64) { const float t = xr[c] - mean; q = fmaf(t, t, q); }
+  for (int c = lane; c < cols; c += 64) { const float t = (xr[c] - x0) - dmean; q = fmaf(t, t, q); }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)cols + eps);
-  for (int c = lane; c < cols; c += 64) Elem<T>::store(y + row * cols + c, (xr[c] - mean) * rstd * w[c] + b[c]);
+  for (int c = lane; c < cols; c += 64) Elem<T>::store(y + row * cols + c, ((xr[c] - x0) - dmean) * rstd * w[c] + b[c]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

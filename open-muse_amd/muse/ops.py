@@ -2745,6 +2745,9 @@ def layernorm_bias_fwd(x, w, b, eps, out_dtype):
     rows, cols = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise _hip.MuseHipError("layernorm_bias_fwd: x is a contiguous f32 [rows, cols] tensor")
+    for name, t in (("w", w), ("b", b)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (cols,) or not t.is_contiguous():
+            raise _hip.MuseHipError(f"layernorm_bias_fwd: {name} is a contiguous f32 [{cols}] tensor, got {t.dtype} {tuple(t.shape)}")
     y = torch.empty((rows, cols), dtype=out_dtype, device=x.device)
     check(lib().muse_layernorm_bias_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), dt(y), rows, cols, eps, stream()),
           "muse_layernorm_bias_fwd")

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import weights as W
+from objective_cpu import f64_reference
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -112,20 +113,9 @@ def _config_b_inputs(seed=3):
 
 
 def _f64_reference(logits, labels, soft, S1, K, g):
-    rows = logits.shape[0]
-    x = logits[:, :K].double()
-    s = torch.arange(rows, device=DEV) % S1
-    b = torch.arange(rows, device=DEV) // S1
-    active = (s >= 1) & (labels != -100)
-    srow = (b * (S1 - 1) + s - 1).clamp(min=0)
-    p = soft.double()[srow]
-    logp = torch.log_softmax(x, dim=-1)
-    row = -(p * logp).sum(-1)
-    n = int(active.sum())
-    loss = float(row[active].sum()) / n
-    grad = g / n * (torch.exp(logp) * p.sum(-1, keepdim=True) - p)
-    grad[~active] = 0.0
-    return loss, grad, active
+    """the float64 restatement of the documented contract, shared with tests/test_gpu_objective_edges.py"""
+    ref = f64_reference(logits, labels, soft, S1, K, g)
+    return ref["loss"], ref["grad"], ref["active"]
 
 
 def test_soft_ce_kernels_at_config_b_size():
