@@ -955,6 +955,36 @@ int muse_masked_mean_probs(const void* logits, int32_t dtype, const int64_t* inp
  *   n == 0 (with valid arguments) returns 0 and launches nothing. */
 int muse_moments_f64(const float* x, int64_t n, int32_t d, int64_t ldx, double* sum, double* outer, void* stream);
 
+/* ---- Gaussian-kernel pair sums for the maximum mean discrepancy on CLIP image embeds (mmd.hip; muse/mmd.py: mmd_distance,
+ * cmmd_distance - CMMD of Jayasumana et al., "Rethinking FID", CVPR 2024).  All arithmetic is f64 on the converted f32 features; a
+ * product of two converted values is exact, so inside a dot product only the additions round.  No n x m matrix is ever written.
+ * muse_row_norms_f64: x f32 [n, d], row stride ldx >= d (elements).  sumsq[i] = sum_k (double)x_ik^2 (one wave per row: lane l adds
+ *   features 4 l + 256 t + (0 .. 3), t ascending, by fma of the exact squares, then a butterfly over the 64 lanes - an order fixed by d
+ *   alone); rinv (NULL = skip) [i] = 1.0 / sqrt(sumsq[i]), IEEE sqrt and quotient.  A zero row gives rinv = inf, and NaN in whatever
+ *   multiplies it by that row: not guarded.
+ * muse_rbf_pair_sums_f64: with c_ij = (rx_i ry_j) sum_k (double)x_ik (double)y_jk, a_i = (rx_i rx_i) sum_k x_ik^2, b_j likewise from y,
+ *   k_ij = exp(-gamma ((a_i + b_j) - 2 c_ij)) - no clamp of the squared distance at 0.  rx / ry f64 [n] / [m]; NULL = a factor of 1,
+ *   bit-identical to an array of ones.
+ *     y != NULL (rectangular): out[0] = sum_{i < n, j < m} k_ij, out[1] = 0
+ *     y == NULL (symmetric; ry, m, ldy ignored): only tiles on or above the diagonal are computed, out[0] = sum_{i < j} k_ij,
+ *       out[1] = sum_i k_ii as computed (not assumed 1): the full sum is 2 out[0] + out[1]
+ *   One workgroup of four waves per 64 x 64 tile of pairs on v_mfma_f64_16x16x4_f64 with K along the feature axis (a lane loads 16
+ *   contiguous bytes of its row per step of 16 features; the order of k in a dot product is a fixed permutation, the same for both
+ *   operands).  A row >= n or a column >= m is excluded from the sums by predicate; loads beyond n, m or d are predicated off, never a
+ *   clamped address.  Every wave writes its partial(s) to `workspace` (muse_rbf_pair_sums_workspace(n, m, symmetric) doubles: 4 per
+ *   tile, twice that when symmetric), a second launch of one workgroup adds them in a fixed order: no floating-point atomics, equal
+ *   calls give equal bits, and the bits do not depend on ldx / ldy.  inf / NaN features give NaN sums.
+ *   gamma is read from HOST memory at the call (one f64; the prototype check of this header knows no by-value double).
+ *   Because a lane loads a float4, rows must start 16-byte aligned: x, y 16-byte aligned AND ldx, ldy multiples of 4, else MUSE_ERR_ALIGN;
+ *   rx, ry, workspace, out (sumsq, rinv) 8-byte aligned, else MUSE_ERR_ALIGN.  d <= 0, d % 4 != 0, n < 0, m < 0, a stride < d, a NULL x /
+ *   gamma / workspace / out (sumsq): MUSE_ERR_BAD_ARG.  More than 2^31 - 1 tiles (or row blocks): MUSE_ERR_UNSUPPORTED.  A refused call
+ *   launches and writes nothing.  n == 0 or m == 0 (with valid arguments): out = {0, 0}, no pair kernel.
+ * muse_rbf_pair_sums_workspace: the number of f64 partials, or a negative MUSE_ERR_* for negative sizes / too many tiles. */
+int muse_row_norms_f64(const float* x, int64_t n, int32_t d, int64_t ldx, double* sumsq, double* rinv, void* stream);
+int64_t muse_rbf_pair_sums_workspace(int64_t n, int64_t m, int32_t symmetric);
+int muse_rbf_pair_sums_f64(const float* x, int64_t n, int64_t ldx, const double* rx, const float* y, int64_t m, int64_t ldy,
+                           const double* ry, int32_t d, const double* gamma, double* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,8 +246,11 @@ SIGNATURES = {
     "muse_masked_row_mean": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p],
     "muse_masked_mean_probs": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_i64, c_i64, c_void_p],
     "muse_moments_f64": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_void_p],
+    "muse_row_norms_f64": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_void_p],
+    "muse_rbf_pair_sums_workspace": [c_i64, c_i64, c_int],
+    "muse_rbf_pair_sums_f64": [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
 }
-_RESTYPES = {"muse_embed_bwd_scratch_floats": c_i64, "muse_embed_bwd2_scratch_bytes": c_i64}
+_RESTYPES = {"muse_embed_bwd_scratch_floats": c_i64, "muse_embed_bwd2_scratch_bytes": c_i64, "muse_rbf_pair_sums_workspace": c_i64}
 
 
 class MuseHipError(RuntimeError):

@@ -363,7 +363,8 @@ class CLIPScorer:
 
     def accumulate(self, stats, images=None, pixel_values=None):
         """embed a batch and add it to `stats` (a muse.FeatureStats of the tower's projection_dim, on the same device) for a Frechet
-        distance on CLIP image embeds (muse/frechet.py): the embeds go straight into `stats.update`, nothing visits the host"""
+        distance on CLIP image embeds (muse/frechet.py), or a muse.FeatureBank for the MMD / CMMD on them (muse/mmd.py): the embeds go
+        straight into `stats.update`, nothing visits the host"""
         return stats.update(self.image_embeds(images=images, pixel_values=pixel_values))
 
     @torch.no_grad()

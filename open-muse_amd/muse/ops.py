@@ -3106,3 +3106,80 @@ def moments_f64_(x, sum, outer):
     _prof_end(e0, "moments_f64", float(n) * d * (d + 1), "flop")
     _touched(sum)
     return _touched(outer)
+
+
+# ---- Gaussian-kernel pair sums (csrc/mmd.hip; muse.mmd_distance): the sums behind the maximum mean discrepancy on CLIP image embeds --------
+def _mmd_rows(name, what, x):
+    """x: f32 [n, d], unit stride along a row, d a positive multiple of 4, every row 16-byte aligned -> (n, d, ld)"""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise _hip.MuseHipError(f"{name}: {what} is an f32 [n, d] tensor with contiguous rows, got {getattr(x, 'dtype', type(x))} "
+                                f"{tuple(getattr(x, 'shape', ()))} strides {tuple(x.stride()) if torch.is_tensor(x) else ()}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    ld = int(x.stride(0)) if n > 1 else d
+    if d < 1 or d % 4 or ld < d:
+        raise _hip.MuseHipError(f"{name}: {what}: the width {d} is a positive multiple of 4 and the row stride {ld} is at least the width")
+    if n and (ld % 4 or x.data_ptr() % 16):
+        raise _hip.MuseHipError(f"{name}: {what}: every row starts 16-byte aligned (a lane loads a float4): row stride {ld} elements, "
+                                f"address % 16 = {x.data_ptr() % 16}")
+    return n, d, ld
+
+
+def _mmd_scales(name, what, r, n, like):
+    if r is None:
+        return
+    require_gpu(r)
+    if r.dtype != torch.float64 or tuple(r.shape) != (n,) or not r.is_contiguous() or r.device != like.device:
+        raise _hip.MuseHipError(f"{name}: {what} is a contiguous f64 [{n}] tensor on {like.device}, got {r.dtype} {tuple(r.shape)} "
+                                f"strides {tuple(r.stride())} on {r.device}")
+
+
+def row_norms_f64(x, want_rinv=True):
+    """x f32 [n, d] -> (sumsq, rinv): sumsq[i] = sum_k x_ik^2 in f64 from exact squares, rinv[i] = 1 / sqrt(sumsq[i]) (None unless
+    want_rinv); one launch (muse_row_norms_f64), no host synchronisation.  A zero row gives rinv = inf (and NaN downstream): not
+    guarded.  Rows as in rbf_pair_sums_f64."""
+    require_gpu(x)
+    n, d, ldx = _mmd_rows("row_norms_f64", "x", x)
+    sumsq = torch.empty(n, dtype=torch.float64, device=x.device)
+    rinv = torch.empty(n, dtype=torch.float64, device=x.device) if want_rinv else None
+    if n == 0:                  # an empty tensor has no storage to point at
+        return sumsq, rinv
+    e0 = _prof_begin()
+    check(lib().muse_row_norms_f64(x.data_ptr(), n, d, ldx, sumsq.data_ptr(), ptr(rinv), stream()), "muse_row_norms_f64")
+    _prof_end(e0, "row_norms_f64", _nbytes(x, sumsq) + (0 if rinv is None else _nbytes(rinv)), "byte")
+    return sumsq, rinv
+
+
+def rbf_pair_sums_f64(x, y=None, gamma=1.0, rx=None, ry=None):
+    """sums of k_ij = exp(-gamma |rx_i x_i - ry_j y_j|^2) over pairs of rows, in f64, without the n x m matrix (muse_rbf_pair_sums_f64:
+    the squared distance is (a_i + b_j) - 2 c_ij from exact products, not clamped at 0).  -> f64 [2] on the device, no host
+    synchronisation:
+        y given: [sum over all i < n, j < m, 0]
+        y None : [sum over i < j, sum over i == j] of x against itself; the full sum is 2 * out[0] + out[1]
+    x, y: f32 [n, d] / [m, d], unit stride along a row, any row stride >= d that is a multiple of 4, d a multiple of 4, 16-byte aligned.
+    rx, ry: None (a factor of 1) or contiguous f64 [n] / [m] (row_norms_f64's rinv for L2-normalised rows).  Equal calls give equal bits."""
+    require_gpu(x, y, rx, ry)
+    n, d, ldx = _mmd_rows("rbf_pair_sums_f64", "x", x)
+    _mmd_scales("rbf_pair_sums_f64", "rx", rx, n, x)
+    if y is None:
+        if ry is not None:
+            raise _hip.MuseHipError("rbf_pair_sums_f64: ry without y (the symmetric form scales both sides by rx)")
+        m, ldy = n, ldx
+    else:
+        m, dy, ldy = _mmd_rows("rbf_pair_sums_f64", "y", y)
+        if dy != d or y.device != x.device:
+            raise _hip.MuseHipError(f"rbf_pair_sums_f64: x and y have one width and one device, got {d} on {x.device} and {dy} on {y.device}")
+        _mmd_scales("rbf_pair_sums_f64", "ry", ry, m, x)
+    out = torch.zeros(2, dtype=torch.float64, device=x.device)
+    if n == 0 or m == 0:        # an empty tensor has no storage to point at
+        return out
+    count = int(lib().muse_rbf_pair_sums_workspace(n, m, 1 if y is None else 0))
+    if count < 0:
+        check(count, "muse_rbf_pair_sums_workspace")
+    workspace = torch.empty(count, dtype=torch.float64, device=x.device)
+    g = C.c_double(float(gamma))
+    e0 = _prof_begin()
+    check(lib().muse_rbf_pair_sums_f64(x.data_ptr(), n, ldx, ptr(rx), ptr(y), m, ldy, ptr(ry), d, C.addressof(g), workspace.data_ptr(),
+                                       out.data_ptr(), stream()), "muse_rbf_pair_sums_f64")
+    pairs = float(n) * (n + 1) / 2 if y is None else float(n) * m
+    _prof_end(e0, "rbf_pair_sums_f64", 2.0 * pairs * d, "flop")
+    return out
